@@ -1,7 +1,13 @@
 """Headline benchmark: denoising steps/sec of the SD1.5 512x512 Prompt-to-Prompt edit loop.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run does what the headline needs and nothing else: it sets up, warms up, times K steps of the headline mode, writes
+the latents of its last step if `--dump-outputs DIR` is given, and prints the JSON line (`metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step`, ...).  Everything else this program measures or checks (the in-run parity probe,
+roofline, edits in flight, the 1024x1024 step, PIE images/s, null-text, the other precision modes, the CPU baseline) runs only
+with `--full`, and then exactly as described below.
 
 The headline (`value`, `roofline`) is measured in the mode that meets north_star's tolerance -- edited images within 1e-3
 max-abs of the fp32 reference (`/root/reference/p2p/edit_syn.py:38` computes in fp32): `--precision f16x3`, fp32 storage with
@@ -131,7 +137,20 @@ def parse():
     ap.add_argument("--steps-1024", type=int, default=10, help="timed edit steps on 128x128 latents (0: skip)")
     ap.add_argument("--nti-images", type=int, default=1, help="BASELINE.json configs[1]: synthetic images timed through null-text "
                     "inversion + edit in the headline mode (0: skip)")
+    ap.add_argument("--full", action="store_true", help="also run everything beside the headline (parity probe, roofline, edits "
+                    "in flight, 1024x1024, PIE, null-text, other modes, CPU baseline); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the timed path computed "
+                    "in its last step (the edit's latents, float32) as DIR/<name>.npy")
     return ap.parse_args()
+
+
+def dump_outputs(job, out_dir, rank, world):
+    """the arrays a caller of the timed loop receives after its last step: the latents [2, 4, hw, hw] of the edit (source and
+    edited prompt), float32; 128 KiB at 512x512.  The inputs are seeded, so equal arguments give equal inputs in every run."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    name = "latents" if world == 1 else f"latents_rank{rank}"
+    np.save(os.path.join(out_dir, name + ".npy"), job.loop.result().float().cpu().numpy())
 
 
 def build_pipe(cfg_name, dev, rank, world, precision="f16"):
@@ -198,13 +217,15 @@ class EditJob:
         self.loop.rewind(self.x_T)
 
     def run_steps(self, n):
-        """n steps, restarting the edit (controller + step counters) whenever 50 are used up"""
+        """n steps, restarting the edit (controller, step counters and latents = x_T) whenever 50 are used up: every 50-step
+        stretch is the same edit.  (Restarting the schedule from the FINISHED latents instead feeds them back in at t = 981
+        on every lap, and they grow from lap to lap until they overflow.)"""
         done = 0
         while done < n:
             room = MAX_STEPS - self.ctrl.cur_step
             if room == 0:
                 self.ctrl.reset()
-                self.loop.rewind()
+                self.loop.rewind(self.x_T)
                 room = MAX_STEPS
             k = min(room, n - done)
             for _ in range(k):
@@ -279,6 +300,8 @@ def main():
             raise SystemExit("--split cfg runs one SD1.x / SD2.x edit on exactly two ranks (--gpus 2 under torchrun)")
         job = EditJob(pipe, cfg, ctx, hw, dev, rank, uncond_list, split_group=dist.group.WORLD)
         elapsed = job.timed(args.steps, args.warmup, barrier, dist, dev)
+        if args.dump_outputs and rank == 0:                # both ranks hold the same latents of the one edit
+            dump_outputs(job, args.dump_outputs, 0, 1)
         if rank == 0:
             print(json.dumps({
                 "metric": f"denoising steps/sec ({MODEL_NAMES.get(args.config, args.config)} {hw * 8}x{hw * 8} P2P edit step, ONE "
@@ -293,13 +316,16 @@ def main():
         dist.destroy_process_group()
         return
 
-    def measure(pipe_m, precision, steps, warmup, full):
-        """the numbers of ONE mode: K edit steps between barriers (+ in-flight throughput, roofline, 1024x1024, PIE if `full`)"""
+    def measure(pipe_m, precision, steps, warmup, full, dump_dir=None):
+        """the numbers of ONE mode: K edit steps between barriers (+ parity probe, roofline if `--full`; + in-flight throughput,
+        1024x1024, PIE if `full`)"""
         peak, dtype, what = MODES[precision]
         # parity first, measured in this run (every rank: same work in front of the timed region; raises beyond the bound)
-        probe = parity_probe(pipe_m, dev, precision) if (args.config, hw) == ("sd15", 64) and steps > 0 else None
+        probe = parity_probe(pipe_m, dev, precision) if args.full and (args.config, hw) == ("sd15", 64) and steps > 0 else None
         job = EditJob(pipe_m, cfg, ctx, hw, dev, rank, uncond_list)
         elapsed = job.timed(steps, warmup, barrier, dist, dev)
+        if dump_dir:                                       # before the roofline below turns this job's loop eager
+            dump_outputs(job, dump_dir, rank, world)
         value = world * steps / elapsed
         res = {"value": round(value, 3), "ms_per_step": round(elapsed / steps * 1e3, 3), "steps": steps, "dtype": dtype,
                "arithmetic": what}
@@ -314,7 +340,7 @@ def main():
             res["throughput_edits_in_flight"] = {
                 str(E): round(edits_in_flight(pipe_m, cfg, ctx, job.x_T, hw, E, dev, dist, barrier, world, rank, uncond_list), 3)
                 for E in [int(e) for e in args.in_flight.split(",") if e.strip()]}
-        if rank == 0:
+        if rank == 0 and args.full:
             register_job(pipe_m, job)
             res["roofline"] = roofline(job, value, world, args.config, precision)      # last use of this job: it ends eager
         job.close()
@@ -338,7 +364,7 @@ def main():
         return res, job
 
     # ---- headline mode
-    head, job = measure(pipe, args.precision, args.steps, args.warmup, True)
+    head, job = measure(pipe, args.precision, args.steps, args.warmup, args.full, dump_dir=args.dump_outputs)
     out = {
         "metric": f"denoising steps/sec ({MODEL_NAMES.get(args.config, args.config)} {hw * 8}x{hw * 8} P2P edit step, UNet batch 4)",
         "value": head["value"], "unit": "steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -358,7 +384,7 @@ def main():
 
     # ---- the other modes beside it (N = 1: they are context for the headline, not scaled)
     others = [m.strip() for m in args.other_modes.split(",") if m.strip() and m.strip() != args.precision]
-    if world == 1 and not cfg.addition_embed:
+    if args.full and world == 1 and not cfg.addition_embed:
         sd_host = pipe._state_dict
         for m in others:
             pipe_m, _ = build_pipe(args.config, dev, rank, world, precision=m)
@@ -376,7 +402,7 @@ def main():
         pipe._state_dict = sd_host
 
     if rank == 0:
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(pipe, cfg, ctx, job.x_T, job.ctrl, job.added, args.cpu_seconds)
             if "images_per_sec" in out:
                 # one PIE image = 50 inversion forwards at batch 1 + 50 edit steps at batch 4 (+ VAE, ignored here):

@@ -4,7 +4,7 @@
 TAG=${1:-r04}; LAT=${2:-0}
 ROOT=$(pwd); OUT=$ROOT/gpurun_out/prof_$TAG; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-HEAD="--steps 20 --warmup 5 --no-cpu-baseline --pie-images 0 --steps-1024 0 --other-modes= --in-flight= --precision f16x3"
+HEAD="--full --steps 20 --warmup 5 --no-cpu-baseline --pie-images 0 --steps-1024 0 --other-modes= --in-flight= --precision f16x3"
 [ "$LAT" != "0" ] && HEAD="$HEAD --latent $LAT --steps 6"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/k_$LAT -- python3 $ROOT/bench.py $HEAD > $OUT/k_$LAT.log 2>&1
 echo "trace rc=$?"

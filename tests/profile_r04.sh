@@ -6,7 +6,7 @@
 WHAT=${*:-trace nti pmc sq bench}
 ROOT=$(pwd); OUT=$ROOT/gpurun_out/prof_r04; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-HEAD="--steps 20 --warmup 5 --no-cpu-baseline --pie-images 0 --nti-images 0 --steps-1024 0 --other-modes= --in-flight="
+HEAD="--full --steps 20 --warmup 5 --no-cpu-baseline --pie-images 0 --nti-images 0 --steps-1024 0 --other-modes= --in-flight="
 if [[ " $WHAT " == *" trace "* ]]; then
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/k512_f16x3 -- python3 $ROOT/bench.py $HEAD --precision f16x3 > $OUT/k512_f16x3.log 2>&1; echo "k512 f16x3 rc=$?"
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/k1024_f16x3 -- python3 $ROOT/bench.py $HEAD --precision f16x3 --latent 128 --steps 6 > $OUT/k1024_f16x3.log 2>&1; echo "k1024 f16x3 rc=$?"
@@ -31,5 +31,5 @@ if [[ " $WHAT " == *" sq "* ]]; then
   echo "sq done"
 fi
 if [[ " $WHAT " == *" bench "* ]]; then
-  python3 bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "bench rc=$?"; tail -c 400 $OUT/bench_default.json
+  python3 bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "bench rc=$?"; tail -c 400 $OUT/bench_default.json
 fi

@@ -9,7 +9,7 @@ ROOT=$(pwd)
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-HEAD="--steps 20 --warmup 5 --no-cpu-baseline --pie-images 0 --steps-1024 0 --other-modes= --in-flight="
+HEAD="--full --steps 20 --warmup 5 --no-cpu-baseline --pie-images 0 --steps-1024 0 --other-modes= --in-flight="
 if [[ " $WHAT " == *" trace "* ]]; then
   for mode in f16x3 f16 f32; do
     steps=20; [ $mode = f32 ] && steps=6
@@ -37,7 +37,7 @@ if [[ " $WHAT " == *" pmc "* ]]; then
 fi
 cd $ROOT
 if [[ " $WHAT " == *" bench "* ]]; then
-  python3 bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
+  python3 bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
   echo "bench rc=$?"
   tail -c 300 $OUT/bench_default.json
 fi

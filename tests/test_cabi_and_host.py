@@ -1,6 +1,7 @@
 """CPU tests: the C-ABI library builds/loads and exports exactly what `include/ief_hip.h` declares; the
 binding refuses host tensors (no CPU fallback); module tree + hook registration; sharding + weight
 broadcast over a 2-process gloo group."""
+import json
 import os
 import re
 import sys
@@ -95,27 +96,46 @@ def test_module_tree_and_registration(cpu_unet):
         cpu_unet(torch.zeros(1, 4, 16, 16), 1, encoder_hidden_states=torch.zeros(1, 77, 64))
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/p2p"), reason="reference checkout not present")
-def test_reference_hook_registration_walks_our_tree(cpu_unet):
-    """the reference's own register.py finds and patches our Attention modules (drop-in hook API)"""
-    import importlib.util
-    from types import SimpleNamespace
-    spec = importlib.util.spec_from_file_location("ref_register", "/root/reference/p2p/model/register.py")
-    ref = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(ref)
+def _check_reference_walk(unet, rec):
+    """our tree against a reference registration walk recorded on it (tests/golden/register_walk.json, G16): the modules the
+    walk patched, in its counting order, with the place it handed to the hook, are exactly our `attention_modules()` under
+    the top-level child they sit in; its count is theirs; and the hook protocol it uses -- `forward` replaced on the instance,
+    later put back from `_original_forward` -- takes each module off the native path and back onto it"""
+    mods = dict(unet.named_modules())
+    walk = [(n, p) for n, m in unet.named_modules() if m.__class__.__name__ == "Attention"
+            for p in [next((q for q in ("down", "up", "mid") if q in n.split(".")[0]), None)] if p is not None]
+    assert [(r["name"], r["place"]) for r in rec["patched"]] == walk
+    assert [mods[r["name"]] for r in rec["patched"]] == unet.attention_modules()
+    assert rec["num_att_layers"] == len(walk) == 32
+    assert rec["native_after_unregister"] and rec["num_att_layers_after_unregister"] == 0
+    patched = [mods[r["name"]] for r in rec["patched"]]
+    try:
+        for m in patched:
+            assert next(m.children(), None) is not None      # the masactrl walk patches an Attention only through its children
+            m._original_forward = m.forward
+            m.forward = lambda *a, **k: None
+        assert not any(m.is_native() for m in unet.attention_modules())
+        for m in patched:
+            m.forward = m._original_forward
+        assert all(m.is_native() for m in unet.attention_modules())
+    finally:
+        for m in patched:
+            m.__dict__.pop("forward", None)
+            m.__dict__.pop("_original_forward", None)
 
-    class Ctl:
-        num_att_layers = -1
 
-        def __call__(self, attn, is_cross, place):
-            return attn
-    model = SimpleNamespace(unet=cpu_unet)
-    c = Ctl()
-    ref.register_attention_control(model, c)
-    assert c.num_att_layers == 32
-    assert not any(m.is_native() for m in cpu_unet.attention_modules())
-    ref.unregister_attention_control(model, c)
-    assert c.num_att_layers == 0 and all(m.is_native() for m in cpu_unet.attention_modules())
+def _register_walk(golden_dir):
+    with open(os.path.join(golden_dir, "register_walk.json")) as f:
+        return json.load(f)
+
+
+def test_reference_hook_registration_walks_our_tree(cpu_unet, golden_dir):
+    """the reference's own p2p `register.py` finds and patches our Attention modules (drop-in hook API), as recorded on this
+    tree by `tests/golden/make_golden_register_walk.py`; it reads `to_out` of every module it patches"""
+    rec = _register_walk(golden_dir)
+    assert rec["config"] == "tiny" and rec["weights_seed"] == 0
+    _check_reference_walk(cpu_unet, rec["p2p"])
+    assert all(hasattr(m, "to_out") for m in cpu_unet.attention_modules())
 
 
 def test_lowering_tables_match_python_controller():
@@ -557,31 +577,11 @@ def test_producer_statistics_are_only_requested_where_they_are_valid():
     assert hip._attach_cstat(lib, p, torch.empty(16384, 320, dtype=torch.float16), 16384, 320, 4096) is not None
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/masactrl"), reason="reference checkout not present")
-def test_reference_masactrl_registration_walks_our_tree(cpu_unet):
+def test_reference_masactrl_registration_walks_our_tree(cpu_unet, golden_dir):
     """the reference's own `masactrl/model/register.py` finds and patches our Attention modules, counts them, and its
-    `unregister_attention_control` leaves them native again (drop-in editor API of the MasaCtrl folder)"""
-    import importlib.util
-    import sys
-    from types import SimpleNamespace
-    sys.path.insert(0, "/root/reference/masactrl")
-    saved = {k: sys.modules.pop(k) for k in list(sys.modules) if k == "model" or k.startswith("model.")}
-    try:
-        spec = importlib.util.spec_from_file_location("ref_masa_register", "/root/reference/masactrl/model/register.py")
-        ref = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(ref)
-        editor = ref.AttentionBase()
-        model = SimpleNamespace(unet=cpu_unet)
-        ref.regiter_attention_editor_diffusers(model, editor)
-        assert editor.num_att_layers == len(cpu_unet.attention_modules()) == 32
-        assert not any(m.is_native() for m in cpu_unet.attention_modules())
-        ref.unregister_attention_control(model, editor)
-        assert editor.num_att_layers == 0 and all(m.is_native() for m in cpu_unet.attention_modules())
-    finally:
-        sys.path.remove("/root/reference/masactrl")
-        for k in [k for k in sys.modules if k == "model" or k.startswith("model.")]:
-            sys.modules.pop(k)
-        sys.modules.update(saved)
+    `unregister_attention_control` leaves them native again (drop-in editor API of the MasaCtrl folder), as recorded on this
+    tree by `tests/golden/make_golden_register_walk.py`"""
+    _check_reference_walk(cpu_unet, _register_walk(golden_dir)["masactrl"])
 
 
 def test_x3_tile_geometry_rule_is_host_side_and_callable_without_a_gpu():

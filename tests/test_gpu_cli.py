@@ -81,13 +81,33 @@ def test_bench_under_torchrun_one_rank(tmp_path):
     out = run(["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
                "--master-port", "29617", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2",
                "--config", "small", "--no-cpu-baseline", "--pie-images", "2", "--steps-1024", "2", "--other-modes", "f16", "--in-flight", "2",
-               "--nti-images", "0"], cwd=ROOT, timeout=900)
+               "--nti-images", "0", "--full"], cwd=ROOT, timeout=900)
     rec = json.loads([l for l in out.splitlines() if l.startswith("{")][-1])
     assert rec["n_gpus"] == 1 and rec["steps"] == 6 and rec["value"] > 0 and "roofline" in rec
     # BASELINE.json's second metric and north_star's second latent size ride on the same line
     assert rec["images_per_sec"] > 0 and rec["images_per_sec_batched"] > 0
     assert rec["steps_per_sec_1024"] > 0 and rec["roofline_1024"]["frac"] > 0
     assert rec["roofline"]["bound"] in ("mfma", "hbm") and 0 < rec["roofline"]["roofline_frac"] <= 1.5
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """a plain run (no `--full`) times exactly `--steps` steps of the headline and nothing else; `--dump-outputs` writes the
+    latents of the last timed step, and two runs with the same arguments write the same arrays.  Past 50 steps the edit
+    restarts from x_T, so step 57 leaves the latents of step 7"""
+    dumps = []
+    for k, steps in enumerate((7, 7, 57)):
+        d = tmp_path / f"out{k}"
+        out = run([os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "2", "--config", "small",
+                   "--dump-outputs", str(d)], cwd=ROOT, timeout=600)
+        rec = json.loads([l for l in out.splitlines() if l.startswith("{")][-1])
+        assert rec["steps"] == steps and rec["value"] > 0 and rec["unit"] == "steps/s" and rec["higher_is_better"] is True
+        assert rec["dtype"] == "f16x3" and abs(rec["ms_per_step"] - 1e3 / rec["value"]) <= 0.01 * rec["ms_per_step"]
+        assert not ({"roofline", "parity_probe", "cpu_baseline", "fp16_mode", "exact_mode", "images_per_sec"} & set(rec))
+        assert sorted(os.listdir(d)) == ["latents.npy"]
+        lat = np.load(d / "latents.npy")
+        assert lat.dtype == np.float32 and lat.shape[:2] == (2, 4) and np.isfinite(lat).all()
+        dumps.append(lat)
+    assert np.array_equal(dumps[0], dumps[1]) and np.array_equal(dumps[0], dumps[2])
 
 
 def test_cfg_split_two_ranks_one_edit(tmp_path):
@@ -109,7 +129,7 @@ def test_bench_two_ranks_weak_and_cfg_split(tmp_path):
     (one edit on two ranks, strong scaling)"""
     base = ["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1"]
     tail = ["--gpus", "2", "--steps", "4", "--warmup", "1", "--config", "tiny", "--no-cpu-baseline", "--dist-backend", "gloo",
-            "--pie-images", "1", "--steps-1024", "0", "--in-flight", "", "--exact-steps", "0"]
+            "--pie-images", "1", "--steps-1024", "0", "--in-flight", "", "--exact-steps", "0", "--full"]
     out = run(base + ["--master-port", "29641", os.path.join(ROOT, "bench.py")] + tail, cwd=ROOT, timeout=600)
     rec = json.loads([l for l in out.splitlines() if l.startswith("{")][-1])
     assert rec["n_gpus"] == 2 and rec["scaling"] == "weak" and rec["value"] > 0 and rec["images_per_sec"] > 0
