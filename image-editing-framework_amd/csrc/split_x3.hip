@@ -872,7 +872,9 @@ __global__ __launch_bounds__(256, (D > 80) ? 1 : 2) void attn_flash_x3_kernel(co
 //   (SQ counters: 30 % more vector instructions per key from the operand-tuple moves the register allocator inserts, and half
 //   the waves to hide the rest behind).  What did pay on this loop: the lazy maximum, the split scale in the exponent and raised
 //   priority in the matrix phases (360 -> 347 us, 5.11 -> 5.01 ms).
-template <int D, int KS, int NWV>
+// LSE: also write the row log-sum-exp (log2 units, as attn_flash_x3_kernel) for ief_attn_bwd_x3 -- an instantiation of its own, so the
+// forward-only kernel keeps its register allocation (d = 40 sits exactly at the 128 registers of four waves per SIMD)
+template <int D, int KS, int NWV, bool LSE = false>
 __global__ __launch_bounds__(64 * NWV, D <= 40 ? 4 : 2) void attn_flash_x3p_kernel(const IefAttnF32Params p) {
     constexpr int DG = (D + 15) / 16, DT = (D + 31) / 32;
     constexpr int KT = 32 * KS;
@@ -1085,6 +1087,9 @@ __global__ __launch_bounds__(64 * NWV, D <= 40 ? 4 : 2) void attn_flash_x3p_kern
     }
     const float l_tot = l_run + __shfl_xor(l_run, 32);
     const float inv = 1.0f / l_tot;                          // O and l carry the same 2^10
+    if constexpr (LSE) {                                     // l carries 2^LOGSP
+        if (qi < p.N && lh == 0) p.lse[((long long)b * p.heads + h) * p.N + qi] = m_run + __log2f(l_tot) - LOGSP;
+    }
     if (qi < p.N) {
 #pragma unroll
         for (int tt = 0; tt < DT; ++tt)
@@ -1119,9 +1124,11 @@ int ief_attn_flash_x3_dispatch(const IefAttnF32Params& p, hipStream_t st) {
         if ((p.ldq & 7) || (p.ldk & 7) || (p.ldv & 7) || (p.sQb & 7) || (p.sKb & 7) || (p.sVb & 7) || (p.planeQ & 7) || (p.planeK & 7) ||
             (p.planeV & 7) || (((uintptr_t)p.Qp | (uintptr_t)p.Kp | (uintptr_t)p.Vp) & 15)) return IEF_EALIGN;
         switch (p.d) {
-            case 40: hipLaunchKernelGGL((attn_flash_x3p_kernel<40, 2, 8>), grid8, dim3(512), 0, st, p); break;
-            case 64: hipLaunchKernelGGL((attn_flash_x3p_kernel<64, 1, 4>), grid, dim3(256), 0, st, p); break;
-            case 80: hipLaunchKernelGGL((attn_flash_x3p_kernel<80, 1, 4>), grid, dim3(256), 0, st, p); break;
+#define FLASHP_GO(D_, KS_, NWV_, G_) do { if (p.lse) hipLaunchKernelGGL((attn_flash_x3p_kernel<D_, KS_, NWV_, true>), G_, dim3(64 * NWV_), 0, st, p); \
+                                         else hipLaunchKernelGGL((attn_flash_x3p_kernel<D_, KS_, NWV_, false>), G_, dim3(64 * NWV_), 0, st, p); } while (0)
+            case 40: FLASHP_GO(40, 2, 8, grid8); break;
+            case 64: FLASHP_GO(64, 1, 4, grid); break;
+            case 80: FLASHP_GO(80, 1, 4, grid); break;
             default: return IEF_ESHAPE;
         }
         IEF_LAUNCH_CHECK();

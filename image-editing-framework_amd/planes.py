@@ -515,10 +515,11 @@ FLASH_PLANES = os.environ.get("IEF_X3P_FLASH", "1") == "1"       # 0: the fused 
 FLASH_PLANES_DIMS = (40, 64, 80)
 
 
-def attn_flash(q, k, v, heads, scale, q_src=None, k_src=None, v_src=None, out=None, out_planes=True):
+def attn_flash(q, k, v, heads, scale, q_src=None, k_src=None, v_src=None, out=None, out_planes=True, lse=None):
     """fused attention on operand planes: q [B,N,h*d], k / v [B,L,h*d] as Planes (column slices of the q|k|v GEMM's output are
     fine); K / V tiles are staged by LDS-DMA, nothing is split in the kernel (`attn_flash_x3p_kernel`).  Returns Planes (for
-    to_out's GEMM) or, with out_planes=False, fp32."""
+    to_out's GEMM) or, with out_planes=False, fp32.
+    lse: optional contiguous fp32 [B, heads, N] receiving the row log-sum-exp (log2 units) that `hip.attn_bwd` consumes."""
     lib = hip.load()
     for t, nm in ((q, "q"), (k, "k"), (v, "v")):
         if not isinstance(t, Planes) or t.dim() != 3:
@@ -539,6 +540,10 @@ def attn_flash(q, k, v, heads, scale, q_src=None, k_src=None, v_src=None, out=No
     p.B, p.heads, p.N, p.L, p.d, p.scale = B, heads, N, L, d, scale
     p.q_src, p.k_src, p.v_src = _ptr(hip._devi32(q_src, "q_src")), _ptr(hip._devi32(k_src, "k_src")), _ptr(hip._devi32(v_src, "v_src"))
     p.x3, p.zeros = 1, _zeros(q.device)
+    if lse is not None:
+        if tuple(hip._dev32(lse, "lse").shape) != (B, heads, N):
+            raise ValueError("planes.attn_flash: lse must be contiguous fp32 [B, heads, N]")
+        p.lse = lse.data_ptr()
     op = None
     if out_planes:
         op, _ = attn_out_args(p, B, N, C, q.device)

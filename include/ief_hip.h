@@ -311,8 +311,8 @@ typedef struct IefAttnF32Params {
     const ief_half* Qp; const ief_half* Kp; const ief_half* Vp;
     long long planeQ, planeK, planeV;
     const void* zeros;      /* >= 16 bytes of device zeros (source of key rows past L) when Qp is set */
-    /* x3 != 0, fp32 Q / K / V (not planes) only: optional [B][heads][N] receiving the row log-sum-exp in log2 units
-     * (max + log2 sum exp2) that ief_attn_bwd_x3 consumes; null: not written */
+    /* x3 != 0 only (fp32 Q / K / V or operand planes; with x3 == 0 a non-null lse is IEF_EINVAL): optional [B][heads][N]
+     * receiving the row log-sum-exp in log2 units (max + log2 sum exp2) that ief_attn_bwd_x3 consumes; null: not written */
     float* lse;
 } IefAttnF32Params;
 int ief_attn_flash_f32(const IefAttnF32Params* p, void* stream);

@@ -146,8 +146,9 @@ def test_gemm_x3_wide_tile_equals_the_narrow_tile():
 @pytest.mark.parametrize("sa,sw", [(1e-4, 1e-3), (1e-2, 1e-5), (300.0, 1.0), (1.0, 30.0)])
 def test_gemm_x3_operand_magnitudes(sa, sw):
     """operands far from unit scale: the lo halves of small elements fall into the fp16 subnormal range (whether the MFMA
-    keeps or flushes them decides the error), large ones approach the end of the fp16 range (65504 / scale: activations
-    16376, weights 255 -- beyond it the output is NaN, as on any fp16 path, not silently wrong)"""
+    keeps or flushes them decides the error), large ones approach the end of the fp16 range (65504 / scale: activations are
+    split with `X3_SCALE_ACT` = 1, so the fp16 range itself, 65504; weights with 2^8, so 255 -- beyond it the output is NaN, as
+    on any fp16 path, not silently wrong)"""
     M, N, K = 256, 128, 640
     a, w = f32(M, K, seed=1) * sa, f32(N, K, seed=2) * sw
     e = rel_err(hip.gemm(dev(a), dev(w)), (a.double() @ w.double().t()).float())
