@@ -874,7 +874,13 @@ __global__ __launch_bounds__(256, (D > 80) ? 1 : 2) void attn_flash_x3_kernel(co
 //   priority in the matrix phases (360 -> 347 us, 5.11 -> 5.01 ms).
 // LSE: also write the row log-sum-exp (log2 units, as attn_flash_x3_kernel) for ief_attn_bwd_x3 -- an instantiation of its own, so the
 // forward-only kernel keeps its register allocation (d = 40 sits exactly at the 128 registers of four waves per SIMD)
-template <int D, int KS, int NWV, bool LSE = false>
+// SPLIT (again an instantiation of its own): the KEYS are dealt over gridDim.z workgroups -- at batch 1 the (query block, head)
+// grid alone fills a quarter of the chip's workgroup slots.  Workgroup z walks key tiles [z T, min((z + 1) T, nt)), T =
+// ceil(nt / gridDim.z); the dispatch clamps gridDim.z to ceil(nt / T), so every split owns a key below L and its maximum is
+// finite.  Nothing is normalised: the split's O rows (still carrying 2^LOGSP), its LAZY maximum m and its row sum l (consistent
+// with that m, which is all a merge needs) go to the caller's fp32 workspace, indexed by the OUTPUT batch row:
+//   ws = O [S][B heads N][D] | (m, l) [S][B heads N][2];     attn_flash_x3p_combine_kernel merges the S partials.
+template <int D, int KS, int NWV, bool LSE = false, bool SPLIT = false>
 __global__ __launch_bounds__(64 * NWV, D <= 40 ? 4 : 2) void attn_flash_x3p_kernel(const IefAttnF32Params p) {
     constexpr int DG = (D + 15) / 16, DT = (D + 31) / 32;
     constexpr int KT = 32 * KS;
@@ -967,13 +973,18 @@ __global__ __launch_bounds__(64 * NWV, D <= 40 ? 4 : 2) void attn_flash_x3p_kern
         for (int r = 0; r < 16; ++r) o[t][r] = 0.f;
     float m_run = -INFINITY, l_run = 0.f;
     const float sc2 = p.scale * 1.44269504088896341f;      // scores in log2 units (operand scale 1)
-    const int nt = (p.L + KT - 1) / KT;
-    issue(0, 0);
-    for (int t = 0; t < nt; ++t) {
+    int nt = (p.L + KT - 1) / KT, t_beg = 0;
+    if constexpr (SPLIT) {
+        const int T = (nt + (int)gridDim.z - 1) / (int)gridDim.z;
+        t_beg = (int)blockIdx.z * T;
+        nt = min(t_beg + T, nt);
+    }
+    issue(t_beg, 0);
+    for (int t = t_beg; t < nt; ++t) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's plane of tile t has landed
         __syncthreads();                                    // everybody's has; everybody is done with the other buffer
-        if (t + 1 < nt) issue(t + 1, (t + 1) & 1);
-        const half_t* Kh = smem_p + (t & 1) * (4 * PL);
+        if (t + 1 < nt) issue(t + 1, (t + 1 - t_beg) & 1);
+        const half_t* Kh = smem_p + ((t - t_beg) & 1) * (4 * PL);
         const half_t* Kl = Kh + PL;
         const half_t* Vh = Kl + PL;
         const half_t* Vl = Vh + PL;
@@ -1086,6 +1097,21 @@ __global__ __launch_bounds__(64 * NWV, D <= 40 ? 4 : 2) void attn_flash_x3p_kern
         __builtin_amdgcn_s_setprio(0);
     }
     const float l_tot = l_run + __shfl_xor(l_run, 32);
+    if constexpr (SPLIT) {                                   // the partial (O, m, l) of this split; lanes li and li + 32 share m_run
+        if (qi < p.N) {
+            const long long rows = (long long)p.B * p.heads * p.N, row = ((long long)b * p.heads + h) * p.N + qi;
+            float* wo = p.ws + ((long long)blockIdx.z * rows + row) * D;
+#pragma unroll
+            for (int tt = 0; tt < DT; ++tt)
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const int d = tt * 32 + 8 * g + 4 * lh;
+                    if (d < D) *(f32x4*)(wo + d) = f32x4{o[tt][4 * g], o[tt][4 * g + 1], o[tt][4 * g + 2], o[tt][4 * g + 3]};
+                }
+            if (lh == 0) *(float2*)(p.ws + (long long)gridDim.z * rows * D + ((long long)blockIdx.z * rows + row) * 2) = make_float2(m_run, l_tot);
+        }
+        return;
+    }
     const float inv = 1.0f / l_tot;                          // O and l carry the same 2^10
     if constexpr (LSE) {                                     // l carries 2^LOGSP
         if (qi < p.N && lh == 0) p.lse[((long long)b * p.heads + h) * p.N + qi] = m_run + __log2f(l_tot) - LOGSP;
@@ -1111,6 +1137,61 @@ __global__ __launch_bounds__(64 * NWV, D <= 40 ? 4 : 2) void attn_flash_x3p_kern
     }
 }
 
+// merges the S partials of attn_flash_x3p_kernel<.., SPLIT>: M = max_s m_s, w_s = 2^(m_s - M), O = sum_s w_s O_s / sum_s w_s l_s in
+// the fixed order s = 0 .. S - 1 (no atomics: two launches give the same bits).  One thread per four head-dim columns of a
+// (b, head, query) row; the 2^LOGSP that O_s and l_s carry alike cancels in the quotient, the lse takes it off as the single launch.
+template <int D>
+__global__ __launch_bounds__(256) void attn_flash_x3p_combine_kernel(const IefAttnF32Params p, const int S) {
+    constexpr int C4 = D / 4;
+    constexpr float LOGSP = 10.f;
+    const long long rows = (long long)p.B * p.heads * p.N;
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= rows * C4) return;
+    const long long row = idx / C4;
+    const int c = (int)(idx - row * C4);
+    const float2* ml = (const float2*)(p.ws + (long long)S * rows * D);
+    float M = -INFINITY;
+    for (int s = 0; s < S; ++s) M = fmaxf(M, ml[s * rows + row].x);
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    float den = 0.f;
+    for (int s = 0; s < S; ++s) {
+        const float2 e = ml[s * rows + row];
+        const float w = __builtin_amdgcn_exp2f(e.x - M);
+        const f32x4 os = *(const f32x4*)(p.ws + (s * rows + row) * D + 4 * c);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[j] = __builtin_fmaf(w, os[j], acc[j]);
+        den = __builtin_fmaf(w, e.y, den);
+    }
+    const float inv = 1.0f / den;
+    const f32x4 v = {acc[0] * inv, acc[1] * inv, acc[2] * inv, acc[3] * inv};
+    const long long bh = row / p.N;
+    const int qi = (int)(row - bh * p.N), b = (int)(bh / p.heads), h = (int)(bh - (long long)b * p.heads);
+    if (p.Out) *(f32x4*)(p.Out + (long long)b * p.sOb + (long long)h * D + (long long)qi * p.ldo + 4 * c) = v;
+    if (p.OutP) {
+        half4 hh, ll;
+        split4(v, 1.0f, hh, ll);
+        half_t* op = p.OutP + (long long)b * p.sOPb + (long long)h * D + (long long)qi * p.ldp + 4 * c;
+        *(half4*)op = hh;
+        *(half4*)(op + p.planeO) = ll;
+    }
+    if (p.lse && c == 0) p.lse[row] = M + __log2f(den) - LOGSP;
+}
+
+// key tiles of the planes kernel per head dim (0: no planes instantiation), and the splits a launch really takes: T = ceil(nt / S)
+// tiles each, S clamped to ceil(nt / T) so that no split is left without a key
+static int flashp_key_tile(int d) { return d == 40 ? 64 : (d == 64 || d == 80) ? 32 : 0; }
+static int flashp_eff_splits(int L, int d, int key_splits) {
+    const int kt = flashp_key_tile(d);
+    if (!kt || key_splits <= 1 || L <= 0) return 1;
+    const int nt = (L + kt - 1) / kt, T = (nt + key_splits - 1) / key_splits;
+    return (nt + T - 1) / T;
+}
+extern "C" long long ief_attn_flash_ws_floats(int B, int heads, int N, int L, int d, int key_splits) {
+    if (B <= 0 || heads <= 0 || N <= 0) return 0;
+    const int S = flashp_eff_splits(L, d, key_splits);
+    return S > 1 ? (long long)S * B * heads * N * (d + 2) : 0;
+}
+
 // called by ief_attn_flash_f32 (exact_f32.hip) after its argument checks when p.x3 != 0
 int ief_attn_flash_x3_dispatch(const IefAttnF32Params& p, hipStream_t st) {
     if (p.Out && ((p.ldo & 3) || (p.sOb & 3) || ((uintptr_t)p.Out & 15))) return IEF_EALIGN;
@@ -1123,6 +1204,25 @@ int ief_attn_flash_x3_dispatch(const IefAttnF32Params& p, hipStream_t st) {
         if (!p.Kp || !p.Vp || !p.zeros) return IEF_EINVAL;
         if ((p.ldq & 7) || (p.ldk & 7) || (p.ldv & 7) || (p.sQb & 7) || (p.sKb & 7) || (p.sVb & 7) || (p.planeQ & 7) || (p.planeK & 7) ||
             (p.planeV & 7) || (((uintptr_t)p.Qp | (uintptr_t)p.Kp | (uintptr_t)p.Vp) & 15)) return IEF_EALIGN;
+        const int S = flashp_eff_splits(p.L, p.d, p.key_splits);
+        if (S > 1) {    // keys over S workgroups + one combine launch; S == 1 (asked for or clamped): the single launch, ws not looked at
+            if (!p.ws || p.ws_floats < ief_attn_flash_ws_floats(p.B, p.heads, p.N, p.L, p.d, p.key_splits)) return IEF_EINVAL;
+            if ((uintptr_t)p.ws & 15) return IEF_EALIGN;
+            if (S > 65535) return IEF_ESHAPE;
+            const long long quads = (long long)p.B * p.heads * p.N * (p.d / 4);
+            const dim3 cgrid((unsigned)((quads + 255) / 256));
+#define FLASHP_SPLIT_GO(D_, KS_, NWV_, G_) do { hipLaunchKernelGGL((attn_flash_x3p_kernel<D_, KS_, NWV_, false, true>), dim3(G_.x, G_.y, S), dim3(64 * NWV_), 0, st, p); \
+                                               IEF_LAUNCH_CHECK(); \
+                                               hipLaunchKernelGGL((attn_flash_x3p_combine_kernel<D_>), cgrid, dim3(256), 0, st, p, S); } while (0)
+            switch (p.d) {
+                case 40: FLASHP_SPLIT_GO(40, 2, 8, grid8); break;
+                case 64: FLASHP_SPLIT_GO(64, 1, 4, grid); break;
+                case 80: FLASHP_SPLIT_GO(80, 1, 4, grid); break;
+                default: return IEF_ESHAPE;
+            }
+            IEF_LAUNCH_CHECK();
+            return IEF_OK;
+        }
         switch (p.d) {
 #define FLASHP_GO(D_, KS_, NWV_, G_) do { if (p.lse) hipLaunchKernelGGL((attn_flash_x3p_kernel<D_, KS_, NWV_, true>), G_, dim3(64 * NWV_), 0, st, p); \
                                          else hipLaunchKernelGGL((attn_flash_x3p_kernel<D_, KS_, NWV_, false>), G_, dim3(64 * NWV_), 0, st, p); } while (0)

@@ -116,7 +116,7 @@ class FusedDenoiser:
         plan = self.unet._plan
         return (id(self.unet), self.mode, self.Bp, tuple(self.lat.shape[-2:]), self.cfg, tuple(context.shape),
                 None if uncond_list is None else len(uncond_list), len(self.sched.timesteps),
-                None if plan is None else plan.signature(self.unet))
+                None if plan is None else plan.signature(self.unet), getattr(self.unet, "attn_key_splits", 1))
 
     def rebind(self, context, guidance_scale, uncond_list, added_cond_kwargs=None):
         """point a captured loop at the next image: new tables, new cross-attention K/V, the new controller's plan"""

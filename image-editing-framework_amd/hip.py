@@ -110,6 +110,7 @@ class IefAttnF32Params(Structure):
         ("OutP", c_void_p), ("planeO", c_longlong), ("sOPb", c_longlong), ("ldp", c_int), ("p_scale", c_float),
         ("Qp", c_void_p), ("Kp", c_void_p), ("Vp", c_void_p), ("planeQ", c_longlong), ("planeK", c_longlong), ("planeV", c_longlong),
         ("zeros", c_void_p), ("lse", c_void_p),
+        ("key_splits", c_int), ("ws", c_void_p), ("ws_floats", c_longlong),
     ]
 
 
@@ -162,6 +163,7 @@ EXPORTS = [
     "ief_map_loss_rows_f32", "ief_nti_adam_f32g",
     # ABI 4: split-operand contractions on pre-split planes (csrc/gemm_x3p.hip)
     "ief_gemm_x3p", "ief_gemm_x3p_tile_bm", "ief_gemm_x3p_tile_bn", "ief_gemm_x3p_tile_wn", "ief_x3_split_act", "ief_groupnorm_silu_x3p_ws", "ief_layernorm_x3p", "ief_groupnorm_silu_x3p_small", "ief_groupnorm_silu_reg", "ief_groupnorm_reg_fits", "ief_attn_bwd_x3", "ief_attn_bwd_delta_f32in",
+    "ief_attn_flash_ws_floats",
 ]
 
 
@@ -254,6 +256,8 @@ def load():
     lib.ief_map_loss_rows_blocks.argtypes = [c_longlong]
     lib.ief_map_loss_rows_f32.argtypes = [c_void_p] * 4 + [c_longlong, c_int, c_float, c_float, c_void_p]
     lib.ief_nti_adam_f32g.argtypes = [c_void_p] * 7 + [c_int, c_void_p]
+    lib.ief_attn_flash_ws_floats.argtypes = [c_int] * 6
+    lib.ief_attn_flash_ws_floats.restype = c_longlong
     lib.ief_groupnorm_f32_ws_floats.argtypes = [c_int, c_int, c_int]
     lib.ief_groupnorm_f32_ws_floats.restype = c_longlong
     lib.ief_groupnorm_silu_f32_ws.argtypes = [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
@@ -1391,7 +1395,7 @@ GN3_F32 = os.environ.get("IEF_GN3_F32", "1") == "1"          # 0: the one-launch
 FLASH_F32 = os.environ.get("IEF_FLASH_F32", "1") == "1"      # 0: always materialise the fp32 maps (A/B runs)
 
 
-def _attn_flash_f32(q, k, v, heads, scale, q_src=None, k_src=None, v_src=None, out=None, out_planes=False, lse=None):
+def _attn_flash_f32(q, k, v, heads, scale, q_src=None, k_src=None, v_src=None, out=None, out_planes=False, lse=None, key_splits=1):
     """fused fp32 attention (`ief_attn_flash_f32`): no map is written; None when the head dim has no instantiation.
     out_planes (split-operand mode only): the result leaves as operand planes for to_out's GEMM (`planes.Planes`);
     lse (split-operand mode only): fp32 [B, heads, N] receiving the row log-sum-exp (log2 units) for `ief_attn_bwd_x3`"""
@@ -1423,6 +1427,7 @@ def _attn_flash_f32(q, k, v, heads, scale, q_src=None, k_src=None, v_src=None, o
         if not p.x3 or tuple(_dev32(lse, "lse").shape) != (B, heads, N) or not lse.is_contiguous():
             raise ValueError("attn_flash: lse (contiguous fp32 [B, heads, N]) is written by the split-operand kernel only")
         p.lse = lse.data_ptr()
+    p.key_splits = int(key_splits)      # > 1: the library refuses (IEF_EINVAL) -- only the operand-planes kernel splits its keys
     with _Timed(f"attn_flash_{'x3' if p.x3 else 'f32'}_kernel<{d}>", 4.0 * B * heads * N * L * d, 4.0 * B * heads * d * (2 * N + 2 * L)):
         _check(lib.ief_attn_flash_f32(byref(p), _stream()), "ief_attn_flash_f32")
     return op if out_planes else out
@@ -1510,15 +1515,19 @@ def p2p_cross_edit_(probs, B, heads, edit_src, edit_slot, mt32, coef):
     return probs
 
 
-def attn_flash(q, k, v, heads, scale, q_src=None, k_src=None, v_src=None, out=None, lse=None, variant=0, out_planes=False):
+def attn_flash(q, k, v, heads, scale, q_src=None, k_src=None, v_src=None, out=None, lse=None, variant=0, out_planes=False,
+               key_splits=1):
     """out[b] = softmax(q[q_src[b]] k[k_src[b]]^T * scale) v[v_src[b]]; q [B,N,h*d], k/v [B,L,h*d] (strided views ok).
     lse: optional fp32 [B, heads, N] receiving the row log-sum-exp (log2 units) that `attn_bwd` consumes.
-    fp32 operands (reference-precision mode): the maps are materialised in HBM, as the reference does."""
+    fp32 operands (reference-precision mode): the maps are materialised in HBM, as the reference does.
+    key_splits: the keys over several workgroups exists for operand planes only (`planes.attn_flash`); > 1 here is refused."""
+    if key_splits != 1 and not (_is32(q) and FLASH_F32):
+        raise ValueError("attn_flash: key_splits exists on operand planes only (planes.attn_flash)")
     if _is32(q):
         if lse is not None and not x3_fused_bwd_ok(q.shape[2] // heads, k.shape[1]):
             raise ValueError("attn_flash: on fp32 operands lse exists only where ief_attn_bwd_x3 consumes it (x3_fused_bwd_ok); "
                              "elsewhere the fp32 backward recomputes the maps")
-        o = _attn_flash_f32(q, k, v, heads, scale, q_src, k_src, v_src, out, out_planes=out_planes, lse=lse)
+        o = _attn_flash_f32(q, k, v, heads, scale, q_src, k_src, v_src, out, out_planes=out_planes, lse=lse, key_splits=key_splits)
         if o is not None:
             return o
         if lse is not None:

@@ -29,6 +29,9 @@ parser.add_argument("--inversion_type", type=str, default="null-text")
 # not a reference flag; default = the mode that meets the reference's fp32 results to 1e-3 (see edit_syn.py); every inversion
 # type runs in every mode (the null-text reverse pass in fp32 for "f16x3" / "f32")
 parser.add_argument("--precision", type=str, default=os.environ.get("IEF_PRECISION", "f16x3"), choices=["f16", "f32", "f16x3"])
+# not a reference flag; "f16x3": keys of the planes self-attention over several workgroups (the batch-1 inversion steps leave
+# most of the chip idle); unset = the IEF_X3P_KEY_SPLITS environment variable, else 1
+parser.add_argument("--attn_key_splits", type=str, default=None, choices=["1", "2", "4", "8", "auto"])
 
 
 def edit_latent(pipe, editor, x_T, source_prompt, target_prompt, edit_type, device, extra=None, num_inference_steps=50,
@@ -72,7 +75,7 @@ def main(argv=None):
     seed_everything(args.seed)
     out_path = "./exp"
     edit_type = "refine"  # ["refine", "replace"]
-    pipe = load_pipe(args.sd_version, device, precision=args.precision)
+    pipe = load_pipe(args.sd_version, device, precision=args.precision, attn_key_splits=args.attn_key_splits)
     xl = pipe.__class__.__name__ == "StableDiffusionXLPipeline"          # dispatch of edit_real.py:97-115
     if args.inversion_type == "ddim":
         editor = (P2P_XL if xl else P2P)(model=pipe, num_inference_steps=50)

@@ -126,6 +126,9 @@ def main(argv=None):
     ap.add_argument("--precision", type=str, default=os.environ.get("IEF_PRECISION", "f16x3"), choices=["f16", "f32", "f16x3"],
                     help="f16x3 (default): fp32 storage, contractions on split fp16 operands -- the reference's fp32 images to 4e-6; "
                          "f32: the same on the fp32-input MFMA; f16: fp16 storage, 2.5x faster, images within 2 grey levels")
+    ap.add_argument("--attn_key_splits", type=str, default=None, choices=["1", "2", "4", "8", "auto"],
+                    help="f16x3: keys of the planes self-attention over this many workgroups (auto: by launch shape; fills the chip "
+                         "on batch-1 inversion steps); unset: the IEF_X3P_KEY_SPLITS environment variable, else 1")
     ap.add_argument("--in_flight", type=int, default=1,
                     help="independent images stepped concurrently on one GPU (null-text optimisations and edits)")
     args = ap.parse_args(argv)
@@ -138,7 +141,7 @@ def main(argv=None):
         from _bootstrap import init_distributed
         dist = init_distributed(device)       # rank 0 loads the weights; `load_pipe` broadcasts them (RCCL over xGMI)
     seed_everything(42)
-    pipe = load_pipe(args.sd_version, device, precision=args.precision)
+    pipe = load_pipe(args.sd_version, device, precision=args.precision, attn_key_splits=args.attn_key_splits)
     xl = pipe.__class__.__name__ == "StableDiffusionXLPipeline"          # dispatch of test.py:86-104
     if args.inversion_type == "ddim":
         editor = (P2P_XL if xl else P2P)(model=pipe, num_inference_steps=50)

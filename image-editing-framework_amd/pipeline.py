@@ -60,12 +60,15 @@ class StableDiffusionPipeline:
     # ------------------------------------------------------------------ construction
     @classmethod
     def from_pretrained(cls, model_key: str, torch_dtype=None, scheduler=None, device="cuda:0",
-                        keep_state_dict: bool = False, precision: str = "f16", empty_weights: bool = False, **unused):
+                        keep_state_dict: bool = False, precision: str = "f16", empty_weights: bool = False, attn_key_splits=None,
+                        **unused):
         """empty_weights: build the UNet from ZERO tensors of the right shapes without drawing / reading any weight -- what
         every rank but 0 of a multi-GPU run does before `dist.broadcast_pipeline` overwrites the packed tensors.
         precision: "f16" (default: fp16 storage / fp32 accumulation, the fast path whatever `torch_dtype` says) or
         "f32" — the reference's own precision (`/root/reference/p2p/edit_syn.py:38` loads the pipeline in fp32): UNet and
-        VAE run on the fp32-MFMA kernels, edited images then agree with the fp32 reference to ~1e-4"""
+        VAE run on the fp32-MFMA kernels, edited images then agree with the fp32 reference to ~1e-4
+        attn_key_splits: 1, 2, 4, 8 or "auto" ("f16x3": keys of the planes self-attention over several workgroups, for batch-1
+        steps; `planes.attn_key_splits`); default: the IEF_X3P_KEY_SPLITS environment variable, else 1"""
         from .unet import UNet2DConditionModel
         if model_key.startswith("synthetic:"):
             parts = model_key.split(":")
@@ -84,7 +87,7 @@ class StableDiffusionPipeline:
                 f"'{model_key}' is neither 'synthetic:<cfg>' nor a local directory.  Hub names cannot be fetched "
                 "offline: point sd_mapping.sd_maps at a local diffusers-layout directory (README of the reference, "
                 "lines 30-32) or use 'synthetic:sd15'.")
-        unet = UNet2DConditionModel(cfg, sd, device=device, precision=precision)
+        unet = UNet2DConditionModel(cfg, sd, device=device, precision=precision, attn_key_splits=_key_splits(attn_key_splits))
         text_encoder = text_encoder.to(device)
         sched = scheduler if scheduler is not None else DDIMScheduler()
         return cls(unet, tokenizer, text_encoder, vae, sched, cfg, sd if keep_state_dict else None)
@@ -115,7 +118,8 @@ class StableDiffusionXLPipeline(StableDiffusionPipeline):
 
     @classmethod
     def from_pretrained(cls, model_key: str, torch_dtype=None, scheduler=None, device="cuda:0",
-                        keep_state_dict: bool = False, precision: str = "f16", empty_weights: bool = False, **unused):
+                        keep_state_dict: bool = False, precision: str = "f16", empty_weights: bool = False, attn_key_splits=None,
+                        **unused):
         from .unet import UNet2DConditionModel
         import dataclasses
         sched = scheduler if scheduler is not None else DDIMScheduler()
@@ -127,7 +131,7 @@ class StableDiffusionXLPipeline(StableDiffusionPipeline):
                 raise ValueError(f"{model_key}: unet/config.json is not an SDXL-family configuration")
             vae = _load_local_vae(model_key, device, precision)
             tokenizer, tokenizer_2, enc1, enc2 = _load_local_text_xl(model_key, cfg)
-            unet = UNet2DConditionModel(cfg, sd, device=device, precision=precision)
+            unet = UNet2DConditionModel(cfg, sd, device=device, precision=precision, attn_key_splits=_key_splits(attn_key_splits))
             return cls(unet, tokenizer, enc1.to(device), vae, sched, cfg, sd if keep_state_dict else None,
                        text_encoder_2=enc2.to(device), tokenizer_2=tokenizer_2)
         if not model_key.startswith("synthetic:"):
@@ -147,7 +151,7 @@ class StableDiffusionXLPipeline(StableDiffusionPipeline):
         enc2 = SyntheticTextEncoder(d2, seed=2).to(device)
         vcfg = SD_VAE if parts[1] == "sdxl" else TINY_VAE
         vae = AutoencoderKL(dataclasses.replace(vcfg, scaling_factor=0.13025), device=device, precision=precision)   # the SDXL VAE's factor
-        unet = UNet2DConditionModel(cfg, sd, device=device, precision=precision)
+        unet = UNet2DConditionModel(cfg, sd, device=device, precision=precision, attn_key_splits=_key_splits(attn_key_splits))
         return cls(unet, tokenizer, enc1, vae, sched, cfg, sd if keep_state_dict else None, text_encoder_2=enc2)
 
     def _hidden_and_pooled(self, texts):
@@ -222,6 +226,11 @@ def _load_local_unet(path, empty=False):
     if missing:
         raise KeyError(f"checkpoint lacks {len(missing)} UNet tensors, e.g. {missing[:3]}")
     return cfg, {k: v.float() for k, v in sd.items()}
+
+
+def _key_splits(v):
+    """`attn_key_splits=` of from_pretrained: None -> the IEF_X3P_KEY_SPLITS environment variable, else 1 (the single launch)"""
+    return os.environ.get("IEF_X3P_KEY_SPLITS", "1") if v is None else v
 
 
 def _load_local_vae(path, device, precision="f16"):

@@ -515,11 +515,65 @@ FLASH_PLANES = os.environ.get("IEF_X3P_FLASH", "1") == "1"       # 0: the fused 
 FLASH_PLANES_DIMS = (40, 64, 80)
 
 
-def attn_flash(q, k, v, heads, scale, q_src=None, k_src=None, v_src=None, out=None, out_planes=True, lse=None):
+# key-split policy of the planes attention (with the measured table).  "auto" splits only where the (query
+# block, head) grid leaves at least half of the CUs WITHOUT a workgroup (a grid of one workgroup per CU gains nothing from a second
+# resident one: batch 2 measured 1 % slower split), never past the chip's workgroup slots (two per CU), and only while every split
+# keeps at least KEY_SPLIT_MIN_TILES key tiles: at 4 tiles per split the partial write + combine launch cost more than they return.
+KEY_SPLIT_MAX = 8
+KEY_SPLIT_MIN_TILES = 8
+KEY_SPLIT_SETTINGS = (1, 2, 4, 8, "auto")
+
+
+def key_split_setting(v):
+    """normalise a user-facing key-split setting (an int, "auto", or their strings: CLI flag / IEF_X3P_KEY_SPLITS) -> int >= 1 or the string auto"""
+    if isinstance(v, str):
+        v = v.strip().lower()
+        if v == "auto":
+            return "auto"
+        v = int(v)
+    v = int(v)
+    if v < 1:
+        raise ValueError(f"attn_key_splits must be >= 1 or 'auto', got {v}")
+    return v
+
+
+def _flash_key_tile(d):
+    return 64 if d == 40 else 32
+
+
+def attn_key_splits(B, heads, N, L, d, cus=None, setting="auto") -> int:
+    """workgroups the planes attention deals the KEYS of one (b, head, query block) over -- a pure host function of the launch's
+    shape.  setting: an int (passed through, clamped as the library clamps it: every split owns a key tile) or "auto": the largest
+    power of two S <= 8 with G S <= 2 cus (G = query blocks x B x heads, two workgroups per CU) and nt // S >= KEY_SPLIT_MIN_TILES
+    key tiles per split, and only where 2 G <= cus (half of the CUs idle unsplit), else 1; always 1 for L < 128.  cus=None: the current device's compute units."""
+    setting = key_split_setting(setting)
+    if d not in FLASH_PLANES_DIMS or L < 1:
+        return 1
+    nt = -(-L // _flash_key_tile(d))
+    if setting != "auto":
+        T = -(-nt // min(setting, nt))
+        return -(-nt // T)
+    if L < 128:
+        return 1
+    if cus is None:
+        cus = torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count
+    G = -(-N // (256 if d == 40 else 128)) * B * heads
+    S = KEY_SPLIT_MAX if 2 * G <= cus else 1
+    while S > 1 and (G * S > 2 * cus or nt // S < KEY_SPLIT_MIN_TILES):
+        S //= 2
+    if S <= 1:
+        return 1
+    T = -(-nt // S)
+    return -(-nt // T)
+
+
+def attn_flash(q, k, v, heads, scale, q_src=None, k_src=None, v_src=None, out=None, out_planes=True, lse=None, key_splits=1):
     """fused attention on operand planes: q [B,N,h*d], k / v [B,L,h*d] as Planes (column slices of the q|k|v GEMM's output are
     fine); K / V tiles are staged by LDS-DMA, nothing is split in the kernel (`attn_flash_x3p_kernel`).  Returns Planes (for
     to_out's GEMM) or, with out_planes=False, fp32.
-    lse: optional contiguous fp32 [B, heads, N] receiving the row log-sum-exp (log2 units) that `hip.attn_bwd` consumes."""
+    lse: optional contiguous fp32 [B, heads, N] receiving the row log-sum-exp (log2 units) that `hip.attn_bwd` consumes.
+    key_splits: 1 (the single launch), an int or "auto" (`attn_key_splits`): the keys of every query block go over that many
+    workgroups (partials in a torch-allocated fp32 workspace -- fine inside graph capture) and one combine launch merges them."""
     lib = hip.load()
     for t, nm in ((q, "q"), (k, "k"), (v, "v")):
         if not isinstance(t, Planes) or t.dim() != 3:
@@ -551,6 +605,13 @@ def attn_flash(q, k, v, heads, scale, q_src=None, k_src=None, v_src=None, out=No
         if out is None:
             out = torch.empty(B, N, C, dtype=torch.float32, device=q.device)
         p.Out, p.sOb, p.ldo = hip._act32(out, "out").data_ptr(), out.stride(0), out.stride(1)
-    with _Timed(f"attn_flash_x3p_kernel<{d}>", 4.0 * B * heads * N * L * d, 4.0 * B * heads * d * (2 * N + 2 * L)):
+    S = 1 if key_splits == 1 else attn_key_splits(B, heads, N, L, d, setting=key_splits)
+    name, nbytes = f"attn_flash_x3p_kernel<{d}>", 4.0 * B * heads * d * (2 * N + 2 * L)
+    if S > 1:
+        nws = lib.ief_attn_flash_ws_floats(B, heads, N, L, d, S)
+        ws = torch.empty(nws, dtype=torch.float32, device=q.device)
+        p.key_splits, p.ws, p.ws_floats = S, ws.data_ptr(), nws
+        name, nbytes = f"attn_flash_x3p_kernel<{d}, split {S}> + attn_flash_x3p_combine_kernel", nbytes + 8.0 * nws
+    with _Timed(name, 4.0 * B * heads * N * L * d, nbytes):
         _check(lib.ief_attn_flash_f32(byref(p), _stream()), "ief_attn_flash_f32 (planes)")
     return op if out_planes else out

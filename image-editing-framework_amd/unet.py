@@ -172,6 +172,7 @@ class Attention(nn.Module):
         self._kv_view = None
         self.ln_w = self.ln_b = self.ln_c1 = None   # input projection with the preceding LayerNorm folded in
         self.ln_eps = 1e-5
+        self.attn_key_splits = 1   # planes self-attention: keys over this many workgroups (int or "auto", planes.attn_key_splits)
 
     def fold_layernorm(self, norm):
         """pack W gamma / beta W^T of the q (cross) or q|k|v (self) projection for the LayerNorm that feeds this module"""
@@ -292,7 +293,7 @@ class Attention(nn.Module):
                 # the q|k|v GEMM writes planes only; the attention kernel stages K / V tiles by LDS-DMA and splits nothing
                 qkv = planes.gemm(xp, w_in, bias=b_in, ln=ln, out=False, out_planes=True)
                 o = planes.attn_flash(qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:], self.heads, self.scale, q_src=qs,
-                                      k_src=ks, v_src=vs)
+                                      k_src=ks, v_src=vs, key_splits=self.attn_key_splits)
             else:
                 qkv = planes.gemm(xp, w_in, bias=b_in, ln=ln)
                 o = hip.attn_flash(qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:], self.heads, self.scale, q_src=qs, k_src=ks,
@@ -647,8 +648,11 @@ class TimestepEmbedding(nn.Module):
 
 
 class UNet2DConditionModel(nn.Module):
-    def __init__(self, cfg: UNetConfig, state_dict: Dict[str, torch.Tensor], device="cuda:0", precision: str = "f16"):
-        """precision: "f16" — fp16 storage, fp32 accumulation (the fast path); "f32" — the reference's precision
+    def __init__(self, cfg: UNetConfig, state_dict: Dict[str, torch.Tensor], device="cuda:0", precision: str = "f16",
+                 attn_key_splits=1):
+        """attn_key_splits: "f16x3" only -- the self-attention on operand planes deals its keys over that many workgroups (1, an
+        int or "auto": a per-launch function of the shape, `planes.attn_key_splits`; batch-1 steps leave most of the chip idle).
+        precision: "f16" — fp16 storage, fp32 accumulation (the fast path); "f32" — the reference's precision
         (`/root/reference/p2p/edit_syn.py:38`): fp32 weights and activations on the fp32-input MFMA kernels; "f16x3" — fp32
         weights and activations, every contraction on split fp16 operands (hi + lo halves, three fp16 MFMAs per product,
         `csrc/split_x3.hip`): ~21 operand bits at a third of the fp16 matrix rate"""
@@ -663,6 +667,20 @@ class UNet2DConditionModel(nn.Module):
             self._build(cfg, state_dict, device)
         finally:
             _PACK = saved
+        self.attn_key_splits = attn_key_splits
+
+    @property
+    def attn_key_splits(self):
+        return self._attn_key_splits
+
+    @attn_key_splits.setter
+    def attn_key_splits(self, v):
+        """one setting for every attention module; part of `denoise`'s pool key, so a graph captured under one setting is never
+        re-pointed at a job that runs under another"""
+        self._attn_key_splits = planes.key_split_setting(v)
+        for m in self.modules():
+            if isinstance(m, Attention):
+                m.attn_key_splits = self._attn_key_splits
 
     def _build(self, cfg, state_dict, device):
         hip.load()  # fail loudly before touching anything else

@@ -314,8 +314,18 @@ typedef struct IefAttnF32Params {
     /* x3 != 0 only (fp32 Q / K / V or operand planes; with x3 == 0 a non-null lse is IEF_EINVAL): optional [B][heads][N]
      * receiving the row log-sum-exp in log2 units (max + log2 sum exp2) that ief_attn_bwd_x3 consumes; null: not written */
     float* lse;
+    /* operand planes in (Qp set) only, appended to ABI 4: key_splits > 1 deals the KEYS of every (b, head, query block) over that
+     * many workgroups, each writing an unnormalised partial (O, lazy max, row sum) to ws, and one combine launch merges them in
+     * a fixed order (deterministic; for the batch-1 launches whose (query block, head) grid leaves most of the chip idle).  The
+     * library clamps the count so that every split owns a key tile; a count that clamps to 1 (and key_splits <= 1) takes the
+     * single launch and ws is not looked at.  ws: ief_attn_flash_ws_floats(...) fp32 of scratch, 16-byte aligned, the caller's
+     * until the stream passes; ws_floats: its size.  Without Qp or with x3 == 0, key_splits > 1 is IEF_EINVAL; so are a null or
+     * short ws; a misaligned one is IEF_EALIGN. */
+    int key_splits; float* ws; long long ws_floats;
 } IefAttnF32Params;
 int ief_attn_flash_f32(const IefAttnF32Params* p, void* stream);
+/* fp32 elements of IefAttnF32Params.ws that the launch needs after clamping key_splits; 0 when it would not split */
+long long ief_attn_flash_ws_floats(int B, int heads, int N, int L, int d, int key_splits);
 int ief_softmax_rows_f32(float* x, long long rows, int L, void* stream);
 /* P'[w] = c1[w] * sum_v P_src[v] M[v][w] + c2[w] * P_tgt[w] in place on maps [B*heads][N][L], L <= 96; MT fp32
  * [slots][96][96] (M transposed, zero padded), coef fp32 [slots][2][96]; edit_src / edit_slot as IefCrossParams */
