@@ -311,6 +311,9 @@ extern "C" int ief_gemm_f32(const IefGemmF32Params* pp, void* stream) {
         if (p.stride != 1 && p.stride != 2) return IEF_ESHAPE;
         if (p.ups && ((p.H | p.Wd) & 1)) return IEF_ESHAPE;
         if (p.x3) return launch_x3(p, st);
+        // igemm_f32_kernel reads every source and the weights in 16-byte pieces
+        if (((uintptr_t)p.A | (uintptr_t)p.W | (uintptr_t)(p.C2 > 0 ? p.A2 : p.A) | (uintptr_t)(p.CE1 > 0 ? p.E1 : p.A) |
+             (uintptr_t)(p.CE2 > 0 ? p.E2 : p.A)) & 15) return IEF_EALIGN;
         return ief_gemm_f32_bn(p.N) == 64 ? launch_igemm_f32<true, false, 1>(p, st) : launch_igemm_f32<true, false, 2>(p, st);
     }
     p.a_scalar = ((p.lda & 3) || (p.K & 3)) ? 1 : 0;          // A rows not 16-byte chunked: element loads for A
@@ -318,6 +321,10 @@ extern "C" int ief_gemm_f32(const IefGemmF32Params* pp, void* stream) {
     if (!p.transb && (p.K & 3)) return IEF_ESHAPE;             // W [N][K] rows are read in 16-byte chunks along K
     if (p.transb && (p.N & 3)) return IEF_ESHAPE;
     if (p.x3) return launch_x3(p, st);
+    // igemm_f32_kernel reads W, and A unless its rows take element loads, in 16-byte pieces: base pointers and, for the batched
+    // products, the batch-row and head strides
+    if (((uintptr_t)p.W & 15) || (!p.a_scalar && ((uintptr_t)p.A & 15))) return IEF_EALIGN;
+    if (p.heads > 0 && (((p.sWb | p.sWh) & 3) || (!p.a_scalar && ((p.sAb | p.sAh) & 3)))) return IEF_EALIGN;
     if (p.transb) {
         return ief_gemm_f32_bn(p.N) == 64 ? launch_igemm_f32<false, true, 1>(p, st) : launch_igemm_f32<false, true, 2>(p, st);
     }
@@ -469,6 +476,7 @@ extern "C" int ief_attn_flash_f32(const IefAttnF32Params* pp, void* stream) {
     dim3 grid((p.N + 127) / 128, p.B * p.heads);
     hipStream_t st = (hipStream_t)stream;
     if (p.x3) return ief_attn_flash_x3_dispatch(p, st);
+    if (((uintptr_t)p.Q | (uintptr_t)p.K | (uintptr_t)p.V) & 15) return IEF_EALIGN;     // 16-byte loads of q, k and v rows
     switch (p.d) {
         case 32: hipLaunchKernelGGL(attn_flash_f32_kernel<32>, grid, dim3(256), 0, st, p); break;
         case 40: hipLaunchKernelGGL(attn_flash_f32_kernel<40>, grid, dim3(256), 0, st, p); break;
@@ -1116,7 +1124,8 @@ extern "C" int ief_groupnorm_silu_f32(const float* x, const float* x2, int C1, i
     if (!x || !out || !gamma || !beta || (C2 > 0 && !x2)) return IEF_EINVAL;
     if (B <= 0 || HW <= 0 || groups <= 0 || C1 <= 0 || C2 < 0 || (C1 + C2) % groups) return IEF_ESHAPE;
     const int cpg = (C1 + C2) / groups;
-    if ((cpg & 1) || (C1 & 1) || (cpg >> 1) > 256) {
+    const bool al8 = (((uintptr_t)x | (uintptr_t)(x2 ? x2 : x) | (uintptr_t)out) & 7) == 0;      // the pair kernel's 8-byte accesses
+    if ((cpg & 1) || (C1 & 1) || (cpg >> 1) > 256 || !al8) {
         hipLaunchKernelGGL(groupnorm_f32_scalar_kernel, dim3(B * groups), dim3(256), 0, (hipStream_t)stream, x, x2, C1, C2, out,
                            gamma, beta, HW, groups, eps, silu);
         IEF_LAUNCH_CHECK();
@@ -1460,6 +1469,7 @@ extern "C" int ief_gather_rows_f32(const float* in, float* out, const int* src, 
 
 // --------------------------------------------------------------------------------------------- boundary convolutions
 // conv_in:  fp32 NCHW [B,Cin<=8,H,W] -> fp32 NHWC [B,H,W,Cout]; w fp32 [3][3][Cin][Cout].  One thread per (pixel, 4 channels).
+// w and out are accessed in 16-byte pieces: both 16-byte aligned (IEF_EALIGN otherwise, nothing launched); x, bias: any alignment.
 // CIN > 0: the channel count is a compile-time constant and every load of a tap ROW (3 taps x CIN activations, 3 x CIN weight
 // vectors) is requested before the first is used -- the plain loop below issued 9 x Cin dependent load pairs per thread (40 us for
 // the 0.38 GFLOP of SD's 4 -> 320 at 64 x 64, batch 4).  The accumulation order (tap, channel) is the loop's: same bits.
@@ -1526,6 +1536,7 @@ extern "C" int ief_conv_in_f32act(const float* x, const float* w, const float* b
                                   int Cout, void* stream) {
     if (!x || !w || !out) return IEF_EINVAL;
     if (B <= 0 || H <= 0 || Wd <= 0 || Cin <= 0 || Cin > 8 || Cout <= 0 || (Cout & 3)) return IEF_ESHAPE;
+    if (((uintptr_t)w | (uintptr_t)out) & 15) return IEF_EALIGN;         // 16-byte weight loads and output stores (x: element loads)
     const long long total = (long long)B * H * Wd * (Cout / 4);
     int grid = (int)((total + 255) / 256);
     if (grid > 8192) grid = 8192;
@@ -1536,6 +1547,8 @@ extern "C" int ief_conv_in_f32act(const float* x, const float* w, const float* b
 }
 
 // conv_out: fp32 NHWC [B,H,W,C] -> fp32 NCHW [B,Cout<=8,H,W]; w fp32 [Cout][3][3][C]; 16 lanes per output pixel split 9*C
+// x and w are read in 16-byte pieces by both kernels: both 16-byte aligned (IEF_EALIGN otherwise, nothing launched); out, bias:
+// any alignment.
 __global__ __launch_bounds__(256) void conv_out_f32_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                            const float* __restrict__ bias, float* __restrict__ out, int B, int C,
                                                            int H, int Wd, int Cout) {
@@ -1653,6 +1666,7 @@ extern "C" int ief_conv_out_f32act(const float* x, const float* w, const float* 
                                    int Cout, void* stream) {
     if (!x || !w || !out) return IEF_EINVAL;
     if (B <= 0 || H <= 0 || Wd <= 0 || C <= 0 || (C & 3) || Cout <= 0 || Cout > 8) return IEF_ESHAPE;
+    if (((uintptr_t)x | (uintptr_t)w) & 15) return IEF_EALIGN;           // both kernels read x and w in 16-byte pieces
     const long long total = (long long)B * H * Wd;
     const size_t lds = (size_t)Cout * 9 * C * sizeof(float);
     const dim3 grid((unsigned)((total + 15) / 16));

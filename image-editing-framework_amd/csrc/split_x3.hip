@@ -11,7 +11,7 @@
 // at 1/16; measured against fp64 the results are as close as the fp32 MFMA's (tests/test_gpu_x3.py).  The scales keep `lo`
 // out of the fp16 subnormal range for elements of ordinary size (|lo| <= 2^-11 |hi|: a normal number once |s x| >= 2^-3;
 // smaller elements keep an absolute resolution of 2^-25 / s — gfx950's MFMA does not flush fp16 subnormals); the host
-// picks them per call (activations 2^2, weights 2^8, softmax maps 2^14), the epilogue divides them out.  |s x| must stay
+// picks them per call (activations 1, weights 2^8, softmax maps 2^14), the epilogue divides them out.  |s x| must stay
 // below 65504 (the fp16 range, as on the fp16-storage path): beyond it `hi` is infinite and the output NaN, not silently wrong.
 //
 //   igemm_x3_kernel<WM, WN, TM, TN, KIND, TRANSB>
@@ -35,7 +35,9 @@
 #include "x3_common.h"
 
 // fp32 weights -> the two fp16 planes [2][n] the GEMM's B operand is staged from when it is a WEIGHT (static: split once per
-// tensor by the host wrapper, not once per launch and workgroup): planes[0] = hi = fp16(s w), planes[1] = lo = fp16(s w - hi)
+// tensor by the host wrapper, not once per launch and workgroup): planes[0] = hi = fp16(s w), planes[1] = lo = fp16(s w - hi).
+// w is read in 16-byte pieces, the planes are written in 8-byte pieces: w 16-byte aligned, planes 8-byte aligned (IEF_EALIGN
+// otherwise, nothing launched).
 __global__ __launch_bounds__(256) void x3_split_weights_kernel(const float* __restrict__ w, half_t* __restrict__ planes, long long n4,
                                                                float s) {
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
@@ -48,6 +50,7 @@ __global__ __launch_bounds__(256) void x3_split_weights_kernel(const float* __re
 extern "C" int ief_x3_split_weights(const float* w, void* planes, long long n, float scale, void* stream) {
     if (!w || !planes) return IEF_EINVAL;
     if (n <= 0 || (n & 3) || !(scale > 0.f)) return IEF_ESHAPE;
+    if (((uintptr_t)w & 15) || ((uintptr_t)planes & 7)) return IEF_EALIGN;
     long long grid = (n / 4 + 255) / 256;
     if (grid > 16384) grid = 16384;
     hipLaunchKernelGGL(x3_split_weights_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, w, (half_t*)planes, n / 4, scale);

@@ -228,7 +228,10 @@ int ief_advance_step(int* step, void* stream);
  * fp32 activations and fp32 weights, contractions on the fp32-input MFMA (csrc/exact_f32.hip); the host picks them by
  * the dtype of the tensors it is handed (hip.py).  Attention in this mode MATERIALISES its maps in HBM as the
  * reference does (/root/reference/p2p/model/register.py:43-51): scores and P.V are two batched launches of ief_gemm_f32
- * with ief_softmax_rows_f32 (and the P2P edit, ief_p2p_cross_edit_f32) between them. */
+ * with ief_softmax_rows_f32 (and the P2P edit, ief_p2p_cross_edit_f32) between them.
+ * Alignment (x3 == 0): ief_gemm_f32 reads W and the conv sources (A, A2, E1, E2) in 16-byte pieces, and A of a linear product
+ * unless lda or K is no multiple of 4 floats; ief_attn_flash_f32 reads Q, K, V so.  Those base pointers must be 16-byte aligned
+ * and the batched products' sAb / sAh / sWb / sWh multiples of 4 floats: IEF_EALIGN otherwise, nothing launched. */
 typedef struct IefGemmF32Params {
     const float* A;         /* [M][K] rows (lda) | conv: NHWC source 1 */
     const float* A2;        /* conv: NHWC source 2 of a channel concat, or NULL */
@@ -276,7 +279,8 @@ typedef struct IefGemmF32Params {
     int geglu;
 } IefGemmF32Params;
 int ief_gemm_f32(const IefGemmF32Params* p, void* stream);
-/* planes[0][i] = fp16(scale w[i]), planes[1][i] = fp16(scale w[i] - planes[0][i]); n % 4 == 0 */
+/* planes[0][i] = fp16(scale w[i]), planes[1][i] = fp16(scale w[i] - planes[0][i]); n % 4 == 0; w 16-byte aligned, planes 8-byte
+ * aligned (IEF_EALIGN otherwise) */
 int ief_x3_split_weights(const float* w, void* planes, long long n, float scale, void* stream);
 int ief_gemm_x3_bn(int N);    /* x3 != 0: output-tile width (80 or 64) for N columns; ief_gemm_x3_bm(M, N): its row count (128) */
 int ief_gemm_x3_bm(int M, int N);
@@ -376,7 +380,9 @@ int ief_silu_f32(const float* x, float* out, long long n, void* stream);
 int ief_geglu_il_f32(const float* pre, float* out, long long rows, int Ch, void* stream);
 int ief_timestep_embedding_f32(const float* t, float* out, int B, int dim, void* stream);
 int ief_gather_rows_f32(const float* in, float* out, const int* src, int B, long long row_elems, void* stream);
-/* boundary convolutions with fp32 activations: fp32 NCHW latents <-> fp32 NHWC; w fp32 [3][3][Cin][Cout] / [Cout][3][3][C] */
+/* boundary convolutions with fp32 activations: fp32 NCHW latents <-> fp32 NHWC; w fp32 [3][3][Cin][Cout] / [Cout][3][3][C].
+ * Operands accessed in 16-byte pieces must be 16-byte aligned (IEF_EALIGN otherwise, nothing launched): w and out of conv_in,
+ * x and w of conv_out */
 int ief_conv_in_f32act(const float* x, const float* w, const float* bias, float* out, int B, int Cin, int H, int Wd, int Cout,
                        void* stream);
 int ief_conv_out_f32act(const float* x, const float* w, const float* bias, float* out, int B, int C, int H, int Wd, int Cout,
