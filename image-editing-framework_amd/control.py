@@ -14,6 +14,12 @@ the same effect is expressed as small device tables, so no map is ever written t
       source-row table int32 [steps+1, 2B]  (identity rows outside the window)
   MasaCtrl mutual self-attention (/root/reference/masactrl/model/attention_control.py:37-68):
       K,V source rows per (step, layer)
+  MasaCtrl mask-guided mutual self-attention (/root/reference/masactrl/model/attention_control.py:134-189), binary masks,
+      batch [u_src, u_tgt, c_src, c_tgt]: a target query inside mask_t attends to the source keys inside mask_s, one
+      outside to the keys outside (the fg / bg blend picks one of two softmaxes per query, and the +1 the fg branch adds
+      to its surviving keys is softmax-invariant): the mutual launch as above, then two launches over gathered row lists
+      that overwrite the target rows -- int32 lists fg_keys / bg_keys / fg_queries / bg_queries per token count and a
+      per-step gate table (1 in the controlled steps) that switches those launches inside a captured graph
   Plug-and-Play injection (/root/reference/pnp/model/register.py:27-90,100-182), batch = 4 blocks of s rows
       [uncond_src, uncond_tgt, cond_src, cond_tgt]: during the first qk_steps timesteps the self-attention of the chosen
       decoder layers computes rows of blocks 1 and 3 with the Q and K of block 2 (:45-52), and during the first
@@ -68,12 +74,13 @@ class StepCounter:
 
 
 class ControlPlan:
-    """kind: 'empty' | 'p2p' | 'masactrl' | 'pnp'"""
+    """kind: 'empty' | 'p2p' | 'masactrl' | 'masactrl_mask' | 'pnp'"""
 
     def __init__(self, controller, kind: str, device, num_prompts: int = 1, num_steps: int = 0,
                  mt: Optional[torch.Tensor] = None, coef_table: Optional[torch.Tensor] = None,
                  self_window=(0, 0), self_max_tokens: int = 256, masa_steps=(), masa_layers=(),
-                 pnp_layers=(), pnp_qk_steps: int = 0, pnp_conv_steps: int = 0, cond_only: bool = False):
+                 pnp_layers=(), pnp_qk_steps: int = 0, pnp_conv_steps: int = 0, cond_only: bool = False,
+                 mask_s: Optional[torch.Tensor] = None, mask_t: Optional[torch.Tensor] = None, mask_tokens=()):
         """cond_only: the UNet batch holds ONLY the conditional rows [cond_src, cond_tgt...] — the half a controller acts
         on (`attention_base.py:20-22`) — as on the conditional rank of a 2-GPU CFG split (`denoise.CfgSplitDenoiser`) and
         in the reference's LOW_RESOURCE protocol (:18-19)"""
@@ -125,13 +132,36 @@ class ControlPlan:
         self.masa_layers = set(int(l) for l in masa_layers)
         self._masa = {}
         self._step_synced = -1
+        # masactrl_mask: the two binary masks (host fp32 [h, w]), the token counts of the controlled layers (their lists are
+        # built by prepare), per N the four device lists, and the per-step gate of the gathered launches
+        self.mask_s = None if mask_s is None else mask_s.detach().float().cpu()
+        self.mask_t = None if mask_t is None else mask_t.detach().float().cpu()
+        self.mask_tokens = tuple(sorted(set(int(n) for n in mask_tokens)))
+        self._mask_lists = {}                      # N -> (fg_keys, bg_keys, fg_queries, bg_queries)
+        self._gate = None                          # (table int32 [steps, 1], cur int32 [1])
+        self._mask_rows = {}                       # B -> (target rows, their halves' source rows)
         self.pnp_layers = set(pnp_layers)          # id() of the Attention modules whose Q/K are injected
         self.pnp_qk_steps, self.pnp_conv_steps = int(pnp_qk_steps), int(pnp_conv_steps)
         self._pnp = {}                             # B -> (qk_table, qk_cur, conv_table, conv_cur)
 
     def prepare(self, B: int):
         """allocate per-batch device tables OUTSIDE any graph capture"""
-        if self.kind == "masactrl" and B not in self._masa:
+        if self.kind == "masactrl_mask":
+            if B != 4:
+                raise RuntimeError(f"mask-guided MasaCtrl acts on the UNet batch [u_src, u_tgt, c_src, c_tgt]; got batch {B}")
+            n = (max(self.masa_steps) + 2) if self.masa_steps else 1
+            if self._gate is None:
+                g = torch.zeros(n, 1, dtype=torch.int32)
+                for st in self.masa_steps:
+                    g[st] = 1
+                self._gate = (g.to(self.device), torch.zeros(1, dtype=torch.int32, device=self.device))
+            if B not in self._mask_rows:
+                half = B // 2
+                self._mask_rows[B] = (torch.tensor([half - 1, B - 1], dtype=torch.int32, device=self.device),
+                                      torch.tensor([0, half], dtype=torch.int32, device=self.device))
+            for N in self.mask_tokens:
+                self.mask_lists(N)
+        if self.kind in ("masactrl", "masactrl_mask") and B not in self._masa:
             n = (max(self.masa_steps) + 2) if self.masa_steps else 1
             self.num_steps = max(self.num_steps, n - 1)
             ident = torch.arange(B, dtype=torch.int32)
@@ -157,6 +187,51 @@ class ControlPlan:
             cv[: self.pnp_conv_steps] = inj
             dev = self.device
             self._pnp[B] = (qk.contiguous().to(dev), ident.clone().to(dev), cv.contiguous().to(dev), ident.clone().to(dev))
+
+    @staticmethod
+    def resized_mask(mask, N: int):
+        """the mask at a layer of N = H x W tokens, flattened: torch's own nearest resize, as the reference's attn_batch runs it"""
+        H = W = int(N ** 0.5)
+        if H * W != N:
+            raise ValueError(f"mask-guided MasaCtrl needs square token grids, got {N} tokens")
+        return torch.nn.functional.interpolate(mask[None, None], (H, W)).flatten()
+
+    def mask_lengths(self, N: int):
+        """the lengths of mask_lists(N), from the masks alone (host; builds nothing)"""
+        ms, mt = self.resized_mask(self.mask_s, N), self.resized_mask(self.mask_t, N)
+        return tuple(int((m == v).sum()) for m, v in ((ms, 1), (ms, 0), (mt, 1), (mt, 0)))
+
+    def mask_lists(self, N: int):
+        """(fg_keys, bg_keys, fg_queries, bg_queries) int32 device lists for layers of N tokens; built on first use, which must
+        lie outside any graph capture (prepare builds those of `mask_tokens`: the lowering passes the token counts of the
+        UNet's CONFIGURED sample size and has checked both key classes there; another latent size adds its counts at the
+        first eager or warm-up forward, and raises if a key class is empty at one of them)"""
+        if N not in self._mask_lists:
+            if self.captured:
+                raise RuntimeError(f"ControlPlan.prepare(B) must build the mask lists of {N} tokens before graph capture")
+            ms, mt = self.resized_mask(self.mask_s, N), self.resized_mask(self.mask_t, N)
+            ls = [torch.nonzero(m == v).flatten().to(torch.int32) for m, v in ((ms, 1), (ms, 0), (mt, 1), (mt, 0))]
+            if ls[0].numel() == 0 or ls[1].numel() == 0:
+                raise RuntimeError(f"mask_s has an empty key class at {N} tokens: no fused rule there.  The lowering checked the "
+                                   f"token counts of the UNet's configured sample size {self.mask_tokens}; run at that size, "
+                                   "or register a subclass of the editor to take the generic path")
+            self._mask_lists[N] = tuple(t.to(self.device) for t in ls)
+            # a token count first met at run time (latents of another size than the configured one): from here on part of
+            # what prepare builds, signature() states and load_from() copies
+            self.mask_tokens = tuple(sorted(set(self.mask_tokens) | {N}))
+        return self._mask_lists[N]
+
+    def mask_launches(self, B: int, N: int, attn):
+        """the gathered launches of a controlled self-attention layer under 'masactrl_mask', after the mutual launch:
+        None, or (q_src, kv_src, gate, [(q_idx, k_idx), ...]) -- a class without target queries launches nothing"""
+        if self.kind != "masactrl_mask" or (attn._exec_index // 2) not in self.masa_layers:
+            return None
+        fk, bk, fq, bq = self.mask_lists(N)        # also in a muted warm-up forward: the lists exist before capture
+        if self.muted:
+            return None
+        tgt, src = self._mask_rows[B]
+        return tgt, src, self._gate[1], [(q, k) for q, k in ((fq, fk), (bq, bk)) if q.numel() > 0]
+
     # ------------------------------------------------------------------ re-use of a captured loop (denoise.acquire)
     def signature(self, unet):
         """everything about this plan that is BAKED into a captured step graph (which kernels run, on which modules,
@@ -166,6 +241,13 @@ class ControlPlan:
                     hip.map_split_scale(self.coef_bound))
         if self.kind == "masactrl":
             return ("masactrl", tuple(sorted(self.masa_layers)), (max(self.masa_steps) + 2) if self.masa_steps else 1)
+        if self.kind == "masactrl_mask":      # the list LENGTHS are launch arguments (grid, N, L); their contents are data
+            # Computed from the masks, so asking builds nothing.  NOTE: it covers `mask_tokens`, which states the UNet's
+            # configured sample size until a forward at another latent size adds its counts (mask_lists) -- denoise keys a
+            # pooled loop BEFORE its warm-up, so at such a size two plans can match here and still differ in a length:
+            # load_from checks every length and refuses the reuse loudly.
+            lens = tuple((N, self.mask_lengths(N)) for N in self.mask_tokens)
+            return ("masactrl_mask", tuple(sorted(self.masa_layers)), (max(self.masa_steps) + 2) if self.masa_steps else 1, lens)
         if self.kind == "pnp":
             idx = {id(m): m._exec_index for m in unet.attention_modules()}
             # the injected resnet as `pnp/model/register.py:_conv_module` picks it: resnets[0] on the SDXL family, else [1]
@@ -189,6 +271,19 @@ class ControlPlan:
             other.prepare(B)
             self.masa_steps = set(other.masa_steps)
             self._masa[B][0].copy_(other._masa[B][0])
+        elif self.kind == "masactrl_mask":
+            other.prepare(B)
+            self.prepare(B)
+            self.masa_steps = set(other.masa_steps)
+            self.mask_s, self.mask_t = other.mask_s, other.mask_t
+            self._masa[B][0].copy_(other._masa[B][0])
+            self._gate[0].copy_(other._gate[0])
+            for N in self.mask_tokens:             # equal lengths where the signatures covered N; checked for the rest
+                if tuple(int(t.numel()) for t in self.mask_lists(N)) != other.mask_lengths(N):
+                    raise RuntimeError(f"masactrl_mask: the captured graph holds lists of other lengths at {N} tokens than "
+                                       "these masks give; this loop cannot be reused for them")
+                for mine, theirs in zip(self.mask_lists(N), other.mask_lists(N)):
+                    mine.copy_(theirs)
         elif self.kind == "pnp":
             other.prepare(B)
             self.pnp_qk_steps, self.pnp_conv_steps = other.pnp_qk_steps, other.pnp_conv_steps
@@ -199,7 +294,7 @@ class ControlPlan:
     def applies(self, B: int) -> bool:
         if self.kind == "empty" or self.muted:
             return False
-        if self.kind in ("masactrl", "pnp"):
+        if self.kind in ("masactrl", "masactrl_mask", "pnp"):
             return True
         if B != self.batch:
             raise RuntimeError(
@@ -219,7 +314,7 @@ class ControlPlan:
         if self.kind == "p2p":
             hip.select_step(self.coef_table, self.coef_cur, self.step)
             hip.select_step(self.self_table, self.self_cur, self.step)
-        elif self.kind == "masactrl":
+        elif self.kind in ("masactrl", "masactrl_mask"):
             if B not in self._masa:
                 if self.captured:
                     raise RuntimeError("ControlPlan.prepare(B) must run before graph capture")
@@ -228,6 +323,8 @@ class ControlPlan:
             if not self.captured and int(self.controller.cur_step) >= tab.shape[0]:
                 self.step.fill_(tab.shape[0] - 1)   # past the last controlled step: identity row
             hip.select_step(tab, cur, self.step)
+            if self.kind == "masactrl_mask":        # the gate table has the same rows: 0 in the identity row past the end
+                hip.select_step(self._gate[0], self._gate[1], self.step)
         elif self.kind == "pnp":
             if B not in self._pnp:
                 if self.captured:
@@ -240,7 +337,7 @@ class ControlPlan:
             hip.select_step(cv, cv_cur, self.step)
 
     def end_forward(self, B: int):
-        if self.kind in ("masactrl", "pnp") and not self.muted:
+        if self.kind in ("masactrl", "masactrl_mask", "pnp") and not self.muted:
             hip.advance_step(self.step)
         elif self.kind != "empty" and not self.muted and B == self.batch:
             hip.advance_step(self.step)
@@ -264,7 +361,7 @@ class ControlPlan:
     def self_sources(self, B: int, N: int, attn):
         if self.kind == "p2p" and self.applies(B) and N <= self.self_max_tokens:
             return self.self_cur, self.self_cur, None
-        if self.kind == "masactrl" and not self.muted and (attn._exec_index // 2) in self.masa_layers:
+        if self.kind in ("masactrl", "masactrl_mask") and not self.muted and (attn._exec_index // 2) in self.masa_layers:
             cur = self._masa[B][1]
             return None, cur, cur
         if self.kind == "pnp" and not self.muted and id(attn) in self.pnp_layers:

@@ -471,6 +471,10 @@ extern "C" int ief_attn_flash_f32(const IefAttnF32Params* pp, void* stream) {
     if (!p.x3 && (!p.Out || (p.ldo & 3) || (p.sOb & 3))) return IEF_EINVAL;
     if (!p.x3 && p.lse) return IEF_EINVAL;                // only the split-operand kernels write the row log-sum-exp
     if (p.key_splits > 1 && (!p.x3 || !p.Qp)) return IEF_EINVAL;     // only the operand-planes kernel splits its keys over workgroups
+    if (p.q_idx || p.k_idx || p.gate) {                   // gathered rows: the operand-planes kernel only, both lists, no lse, no key split
+        if (!p.x3 || !p.Qp || !p.q_idx || !p.k_idx || p.lse || p.key_splits > 1) return IEF_EINVAL;
+        if (((uintptr_t)p.q_idx | (uintptr_t)p.k_idx | (uintptr_t)p.gate) & 3) return IEF_EALIGN;
+    }
     if (p.B <= 0 || p.heads <= 0 || p.N <= 0 || p.L <= 0) return IEF_ESHAPE;
     if ((p.ldq & 3) || (p.ldk & 3) || (p.ldv & 3) || (p.sQb & 3) || (p.sKb & 3) || (p.sVb & 3)) return IEF_EALIGN;
     dim3 grid((p.N + 127) / 128, p.B * p.heads);

@@ -883,8 +883,17 @@ __global__ __launch_bounds__(256, (D > 80) ? 1 : 2) void attn_flash_x3_kernel(co
 // finite.  Nothing is normalised: the split's O rows (still carrying 2^LOGSP), its LAZY maximum m and its row sum l (consistent
 // with that m, which is all a merge needs) go to the caller's fp32 workspace, indexed by the OUTPUT batch row:
 //   ws = O [S][B heads N][D] | (m, l) [S][B heads N][2];     attn_flash_x3p_combine_kernel merges the S partials.
-template <int D, int KS, int NWV, bool LSE = false, bool SPLIT = false>
+// IDX (an instantiation of its own once more; not with LSE or SPLIT): attention over GATHERED rows -- query slot qi loads token row
+// q_idx[qi] and stores its output to that same row, key slot `row` of a tile is token row k_idx[row] (an LDS-DMA piece takes a
+// per-lane source address, so the gather costs one index read per piece and nothing in LDS); p.N / p.L are the list lengths and
+// the tails qi >= N, row >= L are handled as ever.  *gate == 0: the workgroup returns before it touches anything (a captured step
+// graph keeps the launch in every step and the plan's gate table switches it off in the uncontrolled ones).
+template <int D, int KS, int NWV, bool LSE = false, bool SPLIT = false, bool IDX = false>
 __global__ __launch_bounds__(64 * NWV, D <= 40 ? 4 : 2) void attn_flash_x3p_kernel(const IefAttnF32Params p) {
+    static_assert(!IDX || (!LSE && !SPLIT), "the gathered launch writes no lse and does not split its keys");
+    if constexpr (IDX) {
+        if (p.gate && *p.gate == 0) return;      // uniform over the grid: nobody reaches a barrier
+    }
     constexpr int DG = (D + 15) / 16, DT = (D + 31) / 32;
     constexpr int KT = 32 * KS;
     constexpr int CPR = D / 8;                   // 16-byte chunks per row
@@ -914,14 +923,16 @@ __global__ __launch_bounds__(64 * NWV, D <= 40 ? 4 : 2) void attn_flash_x3p_kern
     half_t* OP = p.OutP ? p.OutP + (long long)b * p.sOPb + (long long)h * D : nullptr;
     const int q0 = qb * (32 * NWV) + wid * 32;
     const int qi = q0 + li;
+    int qrow = qi;                               // the token row this lane's query is read from and its output goes to
+    if constexpr (IDX) qrow = qi < p.N ? p.q_idx[qi] : 0;
     // the lane's query: for every 16-deep d group the 8 values d = 16 g + 8 lh + j, hi and lo straight from the planes
     half8_t qh[DG], ql[DG];
 #pragma unroll
     for (int g = 0; g < DG; ++g) {
         const int d0 = g * 16 + 8 * lh;
         if (qi < p.N && d0 < D) {
-            qh[g] = *(const half8_t*)(Qh + (long long)qi * p.ldq + d0);
-            ql[g] = *(const half8_t*)(Qh + p.planeQ + (long long)qi * p.ldq + d0);
+            qh[g] = *(const half8_t*)(Qh + (long long)qrow * p.ldq + d0);
+            ql[g] = *(const half8_t*)(Qh + p.planeQ + (long long)qrow * p.ldq + d0);
         } else {
 #pragma unroll
             for (int j = 0; j < 8; ++j) { qh[g][j] = 0; ql[g][j] = 0; }
@@ -940,6 +951,17 @@ __global__ __launch_bounds__(64 * NWV, D <= 40 ? 4 : 2) void attn_flash_x3p_kern
         const int ch = c - s_row[i] * CPR;
         s_off[i] = (unsigned)((SWZ ? (ch ^ (s_row[i] & 7)) : ch) * 16);     // the swizzle is applied to the chunk FETCHED for this LDS slot
     }
+    // IDX: the token rows of the NEXT tile to issue, k_idx[t KT + s_row[i]], are read one tile ahead where there are registers
+    // for them; d = 40 (128 registers, four waves per SIMD) reads each index in front of its DMA instead
+    constexpr bool AHEAD = IDX && D != 40;
+    int k_row[AHEAD ? NPW : 1];
+    auto fetch_idx = [&](int t) {
+#pragma unroll
+        for (int i = 0; i < (AHEAD ? NPW : 0); ++i) {
+            const int row = t * KT + s_row[i];
+            k_row[i] = (wid + NWV * i < 4 * NP && row < p.L) ? *(const int*)((const char*)p.k_idx + (unsigned)row * 4u) : 0;
+        }
+    };
     auto issue = [&](int t, int buf) {
 #pragma unroll
         for (int i = 0; i < NPW; ++i) {
@@ -948,7 +970,7 @@ __global__ __launch_bounds__(64 * NWV, D <= 40 ? 4 : 2) void attn_flash_x3p_kern
                 const int pl = q / NP, j = q - pl * NP;
                 const int row = t * KT + s_row[i];
                 const int ldr = pl < 2 ? p.ldk : p.ldv;
-                const char* g = row < p.L ? srcs[pl] + (long long)row * ldr * 2 + s_off[i] : zp;
+                const char* g = row < p.L ? srcs[pl] + (long long)(AHEAD ? k_row[i] : IDX ? *(const int*)((const char*)p.k_idx + (unsigned)row * 4u) : row) * ldr * 2 + s_off[i] : zp;
                 x3_glds16(g, smem_p + buf * (4 * PL) + pl * PL + j * 512);
             }
         }
@@ -982,11 +1004,16 @@ __global__ __launch_bounds__(64 * NWV, D <= 40 ? 4 : 2) void attn_flash_x3p_kern
         t_beg = (int)blockIdx.z * T;
         nt = min(t_beg + T, nt);
     }
+    if constexpr (AHEAD) fetch_idx(t_beg);
     issue(t_beg, 0);
+    if constexpr (AHEAD) { if (t_beg + 1 < nt) fetch_idx(t_beg + 1); }
     for (int t = t_beg; t < nt; ++t) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's plane of tile t has landed
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's plane of tile t has landed (IDX: and the indices of tile t + 1)
         __syncthreads();                                    // everybody's has; everybody is done with the other buffer
-        if (t + 1 < nt) issue(t + 1, (t + 1 - t_beg) & 1);
+        if (t + 1 < nt) {
+            issue(t + 1, (t + 1 - t_beg) & 1);
+            if constexpr (AHEAD) { if (t + 2 < nt) fetch_idx(t + 2); }
+        }
         const half_t* Kh = smem_p + ((t - t_beg) & 1) * (4 * PL);
         const half_t* Kl = Kh + PL;
         const half_t* Vh = Kl + PL;
@@ -1120,6 +1147,7 @@ __global__ __launch_bounds__(64 * NWV, D <= 40 ? 4 : 2) void attn_flash_x3p_kern
         if (qi < p.N && lh == 0) p.lse[((long long)b * p.heads + h) * p.N + qi] = m_run + __log2f(l_tot) - LOGSP;
     }
     if (qi < p.N) {
+        if constexpr (IDX) qrow = p.q_idx[qi];   // read again: not kept in a register through the key loop
 #pragma unroll
         for (int tt = 0; tt < DT; ++tt)
 #pragma unroll
@@ -1127,11 +1155,11 @@ __global__ __launch_bounds__(64 * NWV, D <= 40 ? 4 : 2) void attn_flash_x3p_kern
                 const int d = tt * 32 + 8 * g + 4 * lh;
                 if (d < D) {
                     const f32x4 v = {o[tt][4 * g] * inv, o[tt][4 * g + 1] * inv, o[tt][4 * g + 2] * inv, o[tt][4 * g + 3] * inv};
-                    if (O) *(f32x4*)(O + (long long)qi * p.ldo + d) = v;
+                    if (O) *(f32x4*)(O + (long long)qrow * p.ldo + d) = v;
                     if (OP) {
                         half4 hh, ll;
                         split4(v, 1.0f, hh, ll);
-                        half_t* op = OP + (long long)qi * p.ldp + d;
+                        half_t* op = OP + (long long)qrow * p.ldp + d;
                         *(half4*)op = hh;
                         *(half4*)(op + p.planeO) = ll;
                     }
@@ -1207,6 +1235,17 @@ int ief_attn_flash_x3_dispatch(const IefAttnF32Params& p, hipStream_t st) {
         if (!p.Kp || !p.Vp || !p.zeros) return IEF_EINVAL;
         if ((p.ldq & 7) || (p.ldk & 7) || (p.ldv & 7) || (p.sQb & 7) || (p.sKb & 7) || (p.sVb & 7) || (p.planeQ & 7) || (p.planeK & 7) ||
             (p.planeV & 7) || (((uintptr_t)p.Qp | (uintptr_t)p.Kp | (uintptr_t)p.Vp) & 15)) return IEF_EALIGN;
+        if (p.q_idx || p.k_idx || p.gate) {      // gathered rows (ief_attn_flash_f32 has refused lse, key_splits > 1 and a missing list)
+#define FLASHP_IDX_GO(D_, KS_, NWV_, G_) hipLaunchKernelGGL((attn_flash_x3p_kernel<D_, KS_, NWV_, false, false, true>), G_, dim3(64 * NWV_), 0, st, p)
+            switch (p.d) {
+                case 40: FLASHP_IDX_GO(40, 2, 8, grid8); break;
+                case 64: FLASHP_IDX_GO(64, 1, 4, grid); break;
+                case 80: FLASHP_IDX_GO(80, 1, 4, grid); break;
+                default: return IEF_ESHAPE;
+            }
+            IEF_LAUNCH_CHECK();
+            return IEF_OK;
+        }
         const int S = flashp_eff_splits(p.L, p.d, p.key_splits);
         if (S > 1) {    // keys over S workgroups + one combine launch; S == 1 (asked for or clamped): the single launch, ws not looked at
             if (!p.ws || p.ws_floats < ief_attn_flash_ws_floats(p.B, p.heads, p.N, p.L, p.d, p.key_splits)) return IEF_EINVAL;

@@ -111,6 +111,7 @@ class IefAttnF32Params(Structure):
         ("Qp", c_void_p), ("Kp", c_void_p), ("Vp", c_void_p), ("planeQ", c_longlong), ("planeK", c_longlong), ("planeV", c_longlong),
         ("zeros", c_void_p), ("lse", c_void_p),
         ("key_splits", c_int), ("ws", c_void_p), ("ws_floats", c_longlong),
+        ("q_idx", c_void_p), ("k_idx", c_void_p), ("gate", c_void_p),
     ]
 
 

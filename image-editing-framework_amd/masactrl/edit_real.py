@@ -11,7 +11,8 @@ from PIL import Image
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "p2p"))
 from _bootstrap import load_pipe, seed_everything  # noqa: E402
 
-from ief_amd.masactrl.model.attention_control import MutualSelfAttentionControl  # noqa: E402
+from ief_amd.masactrl.model.attention_control import (MutualSelfAttentionControl, MutualSelfAttentionControlMask,  # noqa: E402
+                                                      load_mask_png)
 from ief_amd.masactrl.model.register import regiter_attention_editor_diffusers, unregister_attention_control  # noqa: E402
 from ief_amd.masactrl.model.sd_utils import MasaCtrl, MasaCtrl_NTI, MasaCtrl_XL, MasaCtrl_XL_NTI  # noqa: E402
 from ief_amd.p2p.inversion.ddim import ddim_inversion, ddim_inversion_xl  # noqa: E402
@@ -26,14 +27,18 @@ parser.add_argument("--source_prompt", type=str, default="a gray horse in the fi
 parser.add_argument("--target_prompt", type=str, default="a whie horse in the field")
 parser.add_argument("--source_image", type=str, default="./test.jpg")
 parser.add_argument("--inversion_type", type=str, default="null-text")
+# optional, both or neither: foreground masks of the source / target image (PNG, thresholded at 0.5) -> mask-guided MasaCtrl
+parser.add_argument("--mask_s", type=str, default=None)
+parser.add_argument("--mask_t", type=str, default=None)
 
 STEP, LAYPER = 4, 10
 NUM_INNER_STEPS, EARLY_STOP_EPSILON = 10, 1e-5
 
 
 def edit_one(pipe, editor, invertor, image, source_prompt, target_prompt, inversion_type, device, size,
-             num_inference_steps=50, guidance_scale=7.5):
-    """invert + MasaCtrl-edit one PIL image -> uint8 images [2,H,W,3] (reconstruction, edit); :128-153 of the reference"""
+             num_inference_steps=50, guidance_scale=7.5, masks=None):
+    """invert + MasaCtrl-edit one PIL image -> uint8 images [2,H,W,3] (reconstruction, edit); :128-153 of the reference.
+    masks: optional (mask_s, mask_t) fp32 [h, w] in {0, 1} -> the mask-guided editor"""
     latent = invertor.image2latent(model=pipe, image=image, device=device, dtype=torch.float32)
     latents, context = invertor.ddim_inversion_loop(pipe, latent, source_prompt)
     extra = {}
@@ -45,7 +50,11 @@ def edit_one(pipe, editor, invertor, image, source_prompt, target_prompt, invers
         raise ValueError("Please choose right inversion type")
     init_latent = torch.cat([latents[-1], latents[-1]])
     xl = pipe.__class__.__name__ == "StableDiffusionXLPipeline"          # model_type / LAYPER switch of edit_real.py:96-115
-    controller = MutualSelfAttentionControl(STEP, 54 if xl else LAYPER, model_type="SDXL" if xl else "SD")
+    if masks is not None:
+        controller = MutualSelfAttentionControlMask(STEP, 54 if xl else LAYPER, mask_s=masks[0], mask_t=masks[1],
+                                                    model_type="SDXL" if xl else "SD")
+    else:
+        controller = MutualSelfAttentionControl(STEP, 54 if xl else LAYPER, model_type="SDXL" if xl else "SD")
     regiter_attention_editor_diffusers(editor.model, controller)
     images, _ = editor(prompt=source_prompt + target_prompt, latents=init_latent, guidance_scale=guidance_scale,
                        num_inference_steps=num_inference_steps, height=size, width=size, **extra)
@@ -67,6 +76,8 @@ def pick(pipe, inversion_type, num_inference_steps=50):
 
 def main(argv=None):
     args = parser.parse_args(argv)
+    if (args.mask_s is None) != (args.mask_t is None):
+        parser.error("--mask_s and --mask_t go together")
     device = torch.device("cuda:{}".format(args.device))
     seed_everything(args.seed)
     num_inference_steps = 50
@@ -77,8 +88,9 @@ def main(argv=None):
     os.makedirs(out_path, exist_ok=True)
     original_image = Image.open(args.source_image).convert("RGB").resize((size, size))
     original_image.save(os.path.join(out_path, "source.png"))
+    masks = None if args.mask_s is None else (load_mask_png(args.mask_s, device), load_mask_png(args.mask_t, device))
     images = edit_one(pipe, editor, invertor, original_image, [args.source_prompt], [args.target_prompt],
-                      args.inversion_type, device, size, num_inference_steps)
+                      args.inversion_type, device, size, num_inference_steps, masks=masks)
     save_img(images[0], os.path.join(out_path, "inversion.png"))
     save_img(images[1], os.path.join(out_path, "edit.png"))
 

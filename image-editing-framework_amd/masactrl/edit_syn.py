@@ -10,7 +10,8 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 from _bootstrap import load_pipe, seed_everything  # noqa: E402
 
 from ief_amd.masactrl.model.attention_base import AttentionBase  # noqa: E402
-from ief_amd.masactrl.model.attention_control import MutualSelfAttentionControl  # noqa: E402
+from ief_amd.masactrl.model.attention_control import (MutualSelfAttentionControl, MutualSelfAttentionControlMask,  # noqa: E402
+                                                      load_mask_png)
 from ief_amd.masactrl.model.register import regiter_attention_editor_diffusers  # noqa: E402
 from ief_amd.masactrl.model.sd_utils import MasaCtrl  # noqa: E402
 from ief_amd.p2p.utils.save_image import save_img  # noqa: E402
@@ -21,10 +22,15 @@ parser.add_argument("--device", type=int, default=0)
 parser.add_argument("--seed", type=int, default=8888)
 parser.add_argument("--source_prompt", type=str, default="A standing dog on the grass field")
 parser.add_argument("--target_prompt", type=str, default="A running dog on the grass field")
+# optional, both or neither: foreground masks of the source / target image (PNG, thresholded at 0.5) -> mask-guided MasaCtrl
+parser.add_argument("--mask_s", type=str, default=None)
+parser.add_argument("--mask_t", type=str, default=None)
 
 
 def main(argv=None):
     args = parser.parse_args(argv)
+    if (args.mask_s is None) != (args.mask_t is None):
+        parser.error("--mask_s and --mask_t go together")
     device = torch.device("cuda:{}".format(args.device))
     seed_everything(args.seed)
     num_inference_steps, GUIDANCE_SCALE, STEP, LAYPER = 50, 7.5, 4, 10
@@ -43,7 +49,11 @@ def main(argv=None):
                                 num_inference_steps=num_inference_steps, height=size, width=size)
     save_img(image, os.path.join(out_path, "source.png"))
     init_latent = torch.cat([init_latent, init_latent])
-    controller = MutualSelfAttentionControl(STEP, LAYPER, model_type=model_type)
+    if args.mask_s is not None:
+        controller = MutualSelfAttentionControlMask(STEP, LAYPER, mask_s=load_mask_png(args.mask_s, device),
+                                                    mask_t=load_mask_png(args.mask_t, device), model_type=model_type)
+    else:
+        controller = MutualSelfAttentionControl(STEP, LAYPER, model_type=model_type)
     regiter_attention_editor_diffusers(editor.model, controller)
     image_masactrl, _ = editor(prompt=[args.source_prompt, args.target_prompt], latents=init_latent,
                                guidance_scale=GUIDANCE_SCALE, num_inference_steps=num_inference_steps, height=size,

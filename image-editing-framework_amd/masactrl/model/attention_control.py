@@ -3,9 +3,19 @@
 From `start_step` on, in transformer layers >= `start_layer` (layer = cur_att_layer // 2, counted in execution order:
 6 down, 1 mid, 9 up for SD), every SELF-attention of the uncond half uses the K and V of that half's first sample
 (the source image), and likewise for the cond half (:59-66).  Only this class is reachable from the reference CLIs
-(`masactrl/edit_syn.py:108`, `edit_real.py:136`); the Union / Mask / MaskAuto variants are never instantiated.
+(`masactrl/edit_syn.py:108`, `edit_real.py:136`).
+
+`MutualSelfAttentionControlMask` (:110-189) is the mask-guided variant for the batch [u_src, u_tgt, c_src, c_tgt]: the
+source rows attend to themselves; each target row attends to its half's source keys twice -- "fg" with every key outside
+`mask_s` pushed to `finfo.min`, "bg" with every key inside it -- and the two outputs are blended per query by `mask_t`.
+Here the CLIs reach it through `--mask_s / --mask_t`.  With binary masks in the f16x3 mode `register.py` lowers it to
+gathered flash-attention launches; everywhere else the bodies below run on the generic path.  The Union and MaskAuto
+variants are not ported.
 """
+import os
+
 import torch
+import torch.nn.functional as F
 
 from .attention_base import AttentionBase
 
@@ -42,3 +52,77 @@ class MutualSelfAttentionControl(AttentionBase):
         out_u = self.attn_batch(qu, ku[:num_heads], vu[:num_heads], None, None, is_cross, place_in_unet, num_heads, **kwargs)
         out_c = self.attn_batch(qc, kc[:num_heads], vc[:num_heads], None, None, is_cross, place_in_unet, num_heads, **kwargs)
         return torch.cat([out_u, out_c], dim=0)
+
+
+def _save_mask_png(mask, path):
+    """what `torchvision.utils.save_image(mask[None, None], path)` writes for one [h, w] map: x 255, + 0.5, clamp, 8 bit, RGB"""
+    from PIL import Image
+    g = mask.detach().float().cpu().mul(255).add(0.5).clamp(0, 255).to(torch.uint8)
+    Image.fromarray(g[..., None].expand(-1, -1, 3).contiguous().numpy()).save(path)
+
+
+class MutualSelfAttentionControlMask(MutualSelfAttentionControl):
+    def __init__(self, start_step=4, start_layer=10, layer_idx=None, step_idx=None, total_steps=50, mask_s=None, mask_t=None,
+                 mask_save_dir=None, model_type="SD"):
+        """mask_s / mask_t: source / target masks [h, w] (same shape), resized per layer by `F.interpolate` (nearest)"""
+        super().__init__(start_step, start_layer, layer_idx, step_idx, total_steps, model_type)
+        self.mask_s = mask_s
+        self.mask_t = mask_t
+        print("Using mask-guided MasaCtrl")
+        if mask_save_dir is not None:
+            os.makedirs(mask_save_dir, exist_ok=True)
+            _save_mask_png(self.mask_s, os.path.join(mask_save_dir, "mask_s.png"))
+            _save_mask_png(self.mask_t, os.path.join(mask_save_dir, "mask_t.png"))
+
+    def attn_batch(self, q, k, v, sim, attn, is_cross, place_in_unet, num_heads, **kwargs):
+        """as the parent's; with is_mask_attn and a source mask the scores are taken twice, fg (keys outside the mask at
+        finfo.min, the others + 1) and bg (keys inside at finfo.min), and the outputs come back as [fg rows | bg rows]"""
+        bh, n, d = q.shape
+        b = bh // num_heads
+        H = W = int(n ** 0.5)
+        # only q is regrouped to h (b n) d: k / v are ONE sample's [h, n, d], which is all `forward` ever passes
+        assert k.shape[0] == num_heads and v.shape[0] == num_heads, "attn_batch: k / v must be one sample's [heads, n, d]"
+        qh = q.reshape(b, num_heads, n, d).permute(1, 0, 2, 3).reshape(num_heads, b * n, d)
+        s = torch.bmm(qh, k.transpose(1, 2)) * kwargs.get("scale")
+        if kwargs.get("is_mask_attn") and self.mask_s is not None:
+            print("masked attention")
+            mask = F.interpolate(self.mask_s[None, None].to(device=s.device, dtype=s.dtype), (H, W)).flatten()
+            lowest = torch.finfo(s.dtype).min
+            s_bg = s + mask.masked_fill(mask == 1, lowest)
+            s_fg = s + mask.masked_fill(mask == 0, lowest)
+            s = torch.cat([s_fg, s_bg], dim=0)
+        p = s.softmax(-1)
+        if len(p) == 2 * len(v):
+            v = torch.cat([v] * 2)
+        out = torch.bmm(p, v)                                       # (h1 h) (b n) d
+        h1 = out.shape[0] // num_heads
+        return out.reshape(h1, num_heads, b, n, d).permute(0, 2, 3, 1, 4).reshape(h1 * b, n, num_heads * d)
+
+    def forward(self, q, k, v, sim, attn, is_cross, place_in_unet, num_heads, **kwargs):
+        if is_cross or self.cur_step not in self.step_idx or self.cur_att_layer // 2 not in self.layer_idx:
+            return AttentionBase.forward(self, q, k, v, sim, attn, is_cross, place_in_unet, num_heads, **kwargs)
+        n = q.shape[1]
+        H = W = int(n ** 0.5)
+        qu, qc = q.chunk(2)
+        ku, kc = k.chunk(2)
+        vu, vc = v.chunk(2)
+        args = (None, None, is_cross, place_in_unet, num_heads)
+        out_u_source = self.attn_batch(qu[:num_heads], ku[:num_heads], vu[:num_heads], *args, **kwargs)
+        out_c_source = self.attn_batch(qc[:num_heads], kc[:num_heads], vc[:num_heads], *args, **kwargs)
+        out_u_target = self.attn_batch(qu[-num_heads:], ku[:num_heads], vu[:num_heads], *args, is_mask_attn=True, **kwargs)
+        out_c_target = self.attn_batch(qc[-num_heads:], kc[:num_heads], vc[:num_heads], *args, is_mask_attn=True, **kwargs)
+        if self.mask_s is not None and self.mask_t is not None:
+            out_u_fg, out_u_bg = out_u_target.chunk(2, 0)
+            out_c_fg, out_c_bg = out_c_target.chunk(2, 0)
+            mask = F.interpolate(self.mask_t[None, None].to(device=q.device, dtype=out_u_fg.dtype), (H, W)).reshape(-1, 1)
+            out_u_target = out_u_fg * mask + out_u_bg * (1 - mask)
+            out_c_target = out_c_fg * mask + out_c_bg * (1 - mask)
+        return torch.cat([out_u_source, out_u_target, out_c_source, out_c_target], dim=0)
+
+
+def load_mask_png(path, device="cpu"):
+    """a mask image -> fp32 [h, w] in {0, 1}: grey levels / 255 thresholded at 0.5 (the CLIs' --mask_s / --mask_t)"""
+    import numpy as np
+    from PIL import Image
+    g = torch.from_numpy(np.asarray(Image.open(path).convert("L"), dtype=np.float32) / 255.0)
+    return (g > 0.5).float().to(device)

@@ -5,13 +5,15 @@ The reference patches every `Attention.forward` with a closure that materialises
 ([B*heads, N, N]: 2 GiB each in fp32 at 64x64) and hands them to the editor (:35-48).  Here the two editor classes
 the reference CLIs use — `AttentionBase` (plain attention) and `MutualSelfAttentionControl` — are lowered to a
 device plan: the fused flash-attention kernel takes per-batch K/V source rows, which IS mutual self-attention
-(`ief_attn_flash_f16`, k_src / v_src).  Any OTHER editor (a user subclass of `AttentionBase`, the store / mask
-variants) takes the GENERIC path: a closure with the reference's dataflow (:10-48) on our kernels materialises `sim` and
+(`ief_attn_flash_f16`, k_src / v_src).  `MutualSelfAttentionControlMask` with two binary masks is lowered too where
+the planes attention runs (f16x3): the mutual launch plus two launches over gathered row lists (`control.py`,
+kind 'masactrl_mask'); `lower_editor` prints why when it cannot.  Any OTHER editor (a user subclass of `AttentionBase`,
+the store / auto-mask variants) takes the GENERIC path: a closure with the reference's dataflow (:10-48) on our kernels materialises `sim` and
 `attn` ([B*heads, N, L]) and calls the editor's Python, exactly as `p2p/model/register.py` does for controllers.
 """
 import torch
 
-from ... import hip
+from ... import hip, planes
 from ...control import ControlPlan
 
 
@@ -23,12 +25,68 @@ def _attention_modules(unet):
     return out
 
 
-def lower_editor(editor, device):
+def _controlled_self_layers(unet, layers):
+    """(head dim, tokens) of the self-attention of every transformer layer in `layers` (layer = execution index // 2), at
+    the UNet's configured sample size"""
+    out, res = [], int(unet.cfg.sample_size)
+
+    def visit(block):
+        for m in block.modules():
+            if m.__class__.__name__ == "Attention" and not m.is_cross and (m._exec_index // 2) in layers:
+                out.append((m.dim_head, res * res))
+
+    for blk in unet.down_blocks:
+        visit(blk)
+        if blk.downsamplers is not None:
+            res //= 2
+    visit(unet.mid_block)
+    for blk in unet.up_blocks:
+        visit(blk)
+        if blk.upsamplers is not None:
+            res *= 2
+    return out
+
+
+def _lower_mask_editor(editor, device, unet):
+    """the fused plan of `MutualSelfAttentionControlMask`, or None with one printed line saying why not.  The resolutions are
+    those of the UNet's configured sample size (the latent size is not known at registration); latents of another size get
+    their lists at the first forward, where an empty key class is an error instead of a fall-back"""
+    def no(why):
+        print(f"mask-guided MasaCtrl takes the generic path: {why}")
+        return None
+
+    if unet is None or getattr(unet, "precision", None) != "f16x3" or not getattr(unet, "x3p", False) or not planes.FLASH_PLANES:
+        return no("the fused rule runs on the planes attention of the f16x3 mode only")
+    ms, mt = editor.mask_s, editor.mask_t
+    if ms is None or mt is None:
+        return no("it needs both mask_s and mask_t")
+    for m, nm in ((ms, "mask_s"), (mt, "mask_t")):
+        if not (isinstance(m, torch.Tensor) and m.dim() == 2 and m.shape[0] == m.shape[1]):
+            return no(f"{nm} is not a square [h, w] tensor")
+        if not bool(((m == 0) | (m == 1)).all()):
+            return no(f"{nm} is not binary (values other than 0 and 1)")
+    layers = set(int(l) for l in editor.layer_idx)
+    shapes = _controlled_self_layers(unet, layers)
+    for d, N in shapes:
+        if d not in planes.FLASH_PLANES_DIMS:
+            return no(f"a controlled layer has head dim {d}, outside the planes attention's {planes.FLASH_PLANES_DIMS}")
+    tokens = sorted(set(N for _, N in shapes))
+    for N in tokens:
+        r = ControlPlan.resized_mask(ms.detach().float().cpu(), N)
+        if not bool((r == 1).any()) or not bool((r == 0).any()):
+            return no(f"mask_s has an empty key class at {N} tokens")
+    return ControlPlan(editor, "masactrl_mask", device, masa_steps=editor.step_idx, masa_layers=layers,
+                       mask_s=ms, mask_t=mt, mask_tokens=tokens)
+
+
+def lower_editor(editor, device, unet=None):
     name = type(editor).__name__
     if name == "AttentionBase":
         return ControlPlan(editor, "empty", device)
     if name == "MutualSelfAttentionControl":
         return ControlPlan(editor, "masactrl", device, masa_steps=editor.step_idx, masa_layers=editor.layer_idx)
+    if name == "MutualSelfAttentionControlMask":
+        return _lower_mask_editor(editor, device, unet)
     return None
 
 
@@ -66,7 +124,7 @@ def _places(unet):
 
 def regiter_attention_editor_diffusers(model, editor):
     unet = model.unet
-    plan = lower_editor(editor, unet.device)
+    plan = lower_editor(editor, unet.device, unet)
     mods = _places(unet)
     for place, m in mods:
         m.__dict__.pop("forward", None)

@@ -567,14 +567,34 @@ def attn_key_splits(B, heads, N, L, d, cus=None, setting="auto") -> int:
     return -(-nt // T)
 
 
-def attn_flash(q, k, v, heads, scale, q_src=None, k_src=None, v_src=None, out=None, out_planes=True, lse=None, key_splits=1):
+def attn_flash(q, k, v, heads, scale, q_src=None, k_src=None, v_src=None, out=None, out_planes=True, lse=None, key_splits=1,
+               q_idx=None, k_idx=None, gate=None):
     """fused attention on operand planes: q [B,N,h*d], k / v [B,L,h*d] as Planes (column slices of the q|k|v GEMM's output are
     fine); K / V tiles are staged by LDS-DMA, nothing is split in the kernel (`attn_flash_x3p_kernel`).  Returns Planes (for
     to_out's GEMM) or, with out_planes=False, fp32.
     lse: optional contiguous fp32 [B, heads, N] receiving the row log-sum-exp (log2 units) that `hip.attn_bwd` consumes.
     key_splits: 1 (the single launch), an int or "auto" (`attn_key_splits`): the keys of every query block go over that many
-    workgroups (partials in a torch-allocated fp32 workspace -- fine inside graph capture) and one combine launch merges them."""
+    workgroups (partials in a torch-allocated fp32 workspace -- fine inside graph capture) and one combine launch merges them.
+    q_idx / k_idx (int32 device lists, both or neither): attention over GATHERED token rows -- query slot i is row q_idx[i] of q and
+    its output goes to that same row of the destination, key slot j is row k_idx[j] of k and v.  Only the listed rows are written,
+    so the destination must exist: `out=` an fp32 tensor or `out_planes=` a Planes, [Bo, rows, heads*d] (batch-strided views are
+    fine); the launch's batch is Bo and q_src / k_src / v_src (Bo entries each) pick the operands' batch rows.  Every index must
+    be a row of the operand it addresses: the lists live on the device and are NOT checked here.  gate: optional int32 device
+    scalar; the launch writes nothing while it holds 0.  No lse and no key split with lists (ValueError)."""
     lib = hip.load()
+    idx = q_idx is not None or k_idx is not None
+    if idx and (q_idx is None or k_idx is None):
+        raise ValueError("planes.attn_flash: q_idx and k_idx go together")
+    if gate is not None and not idx:
+        raise ValueError("planes.attn_flash: gate needs q_idx / k_idx")
+    if idx and (lse is not None or key_splits != 1):
+        raise ValueError("planes.attn_flash: a gathered launch (q_idx / k_idx) writes no lse and does not split its keys")
+    dest_p = out_planes if isinstance(out_planes, Planes) else None
+    if idx and dest_p is None and out is None:
+        raise ValueError("planes.attn_flash: with q_idx / k_idx only the listed rows are written: pass the existing destination "
+                         "as out= (fp32) or out_planes= (Planes)")
+    if dest_p is not None and not idx:
+        raise ValueError("planes.attn_flash: out_planes=<Planes> is the destination of a gathered launch (q_idx / k_idx)")
     for t, nm in ((q, "q"), (k, "k"), (v, "v")):
         if not isinstance(t, Planes) or t.dim() != 3:
             raise TypeError(f"planes.attn_flash: {nm} must be Planes [B, rows, heads*d]")
@@ -592,6 +612,22 @@ def attn_flash(q, k, v, heads, scale, q_src=None, k_src=None, v_src=None, out=No
     p.ldq, p.ldk, p.ldv = q.hi.stride(1), k.hi.stride(1), v.hi.stride(1)
     p.sQb, p.sKb, p.sVb = q.hi.stride(0), k.hi.stride(0), v.hi.stride(0)
     p.B, p.heads, p.N, p.L, p.d, p.scale = B, heads, N, L, d, scale
+    if idx:
+        hip._devi32(q_idx, "q_idx"), hip._devi32(k_idx, "k_idx"), hip._devi32(gate, "gate")
+        if q_idx.dim() != 1 or k_idx.dim() != 1 or not 1 <= q_idx.numel() <= N or not 1 <= k_idx.numel() <= L:
+            raise ValueError("planes.attn_flash: q_idx / k_idx must be non-empty 1-D lists no longer than the operand's rows")
+        rows_q = N
+        dest = dest_p.hi if dest_p is not None else hip._act32(out, "out")
+        if dest.dim() != 3 or dest.shape[1] != rows_q or dest.shape[2] != C:
+            raise ValueError(f"planes.attn_flash: the destination must be [Bo, {rows_q}, {C}]")
+        B, N, L = dest.shape[0], q_idx.numel(), k_idx.numel()
+        for t, nm in ((q_src, "q_src"), (k_src, "k_src"), (v_src, "v_src")):
+            if t is not None and t.numel() != B:
+                raise ValueError(f"planes.attn_flash: {nm} must have one entry per destination batch row ({B})")
+            if t is None and B != q.shape[0]:
+                raise ValueError(f"planes.attn_flash: a destination of {B} batch rows over operands of {q.shape[0]} needs {nm}")
+        p.B, p.N, p.L = B, N, L
+        p.q_idx, p.k_idx, p.gate = q_idx.data_ptr(), k_idx.data_ptr(), _ptr(gate)
     p.q_src, p.k_src, p.v_src = _ptr(hip._devi32(q_src, "q_src")), _ptr(hip._devi32(k_src, "k_src")), _ptr(hip._devi32(v_src, "v_src"))
     p.x3, p.zeros = 1, _zeros(q.device)
     if lse is not None:
@@ -599,7 +635,16 @@ def attn_flash(q, k, v, heads, scale, q_src=None, k_src=None, v_src=None, out=No
             raise ValueError("planes.attn_flash: lse must be contiguous fp32 [B, heads, N]")
         p.lse = lse.data_ptr()
     op = None
-    if out_planes:
+    if dest_p is not None:
+        op, h_ = dest_p, dest_p.hi
+        if h_.stride(2) != 1:
+            raise ValueError("planes.attn_flash: out_planes rows must be contiguous")
+        p.OutP, p.planeO, p.sOPb, p.ldp = h_.data_ptr(), dest_p.plane, h_.stride(0), h_.stride(1)
+        if out is not None:
+            if tuple(hip._act32(out, "out").shape) != tuple(h_.shape):
+                raise ValueError("planes.attn_flash: out and out_planes must have one shape")
+            p.Out, p.sOb, p.ldo = out.data_ptr(), out.stride(0), out.stride(1)
+    elif out_planes and not idx:
         op, _ = attn_out_args(p, B, N, C, q.device)
     else:
         if out is None:
@@ -607,11 +652,13 @@ def attn_flash(q, k, v, heads, scale, q_src=None, k_src=None, v_src=None, out=No
         p.Out, p.sOb, p.ldo = hip._act32(out, "out").data_ptr(), out.stride(0), out.stride(1)
     S = 1 if key_splits == 1 else attn_key_splits(B, heads, N, L, d, setting=key_splits)
     name, nbytes = f"attn_flash_x3p_kernel<{d}>", 4.0 * B * heads * d * (2 * N + 2 * L)
-    if S > 1:
+    if idx:
+        name = f"attn_flash_x3p_kernel<{d}, idx>"
+    elif S > 1:
         nws = lib.ief_attn_flash_ws_floats(B, heads, N, L, d, S)
         ws = torch.empty(nws, dtype=torch.float32, device=q.device)
         p.key_splits, p.ws, p.ws_floats = S, ws.data_ptr(), nws
         name, nbytes = f"attn_flash_x3p_kernel<{d}, split {S}> + attn_flash_x3p_combine_kernel", nbytes + 8.0 * nws
     with _Timed(name, 4.0 * B * heads * N * L * d, nbytes):
         _check(lib.ief_attn_flash_f32(byref(p), _stream()), "ief_attn_flash_f32 (planes)")
-    return op if out_planes else out
+    return op if op is not None else out

@@ -294,8 +294,20 @@ class Attention(nn.Module):
                 qkv = planes.gemm(xp, w_in, bias=b_in, ln=ln, out=False, out_planes=True)
                 o = planes.attn_flash(qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:], self.heads, self.scale, q_src=qs,
                                       k_src=ks, v_src=vs, key_splits=self.attn_key_splits)
+                ml = plan.mask_launches(B, N, self) if plan is not None else None
+                if ml is not None:
+                    # mask-guided MasaCtrl: the launch above did mutual attention for every row; the target rows are now
+                    # overwritten by attention of the queries inside (outside) mask_t over their half's source keys inside
+                    # (outside) mask_s -- gathered row lists, disjoint output rows, nothing written while the step's gate is 0
+                    tgt, src, gate, pairs = ml
+                    for q_idx, k_idx in pairs:
+                        planes.attn_flash(qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:], self.heads, self.scale, q_src=tgt,
+                                          k_src=src, v_src=src, out_planes=o[1::2], q_idx=q_idx, k_idx=k_idx, gate=gate)
             else:
                 qkv = planes.gemm(xp, w_in, bias=b_in, ln=ln)
+                if plan is not None and plan.mask_launches(B, N, self) is not None:
+                    raise RuntimeError(f"mask-guided MasaCtrl was lowered onto a layer of head dim {self.dim_head} that has no "
+                                       "planes attention")
                 o = hip.attn_flash(qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:], self.heads, self.scale, q_src=qs, k_src=ks,
                                    v_src=vs, out_planes=True)
         else:

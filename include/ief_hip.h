@@ -326,6 +326,14 @@ typedef struct IefAttnF32Params {
      * until the stream passes; ws_floats: its size.  Without Qp or with x3 == 0, key_splits > 1 is IEF_EINVAL; so are a null or
      * short ws; a misaligned one is IEF_EALIGN. */
     int key_splits; float* ws; long long ws_floats;
+    /* operand planes in (Qp set) only, appended to ABI 4; all null = the launch above.  Attention over GATHERED token rows:
+     * q_idx int32 [N]: query slot i reads row q_idx[i] of Q and its output goes to that same row of Out / OutP (rows not listed
+     * are not written); k_idx int32 [L]: key slot j is row k_idx[j] of K and of V.  N and L are the LIST lengths; every index
+     * must be a row of the operand it addresses (the library cannot check device lists).  Both lists or neither (IEF_EINVAL);
+     * q_src / k_src / v_src select batch rows as ever.  gate: optional device int32; *gate == 0 makes the launch write
+     * nothing (a captured step graph keeps the launch, a per-step table switches it).  With lse or key_splits > 1, without
+     * Qp or with x3 == 0: IEF_EINVAL; a pointer that is not 4-byte aligned: IEF_EALIGN.  d in {40, 64, 80}. */
+    const int* q_idx; const int* k_idx; const int* gate;
 } IefAttnF32Params;
 int ief_attn_flash_f32(const IefAttnF32Params* p, void* stream);
 /* fp32 elements of IefAttnF32Params.ws that the launch needs after clamping key_splits; 0 when it would not split */
