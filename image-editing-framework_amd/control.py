@@ -232,6 +232,24 @@ class ControlPlan:
         tgt, src = self._mask_rows[B]
         return tgt, src, self._gate[1], [(q, k) for q, k in ((fq, fk), (bq, bk)) if q.numel() > 0]
 
+    def controls_first_self(self, unet, tokens: int) -> bool:
+        """does this plan act, in ANY step of its schedule, on the self-attention of the UNet's first transformer (`tokens`
+        queries)?  Decided from what `signature` states -- which layers, which token limit -- never from a step window or a
+        table's contents: those change under a captured graph, and a re-pointed loop (`load_from`) keeps its launches.  The
+        shared prefix of a CFG step (`denoise.cfg_shared_prefix_reason`) runs that self-attention once for both halves of the
+        batch, which is only right while no plan redirects its rows."""
+        blk = unet.down_blocks[0]
+        if not blk.attentions:
+            return False
+        first = blk.attentions[0].transformer_blocks[0].attn1
+        if self.kind == "p2p":         # `/root/reference/p2p/model/attention_base.py:133`: self-attention replace at <= 16^2 keys
+            return tokens <= self.self_max_tokens
+        if self.kind in ("masactrl", "masactrl_mask"):
+            return (first._exec_index // 2) in self.masa_layers
+        if self.kind == "pnp":
+            return id(first) in self.pnp_layers
+        return False
+
     # ------------------------------------------------------------------ re-use of a captured loop (denoise.acquire)
     def signature(self, unet):
         """everything about this plan that is BAKED into a captured step graph (which kernels run, on which modules,

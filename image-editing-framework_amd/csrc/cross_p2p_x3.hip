@@ -21,7 +21,9 @@
 #include "ief_params.h"
 #include "x3_common.h"
 
-template <int D>
+// QS: Q's batch rows go through p.q_src (a CFG step whose two halves share one query projection hands B/2 rows of Q to a launch of
+// B rows); a template parameter so that the launches without it keep their instruction stream.
+template <int D, bool QS = false>
 __global__ __launch_bounds__(256, (D > 80) ? 1 : 2) void attn_cross_p2p_x3_kernel(const IefAttnF32Params p, const int* __restrict__ edit_src,
                                                                                   const int* __restrict__ edit_slot,
                                                                                   const float* __restrict__ MT,
@@ -63,7 +65,7 @@ __global__ __launch_bounds__(256, (D > 80) ? 1 : 2) void attn_cross_p2p_x3_kerne
     constexpr int NLD = (KCH + 255) / 256;
     // normalised maps of batch row `br` for this wave's 32 queries: P[t][r] = softmax over ALL keys, keys >= L exactly 0
     auto probs = [&](int br, f32x16 (&P)[3]) {
-        const float* Q = p.Q + (long long)br * p.sQb + (long long)h * D;
+        const float* Q = p.Q + (long long)(QS ? p.q_src[br] : br) * p.sQb + (long long)h * D;
         const float* Kp = p.K + (long long)br * p.sKb + (long long)h * D;
         half8_t qh[DG], ql[DG];
 #pragma unroll
@@ -308,29 +310,37 @@ __global__ __launch_bounds__(256, (D > 80) ? 1 : 2) void attn_cross_p2p_x3_kerne
     }
 }
 
-// Cross-attention with the fused map edit on fp32 operands, split-operand arithmetic.  p: as ief_attn_flash_f32 (no batch-row
-// indirection: q_src / k_src / v_src must be NULL; L <= 96; d in {40, 64, 80, 160}; 16-byte aligned rows); edit_src / edit_slot /
-// MT / coef as ief_p2p_cross_edit_f32 (edit_src NULL: plain attention).
+// Cross-attention with the fused map edit on fp32 operands, split-operand arithmetic.  p: as ief_attn_flash_f32 (L <= 96; d in
+// {40, 64, 80, 160}; 16-byte aligned rows); edit_src / edit_slot / MT / coef as ief_p2p_cross_edit_f32 (edit_src NULL: plain
+// attention).  q_src (B device int32 entries, or NULL): row b's maps read Q from batch row q_src[b], its source row's maps from
+// q_src[edit_src[b]]; K and V stay on rows b / edit_src[b] (k_src / v_src must be NULL).  The entries must be rows of Q: the
+// caller checks them where it builds the list (the library cannot check device lists).
 extern "C" int ief_attn_cross_p2p_f32(const IefAttnF32Params* pp, const int* edit_src, const int* edit_slot, const float* MT,
                                       const float* coef, void* stream) {
     if (!pp) return IEF_EINVAL;
     const IefAttnF32Params& p = *pp;
-    if (!p.Q || !p.K || !p.V || (!p.Out && !p.OutP) || p.q_src || p.k_src || p.v_src) return IEF_EINVAL;
+    if (!p.Q || !p.K || !p.V || (!p.Out && !p.OutP) || p.k_src || p.v_src) return IEF_EINVAL;
     if (p.OutP && ((p.ldp & 3) || (p.sOPb & 3) || (p.planeO & 3) || ((uintptr_t)p.OutP & 7))) return IEF_EALIGN;
     if (p.p_scale != 0.f && !(p.p_scale >= 1.f && p.p_scale <= 16384.f)) return IEF_EINVAL;
     if (edit_src && (!edit_slot || !MT || !coef)) return IEF_EINVAL;
     if (p.B <= 0 || p.heads <= 0 || p.N <= 0 || p.L <= 0 || p.L > 96) return IEF_ESHAPE;
     if ((p.ldq & 3) || (p.ldk & 3) || (p.ldv & 3) || (p.ldo & 3) || (p.sQb & 3) || (p.sKb & 3) || (p.sVb & 3) || (p.sOb & 3) ||
         (((uintptr_t)p.Q | (uintptr_t)p.K | (uintptr_t)p.V | (uintptr_t)(p.Out ? p.Out : p.Q) | (uintptr_t)(MT ? MT : p.Q)) & 15)) return IEF_EALIGN;
+    if ((uintptr_t)p.q_src & 3) return IEF_EALIGN;
     hipStream_t st = (hipStream_t)stream;
     dim3 grid((p.N + 127) / 128, p.B * p.heads);
+#define IEF_CROSS_X3_LAUNCH(D)                                                                                                  \
+    if (p.q_src) hipLaunchKernelGGL((attn_cross_p2p_x3_kernel<D, true>), grid, dim3(256), 0, st, p, edit_src, edit_slot, MT, coef); \
+    else hipLaunchKernelGGL((attn_cross_p2p_x3_kernel<D, false>), grid, dim3(256), 0, st, p, edit_src, edit_slot, MT, coef);       \
+    break
     switch (p.d) {
-        case 40: hipLaunchKernelGGL(attn_cross_p2p_x3_kernel<40>, grid, dim3(256), 0, st, p, edit_src, edit_slot, MT, coef); break;
-        case 64: hipLaunchKernelGGL(attn_cross_p2p_x3_kernel<64>, grid, dim3(256), 0, st, p, edit_src, edit_slot, MT, coef); break;
-        case 80: hipLaunchKernelGGL(attn_cross_p2p_x3_kernel<80>, grid, dim3(256), 0, st, p, edit_src, edit_slot, MT, coef); break;
-        case 160: hipLaunchKernelGGL(attn_cross_p2p_x3_kernel<160>, grid, dim3(256), 0, st, p, edit_src, edit_slot, MT, coef); break;
+        case 40: IEF_CROSS_X3_LAUNCH(40);
+        case 64: IEF_CROSS_X3_LAUNCH(64);
+        case 80: IEF_CROSS_X3_LAUNCH(80);
+        case 160: IEF_CROSS_X3_LAUNCH(160);
         default: return IEF_ESHAPE;
     }
+#undef IEF_CROSS_X3_LAUNCH
     IEF_LAUNCH_CHECK();
     return IEF_OK;
 }

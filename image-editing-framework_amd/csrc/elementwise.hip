@@ -215,6 +215,44 @@ extern "C" int ief_gather_rows_f16(const ief_half* in, ief_half* out, const int*
     return IEF_OK;
 }
 
+// dst[r] = src[r % Bp] for r in [0, 2 Bp): a tensor computed once for the Bp rows both halves of a CFG batch share, repeated where
+// a consumer reads 2 Bp rows.  One launch, up to IEF_REPEAT_MAX_JOBS tensors (blockIdx.y); a job is `blocks` blocks of `bytes`
+// contiguous bytes (the Bp rows; operand planes [2][Bp]...: two blocks), block k read at src + k bytes and written at
+// dst + 2 k bytes and again `bytes` further.  16-byte loads and stores.
+struct RepeatJobs { IefRepeatJob j[IEF_REPEAT_MAX_JOBS]; };
+__global__ __launch_bounds__(256) void repeat_batch_kernel(const RepeatJobs jobs) {
+    const IefRepeatJob jb = jobs.j[blockIdx.y];
+    const long long per = jb.bytes >> 4, total = per * jb.blocks;
+    const f32x4* __restrict__ src = (const f32x4*)jb.src;
+    f32x4* __restrict__ dst = (f32x4*)jb.dst;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        const long long k = i / per, c = i - k * per;
+        const f32x4 v = src[i];
+        dst[2 * k * per + c] = v;
+        dst[(2 * k + 1) * per + c] = v;
+    }
+}
+extern "C" int ief_repeat_batch(const IefRepeatJob* jobs, int njobs, void* stream) {
+    if (!jobs) return IEF_EINVAL;
+    if (njobs <= 0 || njobs > IEF_REPEAT_MAX_JOBS) return IEF_ESHAPE;
+    RepeatJobs a = {};
+    long long most = 0;
+    for (int i = 0; i < njobs; ++i) {
+        const IefRepeatJob& j = jobs[i];
+        if (!j.src || !j.dst) return IEF_EINVAL;
+        if (j.bytes <= 0 || j.blocks <= 0) return IEF_ESHAPE;
+        if ((j.bytes & 15) || (((uintptr_t)j.src | (uintptr_t)j.dst) & 15)) return IEF_EALIGN;
+        a.j[i] = j;
+        const long long chunks = (j.bytes >> 4) * j.blocks;
+        most = chunks > most ? chunks : most;
+    }
+    long long grid = (most + 255) / 256;
+    if (grid > 2048) grid = 2048;
+    hipLaunchKernelGGL(repeat_batch_kernel, dim3((unsigned)grid, (unsigned)njobs), dim3(256), 0, (hipStream_t)stream, a);
+    IEF_LAUNCH_CHECK();
+    return IEF_OK;
+}
+
 __global__ __launch_bounds__(256) void cast_f32_f16_kernel(const float* __restrict__ x, half_t* __restrict__ o, long long n) {
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) o[i] = (half_t)x[i];
 }

@@ -1477,10 +1477,13 @@ extern "C" int ief_gather_rows_f32(const float* in, float* out, const int* src, 
 // CIN > 0: the channel count is a compile-time constant and every load of a tap ROW (3 taps x CIN activations, 3 x CIN weight
 // vectors) is requested before the first is used -- the plain loop below issued 9 x Cin dependent load pairs per thread (40 us for
 // the 0.38 GFLOP of SD's 4 -> 320 at 64 x 64, batch 4).  The accumulation order (tap, channel) is the loop's: same bits.
-template <int CIN>
+// PL: the launch also writes the result's operand planes (hi at outp, lo `plane` elements further, rows of Cout) -- the split of
+// the very fp32 value it stores, by the split4 every planes producer uses, so the standalone splitter launch is not needed.
+template <int CIN, bool PL = false>
 __global__ __launch_bounds__(256) void conv_in_f32_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                           const float* __restrict__ bias, float* __restrict__ out, int B, int Cin,
-                                                          int H, int Wd, int Cout) {
+                                                          int H, int Wd, int Cout, half_t* __restrict__ outp = nullptr,
+                                                          long long plane = 0) {
     const int C4 = Cout >> 2;
     const long long total = (long long)B * H * Wd * C4;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
@@ -1534,6 +1537,13 @@ __global__ __launch_bounds__(256) void conv_in_f32_kernel(const float* __restric
             for (int e = 0; e < 4; ++e) acc[e] += bias[c4 * 4 + e];
         }
         *(f32x4*)(out + pix * Cout + c4 * 4) = acc;
+        if constexpr (PL) {
+            half4 hh, ll;
+            split4(acc, 1.0f, hh, ll);
+            half_t* op = outp + pix * Cout + c4 * 4;
+            *(half4*)op = hh;
+            *(half4*)(op + plane) = ll;
+        }
     }
 }
 extern "C" int ief_conv_in_f32act(const float* x, const float* w, const float* bias, float* out, int B, int Cin, int H, int Wd,
@@ -1544,8 +1554,24 @@ extern "C" int ief_conv_in_f32act(const float* x, const float* w, const float* b
     const long long total = (long long)B * H * Wd * (Cout / 4);
     int grid = (int)((total + 255) / 256);
     if (grid > 8192) grid = 8192;
-    if (Cin == 4) hipLaunchKernelGGL(conv_in_f32_kernel<4>, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, w, bias, out, B, Cin, H, Wd, Cout);
-    else hipLaunchKernelGGL(conv_in_f32_kernel<0>, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, w, bias, out, B, Cin, H, Wd, Cout);
+    if (Cin == 4) hipLaunchKernelGGL((conv_in_f32_kernel<4, false>), dim3(grid), dim3(256), 0, (hipStream_t)stream, x, w, bias, out, B, Cin, H, Wd, Cout, (half_t*)nullptr, 0ll);
+    else hipLaunchKernelGGL((conv_in_f32_kernel<0, false>), dim3(grid), dim3(256), 0, (hipStream_t)stream, x, w, bias, out, B, Cin, H, Wd, Cout, (half_t*)nullptr, 0ll);
+    IEF_LAUNCH_CHECK();
+    return IEF_OK;
+}
+
+// conv_in that also writes the operand planes of its result (f16x3 trunk: conv_in's output is a skip connection and a shortcut
+// source, both read as planes): outp hi plane [B,H,W,Cout] fp16, lo plane `plane` elements further; 8-byte aligned, plane % 4 == 0
+extern "C" int ief_conv_in_f32act_planes(const float* x, const float* w, const float* bias, float* out, ief_half* outp, long long plane,
+                                         int B, int Cin, int H, int Wd, int Cout, void* stream) {
+    if (!x || !w || !out || !outp) return IEF_EINVAL;
+    if (B <= 0 || H <= 0 || Wd <= 0 || Cin <= 0 || Cin > 8 || Cout <= 0 || (Cout & 3) || plane <= 0 || (plane & 3)) return IEF_ESHAPE;
+    if ((((uintptr_t)w | (uintptr_t)out) & 15) || ((uintptr_t)outp & 7)) return IEF_EALIGN;
+    const long long total = (long long)B * H * Wd * (Cout / 4);
+    int grid = (int)((total + 255) / 256);
+    if (grid > 8192) grid = 8192;
+    if (Cin == 4) hipLaunchKernelGGL((conv_in_f32_kernel<4, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, x, w, bias, out, B, Cin, H, Wd, Cout, (half_t*)outp, plane);
+    else hipLaunchKernelGGL((conv_in_f32_kernel<0, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, x, w, bias, out, B, Cin, H, Wd, Cout, (half_t*)outp, plane);
     IEF_LAUNCH_CHECK();
     return IEF_OK;
 }

@@ -10,11 +10,14 @@ overhead would exceed the GPU time.  Here the whole step is captured once:
     [P2P plan: select_step(gate coefficients), select_step(self-replace sources)]
     latents -> CFG batch copy -> UNet (fused attention control) -> fused CFG + DDIM update (in place)
     advance_step
+(on the f16x3 planes trunk the UNet takes the latents themselves and runs what both halves of the CFG batch share once: no copy;
+`cfg_shared_prefix_reason`)
 
 so a 50-step edit is 50 graph replays with no host work in between; everything that varies
 with the step is a per-step table row selected on the device.  Static buffers: latents (fp32
 NCHW), the CFG batch, the fp16 context (per-step rows when null-text embeddings are supplied).
 """
+import logging
 import os
 from typing import Dict, List, Optional
 
@@ -28,6 +31,52 @@ from . import hip
 REUSE_GRAPHS = os.environ.get("IEF_REUSE_GRAPHS", "1") == "1"
 _POOL: Dict[tuple, list] = {}
 _POOL_CAP = 8
+
+# A CFG step feeds the UNet cat([latents] * 2) (`/root/reference/p2p/model/sd_utils.py:72`) and ONE time-embedding row: rows b and
+# b + Bp are bit-identical until the first launch that reads the context, the cross-attention of down_blocks[0].attentions[0].
+# Where nothing else tells the halves apart (`cfg_shared_prefix_reason`) that prefix -- conv_in, the first resnet, the first
+# transformer's GroupNorm, proj_in, LayerNorm 1, q|k|v, the 64 x 64 self-attention, to_out, LayerNorm 2, the cross-attention's
+# to_q -- runs once, at Bp rows.  IEF_CFG_SHARED_PREFIX=0: every loop builds the CFG batch and runs it whole (A/B runs).
+CFG_SHARED_PREFIX = os.environ.get("IEF_CFG_SHARED_PREFIX", "1") == "1"
+_log = logging.getLogger("ief_amd.denoise")
+_said = set()
+
+
+def cfg_shared_prefix_reason(*, mode, cfg, x3p, aug, first_block_cross, native, fused_cross, ln_folded, plan_on_first_self,
+                             taps=False, enabled=True):
+    """None where a CFG denoising step may run the prefix its two halves share once (at Bp rows), else the reason why not -- a pure
+    function of host-side facts (`UNet2DConditionModel.cfg_shared_facts` collects the model's):
+      mode / cfg          the loop is `denoise` with classifier-free guidance (inversion and the no-CFG loops have no second half)
+      x3p                 the trunk runs on f16x3 operand planes (the only trunk with the seam)
+      aug                 SDXL's additional embedding gives every batch row its own time-embedding row: the halves differ from conv_in on
+      first_block_cross   down_blocks[0] has transformers (SDXL's does not: nothing to share before the first context read)
+      native              no hook owns an attention module of down_blocks[0] (a Python controller sees, and may edit, every row)
+      fused_cross         the first cross-attention takes the fused split-operand kernel, the one launch with Q batch-row indirection
+      ln_folded           IEF_X3P_FOLD_LN=1 (an A/B form of the transformer blocks that has no seam)
+      plan_on_first_self  the control plan redirects rows of the first self-attention in some step (`ControlPlan.controls_first_self`)
+      taps                a debugging forward that records intermediate tensors at full batch
+      enabled             IEF_CFG_SHARED_PREFIX"""
+    if not enabled:
+        return "switched off (IEF_CFG_SHARED_PREFIX=0)"
+    if mode != "denoise" or not cfg:
+        return "not a classifier-free-guidance denoising loop"
+    if not x3p:
+        return "the trunk does not run on f16x3 operand planes"
+    if aug:
+        return "the additional (text-time) embedding differs between the halves of the batch"
+    if not first_block_cross:
+        return "down_blocks[0] has no cross-attention"
+    if not native:
+        return "an attention module of down_blocks[0] is on the generic (hooked) path"
+    if not fused_cross:
+        return "the first cross-attention does not take the fused split-operand kernel"
+    if ln_folded:
+        return "the transformer LayerNorms are folded (IEF_X3P_FOLD_LN=1)"
+    if taps:
+        return "intermediate tensors are tapped"
+    if plan_on_first_self:
+        return "the control plan acts on the self-attention of the first transformer"
+    return None
 
 
 def _check_finite(lat, unet):
@@ -58,7 +107,15 @@ class FusedDenoiser:
         h, w = latent_hw
         C = self.unet.config.in_channels
         self.lat = torch.zeros(self.Bp, C, h, w, dtype=torch.float32, device=dev)
-        self.lat_in = torch.zeros(self.B, C, h, w, dtype=torch.float32, device=dev) if self.cfg else self.lat
+        # decided once, here, from the model and the plan registered NOW: the launches of a captured step follow from it, so it is
+        # part of `_key` (every fact it rests on is in the plan's signature, the model or the shapes)
+        self.shared_reason = self._shared_reason(context.shape[1])
+        self.shared = self.shared_reason is None
+        if (self.cfg and not self.shared and mode == "denoise" and CFG_SHARED_PREFIX and getattr(self.unet, "x3p", False)
+                and self.shared_reason not in _said):
+            _said.add(self.shared_reason)       # a planes model that could share and does not: said once per reason
+            _log.warning("CFG step without the shared prefix: %s", self.shared_reason)
+        self.lat_in = self.lat if (self.shared or not self.cfg) else torch.zeros(self.B, C, h, w, dtype=torch.float32, device=dev)
         self.step = torch.zeros(1, dtype=torch.int32, device=dev)
         self.coef_cur = torch.zeros(4, dtype=torch.float32, device=dev)
         self.coef_table = self.temb_table = self.temb_cur = self.ctx = self.ctx_table = None
@@ -112,11 +169,20 @@ class FusedDenoiser:
             # optimisation / edit) must not change under it
             put("ctx", ctx16.clone())
 
+    def _shared_reason(self, ctx_len):
+        """None where this loop's steps run the shared prefix (`cfg_shared_prefix_reason`), else why not"""
+        facts = getattr(self.unet, "cfg_shared_facts", None)
+        if facts is None:
+            return "the UNet has no shared-prefix form"
+        return cfg_shared_prefix_reason(mode=self.mode, cfg=self.cfg, enabled=CFG_SHARED_PREFIX and type(self)._step_body is FusedDenoiser._step_body,
+                                        **facts(tuple(self.lat.shape[-2:]), ctx_len))
+
     def _key(self, context, uncond_list):
         plan = self.unet._plan
         return (id(self.unet), self.mode, self.Bp, tuple(self.lat.shape[-2:]), self.cfg, tuple(context.shape),
                 None if uncond_list is None else len(uncond_list), len(self.sched.timesteps),
-                None if plan is None else plan.signature(self.unet), getattr(self.unet, "attn_key_splits", 1))
+                None if plan is None else plan.signature(self.unet), self._shared_reason(context.shape[1]) is None,
+                getattr(self.unet, "attn_key_splits", 1))
 
     def rebind(self, context, guidance_scale, uncond_list, added_cond_kwargs=None):
         """point a captured loop at the next image: new tables, new cross-attention K/V, the new controller's plan"""
@@ -140,10 +206,14 @@ class FusedDenoiser:
         hip.select_step(self.coef_table, self.coef_cur, self.step)
         if self.ctx_table is not None:
             hip.select_step(self.ctx_table, self.ctx, self.step)
-        if self.cfg:
-            self.lat_in[: self.Bp].copy_(self.lat)
-            self.lat_in[self.Bp:].copy_(self.lat)
-        eps = self.unet(self.lat_in, encoder_hidden_states=self.ctx, temb_row=self.temb_cur)["sample"]
+        if self.cfg and self.shared:
+            # the UNet takes the Bp latents themselves: no CFG batch copy, and what both halves share is computed once
+            eps = self.unet(self.lat, encoder_hidden_states=self.ctx, temb_row=self.temb_cur, cfg_pair=True)["sample"]
+        else:
+            if self.cfg:
+                self.lat_in[: self.Bp].copy_(self.lat)
+                self.lat_in[self.Bp:].copy_(self.lat)
+            eps = self.unet(self.lat_in, encoder_hidden_states=self.ctx, temb_row=self.temb_cur)["sample"]
         if self.cfg:
             hip.cfg_ddim_step(eps[: self.Bp], eps[self.Bp:], self.lat, self.coef_cur, out=self.lat)
         else:

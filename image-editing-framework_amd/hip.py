@@ -125,6 +125,13 @@ class IefAttnBwdF32Params(Structure):
     ]
 
 
+class IefRepeatJob(Structure):
+    _fields_ = [("src", c_void_p), ("dst", c_void_p), ("bytes", c_longlong), ("blocks", c_int)]
+
+
+REPEAT_MAX_JOBS = 4   # include/ief_hip.h IEF_REPEAT_MAX_JOBS
+
+
 class IefGemmX3pParams(Structure):
     _fields_ = [
         ("A", c_void_p), ("planeA", c_longlong), ("A2", c_void_p), ("planeA2", c_longlong),
@@ -165,6 +172,8 @@ EXPORTS = [
     # ABI 4: split-operand contractions on pre-split planes (csrc/gemm_x3p.hip)
     "ief_gemm_x3p", "ief_gemm_x3p_tile_bm", "ief_gemm_x3p_tile_bn", "ief_gemm_x3p_tile_wn", "ief_x3_split_act", "ief_groupnorm_silu_x3p_ws", "ief_layernorm_x3p", "ief_groupnorm_silu_x3p_small", "ief_groupnorm_silu_reg", "ief_groupnorm_reg_fits", "ief_attn_bwd_x3", "ief_attn_bwd_delta_f32in",
     "ief_attn_flash_ws_floats",
+    # CFG step with a shared prefix: conv_in that writes its planes, the batch repeat
+    "ief_conv_in_f32act_planes", "ief_repeat_batch",
 ]
 
 
@@ -275,6 +284,8 @@ def load():
     lib.ief_gather_rows_f32.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_longlong, c_void_p]
     lib.ief_conv_in_f32act.argtypes = [c_void_p] * 4 + [c_int] * 5 + [c_void_p]
     lib.ief_conv_out_f32act.argtypes = [c_void_p] * 4 + [c_int] * 5 + [c_void_p]
+    lib.ief_conv_in_f32act_planes.argtypes = [c_void_p] * 5 + [c_longlong] + [c_int] * 5 + [c_void_p]
+    lib.ief_repeat_batch.argtypes = [POINTER(IefRepeatJob), c_int, c_void_p]
     lib.ief_image_u8.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]
     lib.ief_gemm_x3p.argtypes = [POINTER(IefGemmX3pParams), c_void_p]
     lib.ief_gemm_x3p_tile_bm.argtypes = [c_int]
@@ -1215,18 +1226,30 @@ def gather_rows(x, src):
     return out
 
 
-def conv_in(x, w, bias, out=None):
-    """latent fp32 NCHW [B,Cin,H,W] -> fp16 NHWC [B,H,W,Cout]; w fp16 [3,3,Cin,Cout] (k-major).  fp32 w: fp32 NHWC out."""
+def conv_in(x, w, bias, out=None, out_planes=False):
+    """latent fp32 NCHW [B,Cin,H,W] -> fp16 NHWC [B,H,W,Cout]; w fp16 [3,3,Cin,Cout] (k-major).  fp32 w: fp32 NHWC out.
+    out_planes (fp32 w only): the same launch also writes the result's operand planes -> (out, planes.Planes), bit for bit
+    `planes.split(out)`."""
     lib = load()
     _dev32(x, "x")
+    if out_planes and not _is32(w):
+        raise ValueError("conv_in: operand planes exist for the fp32-storage modes only")
     if _is32(w):
         B, Cin, H, Wd = x.shape
         if tuple(w.shape[:3]) != (3, 3, Cin) or not _act32(w, "w").is_contiguous():
             raise ValueError("conv_in: weight must be contiguous [3, 3, Cin, Cout]")
         if out is None:
             out = torch.empty(B, H, Wd, w.shape[3], dtype=torch.float32, device=x.device)
-        _check(lib.ief_conv_in_f32act(x.data_ptr(), w.data_ptr(), _ptr(bias), out.data_ptr(), B, Cin, H, Wd, w.shape[3],
-                                      _stream()), "ief_conv_in_f32act")
+        if out_planes:
+            from . import planes as _pl
+            op = _pl.Planes.empty(B, H, Wd, w.shape[3], device=x.device)
+            with _Timed("conv_in_f32_kernel<planes>", 2.0 * B * H * Wd * 9 * Cin * w.shape[3], 8.0 * out.numel()):
+                _check(lib.ief_conv_in_f32act_planes(x.data_ptr(), w.data_ptr(), _ptr(bias), out.data_ptr(), op.t.data_ptr(), op.plane,
+                                                     B, Cin, H, Wd, w.shape[3], _stream()), "ief_conv_in_f32act_planes")
+            return out, op
+        with _Timed("conv_in_f32_kernel", 2.0 * B * H * Wd * 9 * Cin * w.shape[3], 4.0 * out.numel()):
+            _check(lib.ief_conv_in_f32act(x.data_ptr(), w.data_ptr(), _ptr(bias), out.data_ptr(), B, Cin, H, Wd, w.shape[3],
+                                          _stream()), "ief_conv_in_f32act")
         return out
     _dev16(w, "w")
     B, Cin, H, Wd = x.shape
@@ -1238,6 +1261,33 @@ def conv_in(x, w, bias, out=None):
     _check(lib.ief_conv_in_f32(x.data_ptr(), w.data_ptr(), _ptr(bias), out.data_ptr(), B, Cin, H, Wd, Cout, _stream()),
            "ief_conv_in_f32")
     return out
+
+
+def repeat_batch(*tensors):
+    """every argument (a contiguous device tensor [Bp, ...] or a `planes.Planes` of such rows) repeated along the batch:
+    -> tensors [2 Bp, ...] with out[r] = x[r % Bp], all written by ONE launch (`ief_repeat_batch`, up to REPEAT_MAX_JOBS
+    arguments).  16-byte loads and stores: a Bp-row block whose address or size is no multiple of 16 is refused (IEF_EALIGN)."""
+    lib = load()
+    if not 1 <= len(tensors) <= REPEAT_MAX_JOBS:
+        raise ValueError(f"repeat_batch: 1 .. {REPEAT_MAX_JOBS} tensors per launch")
+    from . import planes as _pl
+    jobs = (IefRepeatJob * len(tensors))()
+    outs, nbytes = [], 0.0
+    for j, x in zip(jobs, tensors):
+        pl = isinstance(x, _pl.Planes)
+        t = x.t if pl else x
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.is_contiguous() and t.dim() >= (2 if pl else 1) and t.numel() > 0):
+            raise ValueError("repeat_batch: contiguous, non-empty device tensors [Bp, ...] (or Planes of them) expected")
+        blocks = 2 if pl else 1
+        shape = list(t.shape)
+        shape[1 if pl else 0] *= 2
+        o = torch.empty(shape, dtype=t.dtype, device=t.device)
+        j.src, j.dst, j.bytes, j.blocks = t.data_ptr(), o.data_ptr(), t.numel() * t.element_size() // blocks, blocks
+        nbytes += 3.0 * t.numel() * t.element_size()
+        outs.append(_pl.Planes(o) if pl else o)
+    with _Timed("repeat_batch_kernel", 0.0, nbytes):
+        _check(lib.ief_repeat_batch(jobs, len(tensors), _stream()), "ief_repeat_batch")
+    return outs[0] if len(outs) == 1 else tuple(outs)
 
 
 def conv_out(x, w, bias, out=None):
@@ -1396,13 +1446,17 @@ GN3_F32 = os.environ.get("IEF_GN3_F32", "1") == "1"          # 0: the one-launch
 FLASH_F32 = os.environ.get("IEF_FLASH_F32", "1") == "1"      # 0: always materialise the fp32 maps (A/B runs)
 
 
-def _attn_flash_f32(q, k, v, heads, scale, q_src=None, k_src=None, v_src=None, out=None, out_planes=False, lse=None, key_splits=1):
+def _attn_flash_f32(q, k, v, heads, scale, q_src=None, k_src=None, v_src=None, out=None, out_planes=False, lse=None, key_splits=1,
+                    batch=None):
     """fused fp32 attention (`ief_attn_flash_f32`): no map is written; None when the head dim has no instantiation.
+    batch: the launch's batch rows where q has fewer of them and q_src (checked by the caller) selects among them
     out_planes (split-operand mode only): the result leaves as operand planes for to_out's GEMM (`planes.Planes`);
     lse (split-operand mode only): fp32 [B, heads, N] receiving the row log-sum-exp (log2 units) for `ief_attn_bwd_x3`"""
     lib = load()
     B, N, C = q.shape
     L, d = k.shape[1], C // heads
+    if batch is not None:
+        B = int(batch)
     if not FLASH_F32 or d not in (32, 40, 64, 80, 160):
         return None
     p = IefAttnF32Params()
@@ -1571,15 +1625,56 @@ def map_split_scale(coef_bound: float) -> float:
     return s
 
 
-def _attn_cross_p2p_x3(q, k, v, heads, scale, edit_src, edit_slot, mt32, coef, out=None, out_planes=False, coef_bound=1.0):
+class BatchRows:
+    """a batch-row indirection list built ON THE HOST and checked there: `dev` int32 [B] on the device, every entry a row of an
+    operand with `rows` batch rows.  The kernels cannot check device lists; the lists a control plan switches per step live on the
+    device only, this one is fixed for the life of its loop, so the check happens where it is built."""
+    __slots__ = ("dev", "rows", "n")
+
+    def __init__(self, entries, rows, device):
+        entries = [int(e) for e in entries]
+        if not entries or any(e < 0 or e >= rows for e in entries):
+            raise ValueError(f"batch-row list {entries}: every entry must be a row of an operand with {rows} batch rows")
+        self.rows, self.n = int(rows), len(entries)
+        self.dev = torch.tensor(entries, dtype=torch.int32, device=device)
+
+
+_cfg_rows = {}
+
+
+def cfg_q_rows(Bp, device):
+    """q_src of a launch over a CFG batch of 2 Bp rows whose halves share ONE Bp-row query projection: [0..Bp-1, 0..Bp-1].
+    One list per (Bp, device), made at the first eager use (a captured graph keeps reading it; none is made while capturing)."""
+    key = (int(Bp), str(torch.device(device)))
+    r = _cfg_rows.get(key)
+    if r is None:
+        if _capturing():
+            raise RuntimeError("cfg_q_rows: run one eager forward of this batch before capturing")
+        r = _cfg_rows[key] = BatchRows(list(range(Bp)) * 2, Bp, device)
+    return r
+
+
+def _attn_cross_p2p_x3(q, k, v, heads, scale, edit_src, edit_slot, mt32, coef, out=None, out_planes=False, coef_bound=1.0,
+                       q_src=None):
     """`ief_attn_cross_p2p_f32`: the edited cross-attention layer of the f16x3 mode in one launch (maps stay in registers).
-    coef_bound: max_w (|c1| + |c2|) over the plan's coefficient tables (sizes the split of the edited maps)"""
+    coef_bound: max_w (|c1| + |c2|) over the plan's coefficient tables (sizes the split of the edited maps).
+    edit_src None: plain attention by the same kernel.  q_src (`BatchRows`): the launch's batch is k's; row b reads q[q_src[b]]."""
     lib = load()
     B, N, C = q.shape
     L, d = k.shape[1], C // heads
-    _dev32(mt32, "mt32"), _dev32(coef, "coef")
-    if tuple(mt32.shape[-2:]) != (96, 96) or coef.shape[-1] != 96 or not mt32.is_contiguous() or not coef.is_contiguous():
-        raise ValueError("attn_cross_p2p: mt must be contiguous [slots,96,96] fp32, coef [slots,2,96] fp32")
+    if q_src is not None:
+        if not isinstance(q_src, BatchRows) or q_src.rows != q.shape[0] or q_src.n != k.shape[0]:
+            raise ValueError("attn_cross_p2p: q_src must be a hip.BatchRows with one entry per batch row of k / v, checked against "
+                             "the batch rows of q")
+        B = k.shape[0]
+    if k.shape[0] != B or v.shape[0] != B:
+        raise ValueError("attn_cross_p2p: q, k, v must have one batch (q may have another one with q_src)")
+    if edit_src is not None:
+        _dev32(mt32, "mt32"), _dev32(coef, "coef")
+        if tuple(mt32.shape[-2:]) != (96, 96) or coef.shape[-1] != 96 or not mt32.is_contiguous() or not coef.is_contiguous():
+            raise ValueError("attn_cross_p2p: mt must be contiguous [slots,96,96] fp32, coef [slots,2,96] fp32")
+        if _devi32(edit_src, "edit_src").numel() != B or _devi32(edit_slot, "edit_slot").numel() != B:
+            raise ValueError("attn_cross_p2p: edit_src / edit_slot need one entry per batch row")
     p = IefAttnF32Params()
     p.Q, p.K, p.V = _act32(q, "q").data_ptr(), _act32(k, "k").data_ptr(), _act32(v, "v").data_ptr()
     op = None
@@ -1597,18 +1692,32 @@ def _attn_cross_p2p_x3(q, k, v, heads, scale, edit_src, edit_slot, mt32, coef, o
     p.sVb, _, p.ldv = _batched32(p, v, heads, d, "v")
     p.p_scale = map_split_scale(coef_bound)
     p.x3 = 1
-    nedit = 2.0 * B * heads * N * 96 * 96
+    if q_src is not None:
+        p.q_src = q_src.dev.data_ptr()
+    nedit = 2.0 * B * heads * N * 96 * 96 if edit_src is not None else 0.0
     with _Timed(f"attn_cross_p2p_x3_kernel<{d}>", 4.0 * B * heads * N * L * d + nedit, 4.0 * B * heads * d * (2 * N + 2 * L)):
-        _check(lib.ief_attn_cross_p2p_f32(byref(p), _devi32(edit_src, "edit_src").data_ptr(), _devi32(edit_slot, "edit_slot").data_ptr(),
-                                          mt32.data_ptr(), coef.data_ptr(), _stream()), "ief_attn_cross_p2p_f32")
+        _check(lib.ief_attn_cross_p2p_f32(byref(p), _ptr(edit_src), _ptr(edit_slot), _ptr(mt32) if edit_src is not None else None,
+                                          _ptr(coef) if edit_src is not None else None, _stream()), "ief_attn_cross_p2p_f32")
     return op if out_planes else out
 
 
 def attn_cross_p2p(q, k, v, heads, scale, edit_src=None, edit_slot=None, mt=None, coef=None, out=None, out_planes=False,
-                   coef_bound=1.0):
+                   coef_bound=1.0, q_src=None):
     """Cross-attention (<= 96 keys) with the fused Prompt-to-Prompt map edit (see include/ief_hip.h).
     fp32 operands: materialised maps, `mt` must then be the fp32 table.  out_planes (split-operand mode): the result as operand
-    planes for to_out's GEMM; coef_bound: max (|c1| + |c2|) of the plan (sizes the split of the edited maps)."""
+    planes for to_out's GEMM; coef_bound: max (|c1| + |c2|) of the plan (sizes the split of the edited maps).
+    q_src (`BatchRows`, split-operand mode, L <= 96 only): k / v carry the launch's batch rows, row b reads q[q_src[b]] -- the edited
+    layer on `attn_cross_p2p_x3_kernel`, the unedited one on the flash kernel it takes anyway; no other route (ValueError)."""
+    if q_src is not None:
+        if not (_is32(q) and _F32_CONTRACT == "x3" and k.shape[1] <= 96 and q.shape[2] // heads in (40, 64, 80, 160)):
+            raise ValueError("attn_cross_p2p: q_src exists on the fused split-operand kernel only (f16x3, <= 96 keys, head dim 40 / "
+                             "64 / 80 / 160)")
+        if not isinstance(q_src, BatchRows) or q_src.rows != q.shape[0] or q_src.n != k.shape[0] or v.shape[0] != k.shape[0]:
+            raise ValueError("attn_cross_p2p: q_src must be a hip.BatchRows with one entry per batch row of k / v, checked against "
+                             "the batch rows of q")
+        if edit_src is None and FLASH_F32:      # the launch the unedited layer takes without q_src, hence its bits
+            return _attn_flash_f32(q, k, v, heads, scale, q_src=q_src.dev, out=out, out_planes=out_planes, batch=k.shape[0])
+        return _attn_cross_p2p_x3(q, k, v, heads, scale, edit_src, edit_slot, mt, coef, out, out_planes, coef_bound, q_src=q_src)
     if _is32(q):
         if edit_src is None:
             o = _attn_flash_f32(q, k, v, heads, scale, out=out, out_planes=out_planes)

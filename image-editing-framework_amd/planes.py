@@ -91,7 +91,8 @@ def split(x, out=None, scale=ACT_SCALE):
     if out is None:
         out = Planes.empty(*x.shape, device=x.device)
     _, _, ldp = out.rows_ld("out")
-    _check(lib.ief_x3_split_act(x.data_ptr(), out.t.data_ptr(), out.plane, rows, C, ldx, ldp, float(scale), _stream()), "ief_x3_split_act")
+    with _Timed("x3_split_act_kernel", 0.0, 8.0 * rows * C):
+        _check(lib.ief_x3_split_act(x.data_ptr(), out.t.data_ptr(), out.plane, rows, C, ldx, ldp, float(scale), _stream()), "ief_x3_split_act")
     return out
 
 

@@ -273,13 +273,20 @@ class Attention(nn.Module):
         w = self.w_qkv if self.w_qkv is not None else self.to_q.weight
         self.ln3 = planes.FoldedLN(w, None, norm.weight, norm.bias, norm.eps)
 
-    def forward_x3p(self, xp, ctx, residual, ln_stats=None, want_stats=False):
+    def forward_x3p(self, xp, ctx, residual, ln_stats=None, want_stats=False, cfg_rows=None):
         """split-operand mode on operand planes (csrc/gemm_x3p.hip): xp = planes of the LayerNorm'ed input (written by the
         LayerNorm launch) -- or, with ln_stats (planes.RowStats of its rows), planes of the RAW residual stream: the LayerNorm is
         then folded into the input projection.  The attention kernel writes the planes to_out's GEMM stages by LDS-DMA; returns
         fp32 (the residual stream); want_stats: (fp32, Planes, RowStats) of the output for the next folded LayerNorm.  Same
-        dataflow as `forward` (`/root/reference/p2p/model/register.py:11-64`)."""
+        dataflow as `forward` (`/root/reference/p2p/model/register.py:11-64`).
+        cfg_rows (`hip.BatchRows`, the shared prefix of a CFG step): xp holds the Bp rows both halves of the CFG batch share.  A
+        self-attention module then runs at Bp rows (its plan, asked about the FULL batch, must leave it alone); a cross-attention
+        module projects q once at Bp rows and attends at 2 Bp rows -- ctx, residual and the result have 2 Bp rows."""
         B, N, C = xp.shape
+        if cfg_rows is not None:
+            if cfg_rows.rows != B:
+                raise ValueError("forward_x3p: cfg_rows was built for another batch")
+            B = cfg_rows.n           # what the control plan and the cross-attention launch count
         self.last_tokens = N
         plan = self._plan
         w_in, b_in, ln = (self.w_qkv if ctx is None else self.to_q.weight), None, None
@@ -289,6 +296,10 @@ class Attention(nn.Module):
             qs = ks = vs = None
             if plan is not None:
                 qs, ks, vs = plan.self_sources(B, N, self)
+            if cfg_rows is not None and (qs is not None or ks is not None or vs is not None
+                                         or (plan is not None and plan.mask_launches(B, N, self) is not None)):
+                raise RuntimeError(f"{self.layer_name}: the control plan acts on a self-attention that runs in the shared prefix of a "
+                                   "CFG step (ControlPlan.controls_first_self must say so)")
             if planes.FLASH_PLANES and self.dim_head in planes.FLASH_PLANES_DIMS:
                 # the q|k|v GEMM writes planes only; the attention kernel stages K / V tiles by LDS-DMA and splits nothing
                 qkv = planes.gemm(xp, w_in, bias=b_in, ln=ln, out=False, out_planes=True)
@@ -316,7 +327,7 @@ class Attention(nn.Module):
             args = plan.cross_edit(B, self) if plan is not None else {}
             if self.map_out is not None:
                 hip.attn_probs(q, kv[..., :C], self.heads, self.scale, out=self.map_out)
-            o = hip.attn_cross_p2p(q, kv[..., :C], kv[..., C:], self.heads, self.scale, out_planes=True, **args)
+            o = hip.attn_cross_p2p(q, kv[..., :C], kv[..., C:], self.heads, self.scale, out_planes=True, q_src=cfg_rows, **args)
         if plan is not None:
             plan.layer_done(self)
         lin = self.to_out[0]
@@ -434,17 +445,31 @@ class BasicTransformerBlock(nn.Module):
             return planes.gemm(g, lin.weight, bias=lin.bias, residual=h, out=True, out_planes=True, row_stats=True)
         return planes.gemm(g, lin.weight, bias=lin.bias, residual=h)
 
-    def forward_x3p(self, h, ctx, last):
+    def forward_x3p(self, h, ctx, last, cfg_rows=None, carry=()):
         """split-operand mode on operand planes: every LayerNorm writes the planes its GEMM consumes, FeedForward.net[0]
-        writes the GEGLU product as planes; last: the block's output is read by proj_out only -> planes only"""
-        h = self._attend_x3p(self.attn1, self.norm1, h, None)
-        h = self._attend_x3p(self.attn2, self.norm2, h, ctx)
+        writes the GEGLU product as planes; last: the block's output is read by proj_out only -> planes only.
+        cfg_rows (`hip.BatchRows`; both attention modules native): h holds the Bp rows the halves of a CFG batch share.  The
+        self half -- LayerNorm 1, attn1, LayerNorm 2, attn2's query projection -- runs on them; ONE repeat launch then makes the 2 Bp
+        rows of attn1's output (the residual of attn2's to_out) and of every tensor in `carry` (what the caller's later launches
+        read at 2 Bp rows); the cross-attention and everything after it run at 2 Bp rows.  Returns (out, repeated carry)."""
+        if cfg_rows is not None:
+            h = self.attn1.forward_x3p(planes.layernorm(h, self.norm1.weight, self.norm1.bias, self.norm1.eps), None, residual=h,
+                                       cfg_rows=cfg_rows)
+            n2 = planes.layernorm(h, self.norm2.weight, self.norm2.bias, self.norm2.eps)
+            rep = hip.repeat_batch(h, *carry)
+            h, carry = (rep[0], tuple(rep[1:])) if carry else (rep, ())
+            h = self.attn2.forward_x3p(n2, ctx, residual=h, cfg_rows=cfg_rows)
+        else:
+            h = self._attend_x3p(self.attn1, self.norm1, h, None)
+            h = self._attend_x3p(self.attn2, self.norm2, h, ctx)
         n3 = planes.layernorm(h, self.norm3.weight, self.norm3.bias, self.norm3.eps)
         f0, lin = self.ff.net[0].proj, self.ff.net[2]
         g = planes.gemm(n3, f0.weight, bias=f0.bias, geglu=True, out=False, out_planes=True)
         if last:
-            return planes.gemm(g, lin.weight, bias=lin.bias, residual=h, out=False, out_planes=True)
-        return planes.gemm(g, lin.weight, bias=lin.bias, residual=h)
+            r = planes.gemm(g, lin.weight, bias=lin.bias, residual=h, out=False, out_planes=True)
+        else:
+            r = planes.gemm(g, lin.weight, bias=lin.bias, residual=h)
+        return (r, carry) if cfg_rows is not None else r
 
 
 class Transformer2DModel(nn.Module):
@@ -478,15 +503,28 @@ class Transformer2DModel(nn.Module):
         return self.proj_out(h.reshape(B, H, W, C), residual=x, col_stats=col_stats)
 
 
-    def forward_x3p(self, x, encoder_hidden_states=None, want_planes=False):
+    def forward_x3p(self, x, encoder_hidden_states=None, want_planes=False, cfg_rows=None, carry=()):
         """x fp32 NHWC -> (out fp32, Planes | None): GroupNorm writes proj_in's operand planes, the last block's FeedForward
         writes proj_out's; proj_out's epilogue adds the fp32 residual and (want_planes) also emits the planes of the result for
-        a consumer that reads the raw stream (a shortcut source, Downsample2D / Upsample2D, a skip connection)"""
+        a consumer that reads the raw stream (a shortcut source, Downsample2D / Upsample2D, a skip connection).
+        cfg_rows (`hip.BatchRows`): x holds the Bp rows the halves of a CFG batch share -- GroupNorm, proj_in and the self half of
+        the first block run on them (`BasicTransformerBlock.forward_x3p`); the context and the result have 2 Bp rows; x (the
+        residual of proj_out) and the tensors in `carry` are repeated by the block's one repeat launch.  Returns
+        (out, Planes | None, repeated carry)."""
         B, H, W, C = x.shape
         n = self.norm
         hn = planes.groupnorm(x, n.weight, n.bias, n.num_groups, n.eps, silu=False)
         last = len(self.transformer_blocks) - 1
-        if all(blk.foldable_x3p() for blk in self.transformer_blocks):
+        if cfg_rows is not None:
+            h = planes.gemm(hn.reshape(B, H * W, C), self.proj_in.weight, bias=self.proj_in.bias)
+            for k, blk in enumerate(self.transformer_blocks):
+                if k == 0:
+                    h, rep = blk.forward_x3p(h, encoder_hidden_states, last=(k == last), cfg_rows=cfg_rows, carry=(x,) + tuple(carry))
+                    x, carry = rep[0], rep[1:]
+                    B = x.shape[0]
+                else:
+                    h = blk.forward_x3p(h, encoder_hidden_states, last=(k == last))
+        elif all(blk.foldable_x3p() for blk in self.transformer_blocks):
             h, hp, st = planes.gemm(hn.reshape(B, H * W, C), self.proj_in.weight, bias=self.proj_in.bias, out=True, out_planes=True,
                                     row_stats=True)
             for k, blk in enumerate(self.transformer_blocks):
@@ -502,8 +540,10 @@ class Transformer2DModel(nn.Module):
         r = planes.gemm(h, self.proj_out.weight, bias=self.proj_out.bias, residual=x.reshape(B, H * W, C), out=True,
                         out_planes=want_planes)
         if want_planes:
-            return r[0].reshape(B, H, W, C), r[1].reshape(B, H, W, C)
-        return r.reshape(B, H, W, C), None
+            r = r[0].reshape(B, H, W, C), r[1].reshape(B, H, W, C)
+        else:
+            r = r.reshape(B, H, W, C), None
+        return r + (tuple(carry),) if cfg_rows is not None else r
 
 
 # ------------------------------------------------------------------------------------- resnet
@@ -819,10 +859,26 @@ class UNet2DConditionModel(nn.Module):
             return self._time_rows(timesteps_f32, aug)
 
     def forward(self, sample, timestep=None, encoder_hidden_states=None, cross_attention_kwargs=None,
-                added_cond_kwargs=None, return_dict=True, temb_row=None, taps=None, **kw):
+                added_cond_kwargs=None, return_dict=True, temb_row=None, taps=None, cfg_pair=False, **kw):
+        """cfg_pair: `sample` [Bp, ...] stands for the classifier-free-guidance batch cat([sample, sample]) of 2 Bp rows
+        (`/root/reference/p2p/model/sd_utils.py:72`); context and result have 2 Bp rows.  Where `cfg_shared_facts` allows it
+        (`denoise.cfg_shared_prefix_reason`) everything in front of the first cross-attention runs once, at Bp rows; elsewhere the
+        batch is built here and the forward is the usual one."""
         with hip.f32_contraction(self.contract):
             return self._forward(sample, timestep, encoder_hidden_states, cross_attention_kwargs, added_cond_kwargs,
-                                 return_dict, temb_row, taps, **kw)
+                                 return_dict, temb_row, taps, cfg_pair=cfg_pair, **kw)
+
+    def cfg_shared_facts(self, latent_hw, ctx_len=77):
+        """what `denoise.cfg_shared_prefix_reason` needs to know about this model and its registered control plan (host only)"""
+        blk = self.down_blocks[0]
+        att = [m for m in blk.modules() if isinstance(m, Attention)]
+        cross = bool(blk.has_cross_attention) and len(blk.attentions) > 0
+        plan = self._plan
+        return dict(x3p=bool(self.x3p), aug=bool(self.cfg.addition_embed), first_block_cross=cross,
+                    native=all(m.is_native() for m in att),
+                    fused_cross=cross and att[1].dim_head in (40, 64, 80, 160) and int(ctx_len) <= 96 and hip.FLASH_F32 and hip.X3_FUSE_CROSS,
+                    ln_folded=bool(planes.LN_FOLD),
+                    plan_on_first_self=plan is not None and plan.controls_first_self(self, int(latent_hw[0]) * int(latent_hw[1])))
 
     def _aug_embedding(self, added_cond_kwargs):
         """SDXL: fp16 [B, time_embed_dim] = add_embedding(cat([text_embeds, sinusoids of the 6 time ids])) — constant over
@@ -857,7 +913,7 @@ class UNet2DConditionModel(nn.Module):
 
     # ------------------------------------------------------------------ forward
     def _forward(self, sample, timestep=None, encoder_hidden_states=None, cross_attention_kwargs=None,
-                 added_cond_kwargs=None, return_dict=True, temb_row=None, taps=None, **kw):
+                 added_cond_kwargs=None, return_dict=True, temb_row=None, taps=None, cfg_pair=False, **kw):
         """sample fp32/fp16 NCHW [B,4,H,W]; timestep scalar / 0-d tensor; ctx [B,77,Cc] -> eps fp32 NCHW.
 
         `temb_row` (fp32 [1, width]) short-circuits the time embedding for the captured-graph loop."""
@@ -865,8 +921,15 @@ class UNet2DConditionModel(nn.Module):
             raise RuntimeError("UNet input must be a device tensor (no CPU path)")
         x = sample if sample.dtype == torch.float32 else sample.float()
         x = x.contiguous()
-        B = x.shape[0]
         ctx = encoder_hidden_states
+        if cfg_pair:
+            from .denoise import cfg_shared_prefix_reason
+            if ctx.shape[0] != 2 * x.shape[0]:
+                raise ValueError(f"cfg_pair: {x.shape[0]} latents stand for {2 * x.shape[0]} batch rows, the context has {ctx.shape[0]}")
+            if cfg_shared_prefix_reason(mode="denoise", cfg=True, taps=taps is not None,
+                                        **self.cfg_shared_facts(x.shape[-2:], ctx.shape[1])) is not None:
+                x, cfg_pair = torch.cat([x, x]), False
+        B = x.shape[0] * (2 if cfg_pair else 1)      # the batch the context, the control plan and the result have
         if ctx.dtype != self.dtype:
             ctx = self._ctx_f16(ctx)
         if temb_row is None:
@@ -891,7 +954,9 @@ class UNet2DConditionModel(nn.Module):
                 taps[name] = v.float().permute(0, 3, 1, 2).cpu()
 
         if self.x3p:
-            eps = self._trunk_x3p(x, trow, ctx, tap)
+            if cfg_pair and temb_row.shape[0] != 1:
+                raise ValueError("cfg_pair: one time-embedding row for the whole batch expected")
+            eps = self._trunk_x3p(x, trow, ctx, tap, cfg_pair=cfg_pair)
             if per_step_kv:
                 for m in cross:
                     m._kv_view = None
@@ -937,20 +1002,26 @@ class UNet2DConditionModel(nn.Module):
             return (eps,)
         return UNetOutput(sample=eps)
 
-    def _trunk_x3p(self, x, trow, ctx, tap):
+    def _trunk_x3p(self, x, trow, ctx, tap, cfg_pair=False):
         """conv_in .. conv_out of the split-operand mode on operand planes.  `hp` travels beside `h`: the planes of h, emitted
         by the launch that produced h WHERE A CONSUMER READS THE RAW STREAM through a GEMM / convolution — a skip connection or
         block input feeding a fused 1x1 shortcut, Downsample2D / Upsample2D (no normalisation in front of them) — else None.
-        Everything a normalisation feeds gets its planes from that normalisation's launch."""
-        h = hip.conv_in(x, self.conv_in.weight, self.conv_in.bias)
-        hp = planes.split(h)
+        Everything a normalisation feeds gets its planes from that normalisation's launch.
+        cfg_pair: x holds the Bp latents both halves of a CFG batch share (`forward`); conv_in, the first resnet and the first
+        transformer up to its cross-attention's query projection run on them, the rest at the 2 Bp rows of ctx."""
+        h, hp = hip.conv_in(x, self.conv_in.weight, self.conv_in.bias, out_planes=True)      # conv_in writes its own planes
         tap("conv_in", h)
         skips = [(h, hp)]
         for bi, blk in enumerate(self.down_blocks):
             for j, res in enumerate(blk.resnets):
                 attn = blk.has_cross_attention
                 h, hp = res.forward_x3p(h, hp, trow(res), want_planes=not attn)       # every down-path output is a skip connection
-                if attn:
+                if attn and cfg_pair and bi == 0 and j == 0:
+                    # conv_in's output is a skip connection (up_blocks[-1] reads it at 2 Bp rows): it rides the one repeat launch
+                    h, hp, skip0 = blk.attentions[0].forward_x3p(h, ctx, want_planes=True, cfg_rows=hip.cfg_q_rows(x.shape[0], x.device),
+                                                                 carry=skips[0])
+                    skips[0] = skip0
+                elif attn:
                     h, hp = blk.attentions[j].forward_x3p(h, ctx, want_planes=True)
                 skips.append((h, hp))
             if blk.downsamplers is not None:

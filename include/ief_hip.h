@@ -344,8 +344,10 @@ int ief_softmax_rows_f32(float* x, long long rows, int L, void* stream);
 int ief_p2p_cross_edit_f32(float* P, const int* edit_src, const int* edit_slot, const float* MT, const float* coef, int B,
                            int heads, int N, int L, void* stream);
 /* the four launches above (scores, softmax, edit, apply) as ONE: cross-attention over L <= 96 keys with the map edit applied to
- * maps that stay in registers; split-operand arithmetic (p->x3 is not consulted), d in {40, 64, 80, 160}, no batch-row indirection
- * (q_src / k_src / v_src NULL); edit_src NULL: plain attention (csrc/cross_p2p_x3.hip) */
+ * maps that stay in registers; split-operand arithmetic (p->x3 is not consulted), d in {40, 64, 80, 160}; edit_src NULL: plain
+ * attention (csrc/cross_p2p_x3.hip).  q_src (B entries, or NULL): the maps of row b read Q from batch row q_src[b], those of its
+ * source row from q_src[edit_src[b]] -- Q may then have fewer batch rows than the launch (a CFG batch whose halves share one query
+ * projection); K and V stay on rows b / edit_src[b]: k_src / v_src must be NULL (IEF_EINVAL).  The caller checks the entries. */
 int ief_attn_cross_p2p_f32(const IefAttnF32Params* p, const int* edit_src, const int* edit_slot, const float* MT, const float* coef,
                            void* stream);
 int ief_groupnorm_silu_f32(const float* x, const float* x2, int C1, int C2, float* out, const float* gamma, const float* beta,
@@ -395,6 +397,18 @@ int ief_conv_in_f32act(const float* x, const float* w, const float* bias, float*
                        void* stream);
 int ief_conv_out_f32act(const float* x, const float* w, const float* bias, float* out, int B, int C, int H, int Wd, int Cout,
                         void* stream);
+/* ief_conv_in_f32act that ALSO writes the operand planes of its result in the same launch (the split of the stored fp32 value, bit
+ * for bit what ief_x3_split_act makes of it at scale 1): outp hi plane [B][H][W][Cout] fp16 (8-byte aligned), lo plane `plane`
+ * elements further (plane % 4 == 0).  The fp32 output has the bits of ief_conv_in_f32act. */
+int ief_conv_in_f32act_planes(const float* x, const float* w, const float* bias, float* out, ief_half* outp, long long plane, int B,
+                              int Cin, int H, int Wd, int Cout, void* stream);
+/* batch repeat, dst[r] = src[r % Bp] for r in [0, 2 Bp): up to IEF_REPEAT_MAX_JOBS tensors in ONE launch.  A job is `blocks`
+ * blocks of `bytes` contiguous bytes each (`bytes` = the Bp rows of a tensor; operand planes [2][Bp]...: blocks = 2): block k is
+ * read at src + k bytes and written at dst + 2 k bytes and again `bytes` further.  src / dst / bytes not multiples of 16:
+ * IEF_EALIGN, nothing launched.  src and dst must not overlap. */
+#define IEF_REPEAT_MAX_JOBS 4
+typedef struct IefRepeatJob { const void* src; void* dst; long long bytes; int blocks; } IefRepeatJob;
+int ief_repeat_batch(const IefRepeatJob* jobs, int njobs, void* stream);
 /* uint8 image epilogue of latent2image (/root/reference/p2p/model/sd_utils.py:85-88): fp32 NCHW in [-1, 1] -> uint8 NHWC,
  * (x / 2 + 0.5).clamp(0, 1) * 255 truncated */
 int ief_image_u8(const float* x, unsigned char* out, int B, int C, int H, int Wd, void* stream);
