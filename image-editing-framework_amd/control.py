@@ -20,6 +20,14 @@ the same effect is expressed as small device tables, so no map is ever written t
       to its surviving keys is softmax-invariant): the mutual launch as above, then two launches over gathered row lists
       that overwrite the target rows -- int32 lists fg_keys / bg_keys / fg_queries / bg_queries per token count and a
       per-step gate table (1 in the controlled steps) that switches those launches inside a captured graph
+  MasaCtrl with masks from cross-attention (/root/reference/masactrl/model/attention_control.py:192-330), same batch: the masks
+      of a controlled layer are the mean of the head-mean 16 x 16 cross-attention maps the step has computed SO FAR, summed over
+      prompt tokens, normalised per row, resized and thresholded -- data made on the device per step and layer, so no list
+      length can be a launch argument.  Every 256-token cross-attention module writes its two token-mass rows into its slot
+      of a [K, 2, 256] buffer (`ief_cross_token_mass_f32`: rows c_src / c_tgt, token multiplicity vectors), a controlled layer
+      with c >= 1 earlier slots turns the first c slots into packed class bits (`ief_masa_auto_classes`) and ONE class-masked
+      launch over all source keys overwrites the two target rows; the per-step gate switches both off in uncontrolled steps.
+      c is a property of the layer's place in the execution order (static); thres, the multiplicities and the gate are data
   Plug-and-Play injection (/root/reference/pnp/model/register.py:27-90,100-182), batch = 4 blocks of s rows
       [uncond_src, uncond_tgt, cond_src, cond_tgt]: during the first qk_steps timesteps the self-attention of the chosen
       decoder layers computes rows of blocks 1 and 3 with the Q and K of block 2 (:45-52), and during the first
@@ -74,13 +82,17 @@ class StepCounter:
 
 
 class ControlPlan:
-    """kind: 'empty' | 'p2p' | 'masactrl' | 'masactrl_mask' | 'pnp'"""
+    """kind: 'empty' | 'p2p' | 'masactrl' | 'masactrl_mask' | 'masactrl_mask_auto' | 'pnp'"""
+    MASA_KINDS = ("masactrl", "masactrl_mask", "masactrl_mask_auto")
+    GATED_KINDS = ("masactrl_mask", "masactrl_mask_auto")
+    MAP_TOKENS, CTX_TOKENS = 256, 77
 
     def __init__(self, controller, kind: str, device, num_prompts: int = 1, num_steps: int = 0,
                  mt: Optional[torch.Tensor] = None, coef_table: Optional[torch.Tensor] = None,
                  self_window=(0, 0), self_max_tokens: int = 256, masa_steps=(), masa_layers=(),
                  pnp_layers=(), pnp_qk_steps: int = 0, pnp_conv_steps: int = 0, cond_only: bool = False,
-                 mask_s: Optional[torch.Tensor] = None, mask_t: Optional[torch.Tensor] = None, mask_tokens=()):
+                 mask_s: Optional[torch.Tensor] = None, mask_t: Optional[torch.Tensor] = None, mask_tokens=(),
+                 auto_slots=None, auto_layers=None, auto_thres: float = 0.1, auto_ref=(), auto_cur=()):
         """cond_only: the UNet batch holds ONLY the conditional rows [cond_src, cond_tgt...] — the half a controller acts
         on (`attention_base.py:20-22`) — as on the conditional rank of a 2-GPU CFG split (`denoise.CfgSplitDenoiser`) and
         in the reference's LOW_RESOURCE protocol (:18-19)"""
@@ -140,13 +152,21 @@ class ControlPlan:
         self._mask_lists = {}                      # N -> (fg_keys, bg_keys, fg_queries, bg_queries)
         self._gate = None                          # (table int32 [steps, 1], cur int32 [1])
         self._mask_rows = {}                       # B -> (target rows, their halves' source rows)
+        # masactrl_mask_auto: {exec index of a 256-token cross-attention module: its slot}, {exec index of a controlled
+        # self-attention module: (c = slots written before it in a forward, its token count at the configured sample size)}
+        self.auto_slots = dict(auto_slots or {})
+        self.auto_layers = dict(auto_layers or {})
+        self.auto_thres = float(auto_thres)
+        self.auto_ref, self.auto_cur = [int(i) for i in auto_ref], [int(i) for i in auto_cur]
+        self._auto = None                          # (slots fp32 [K, 2, 256], weights fp32 [2, 77], thres fp32 [1])
+        self._auto_cls = {}                        # (exec index, N) -> (k_cls, q_cls) int32 [N / 32]
         self.pnp_layers = set(pnp_layers)          # id() of the Attention modules whose Q/K are injected
         self.pnp_qk_steps, self.pnp_conv_steps = int(pnp_qk_steps), int(pnp_conv_steps)
         self._pnp = {}                             # B -> (qk_table, qk_cur, conv_table, conv_cur)
 
     def prepare(self, B: int):
         """allocate per-batch device tables OUTSIDE any graph capture"""
-        if self.kind == "masactrl_mask":
+        if self.kind in self.GATED_KINDS:
             if B != 4:
                 raise RuntimeError(f"mask-guided MasaCtrl acts on the UNet batch [u_src, u_tgt, c_src, c_tgt]; got batch {B}")
             n = (max(self.masa_steps) + 2) if self.masa_steps else 1
@@ -161,7 +181,16 @@ class ControlPlan:
                                       torch.tensor([0, half], dtype=torch.int32, device=self.device))
             for N in self.mask_tokens:
                 self.mask_lists(N)
-        if self.kind in ("masactrl", "masactrl_mask") and B not in self._masa:
+            if self.kind == "masactrl_mask_auto":
+                if self._auto is None:
+                    K = max(len(self.auto_slots), 1)
+                    self._auto = (torch.zeros(K, 2, self.MAP_TOKENS, dtype=torch.float32, device=self.device),
+                                  self.auto_weights().to(self.device),
+                                  torch.tensor([self.auto_thres], dtype=torch.float32, device=self.device))
+                for ei, (c, N) in self.auto_layers.items():
+                    if c >= 1:
+                        self._class_words(ei, N)
+        if self.kind in self.MASA_KINDS and B not in self._masa:
             n = (max(self.masa_steps) + 2) if self.masa_steps else 1
             self.num_steps = max(self.num_steps, n - 1)
             ident = torch.arange(B, dtype=torch.int32)
@@ -232,6 +261,70 @@ class ControlPlan:
         tgt, src = self._mask_rows[B]
         return tgt, src, self._gate[1], [(q, k) for q, k in ((fq, fk), (bq, bk)) if q.numel() > 0]
 
+    # ------------------------------------------------------------------ masks from cross-attention ('masactrl_mask_auto')
+    def auto_weights(self):
+        """fp32 [2, 77]: how often each prompt token is listed in ref_token_idx (row 0) / cur_token_idx (row 1)"""
+        w = torch.zeros(2, self.CTX_TOKENS, dtype=torch.float32)
+        for r, idx in enumerate((self.auto_ref, self.auto_cur)):
+            for i in idx:
+                w[r, i] += 1
+        return w
+
+    def _class_words(self, ei: int, N: int):
+        """(k_cls, q_cls) of the controlled layer with execution index ei at N tokens; allocated on first use, which must lie
+        outside any graph capture (prepare allocates those of the configured sample size, a muted warm-up forward the rest)"""
+        key = (ei, N)
+        if key not in self._auto_cls:
+            if self.captured:
+                raise RuntimeError(f"ControlPlan.prepare(B) must allocate the class words of layer {ei // 2} before graph capture")
+            if N % 32 or int(N ** 0.5) ** 2 != N:
+                raise RuntimeError(f"masactrl_mask_auto: a controlled layer of {N} tokens (square grids of a multiple of 32 only)")
+            self._auto_cls[key] = (torch.zeros(N // 32, dtype=torch.int32, device=self.device),
+                                   torch.zeros(N // 32, dtype=torch.int32, device=self.device))
+        return self._auto_cls[key]
+
+    def cross_mass(self, B: int, N: int, attn, q, k):
+        """under 'masactrl_mask_auto' a cross-attention module with 256 queries writes its slot: the head-mean map of row c_src
+        summed over the reference tokens, that of row c_tgt over the current tokens (q fp32 [B, N, C], k fp32 [B, 77, C])"""
+        if self.kind != "masactrl_mask_auto":
+            return
+        slot = self.auto_slots.get(attn._exec_index)
+        if (slot is not None) != (N == self.MAP_TOKENS):
+            raise RuntimeError(f"{attn.layer_name}: the auto-mask plan was lowered for the UNet's configured sample size, where "
+                               f"this module has {'256' if slot is not None else 'not 256'} queries; it runs at {N}.  Run at "
+                               "that size, or register a subclass of the editor to take the generic path")
+        if slot is None or self.muted:
+            return
+        if B != 4 or q.shape[0] != B or k.shape[0] != B or k.shape[1] != self.CTX_TOKENS:
+            raise RuntimeError(f"masactrl_mask_auto: cross-attention of batch {tuple(q.shape)} x {tuple(k.shape)}; the rule is "
+                               f"stated for the batch [u_src, u_tgt, c_src, c_tgt] and {self.CTX_TOKENS} prompt tokens")
+        slots, w, _ = self._auto
+        hip.cross_token_mass(q, k, attn.heads, attn.scale, (B // 2, B - 1), w, slots[slot])
+
+    def auto_launch(self, B: int, N: int, attn):
+        """a controlled self-attention layer under 'masactrl_mask_auto', after the mutual launch: None (not controlled, or no
+        slot written before it: plain mutual attention), or -- after launching the class kernel -- (target rows, their halves'
+        source rows, gate, k_cls, q_cls) for the class-masked launch that overwrites the target rows"""
+        if self.kind != "masactrl_mask_auto" or (attn._exec_index // 2) not in self.masa_layers:
+            return None
+        c = self.auto_layers.get(attn._exec_index, (0, N))[0]
+        if c < 1:
+            return None
+        kc, qc = self._class_words(attn._exec_index, N)      # also in a muted warm-up forward: they exist before capture
+        if self.muted:
+            return None
+        tgt, src = self._mask_rows[B]
+        slots, _, thres = self._auto
+        hip.masa_auto_classes(slots, c, thres, int(N ** 0.5), kc, qc, gate=self._gate[1])
+        return tgt, src, self._gate[1], kc, qc
+
+    def class_bits(self, layer: int, N: int = None):
+        """(key bits, query bits) bool [N] on the host: what the class kernel last wrote for transformer layer `layer` (tests)"""
+        for (ei, n), (kc, qc) in self._auto_cls.items():
+            if ei // 2 == layer and (N is None or n == N):
+                return hip.unpack_class_bits(kc, n), hip.unpack_class_bits(qc, n)
+        raise KeyError(f"no class words for layer {layer}")
+
     def controls_first_self(self, unet, tokens: int) -> bool:
         """does this plan act, in ANY step of its schedule, on the self-attention of the UNet's first transformer (`tokens`
         queries)?  Decided from what `signature` states -- which layers, which token limit -- never from a step window or a
@@ -244,7 +337,9 @@ class ControlPlan:
         first = blk.attentions[0].transformer_blocks[0].attn1
         if self.kind == "p2p":         # `/root/reference/p2p/model/attention_base.py:133`: self-attention replace at <= 16^2 keys
             return tokens <= self.self_max_tokens
-        if self.kind in ("masactrl", "masactrl_mask"):
+        if self.kind == "masactrl_mask_auto" and (first._exec_index + 1) in self.auto_slots:
+            return True                # the first transformer's cross-attention writes a slot from rows c_src / c_tgt of the FULL batch
+        if self.kind in self.MASA_KINDS:
             return (first._exec_index // 2) in self.masa_layers
         if self.kind == "pnp":
             return id(first) in self.pnp_layers
@@ -266,6 +361,9 @@ class ControlPlan:
             # load_from checks every length and refuses the reuse loudly.
             lens = tuple((N, self.mask_lengths(N)) for N in self.mask_tokens)
             return ("masactrl_mask", tuple(sorted(self.masa_layers)), (max(self.masa_steps) + 2) if self.masa_steps else 1, lens)
+        if self.kind == "masactrl_mask_auto":  # which modules write a slot and which layers read how many: launches; the rest is data
+            return ("masactrl_mask_auto", tuple(sorted(self.masa_layers)), (max(self.masa_steps) + 2) if self.masa_steps else 1,
+                    tuple(sorted(self.auto_slots.items())), tuple(sorted(self.auto_layers.items())))
         if self.kind == "pnp":
             idx = {id(m): m._exec_index for m in unet.attention_modules()}
             # the injected resnet as `pnp/model/register.py:_conv_module` picks it: resnets[0] on the SDXL family, else [1]
@@ -302,6 +400,15 @@ class ControlPlan:
                                        "these masks give; this loop cannot be reused for them")
                 for mine, theirs in zip(self.mask_lists(N), other.mask_lists(N)):
                     mine.copy_(theirs)
+        elif self.kind == "masactrl_mask_auto":
+            other.prepare(B)
+            self.prepare(B)
+            self.masa_steps = set(other.masa_steps)
+            self.auto_thres, self.auto_ref, self.auto_cur = other.auto_thres, list(other.auto_ref), list(other.auto_cur)
+            self._masa[B][0].copy_(other._masa[B][0])
+            self._gate[0].copy_(other._gate[0])
+            self._auto[1].copy_(other._auto[1])
+            self._auto[2].copy_(other._auto[2])
         elif self.kind == "pnp":
             other.prepare(B)
             self.pnp_qk_steps, self.pnp_conv_steps = other.pnp_qk_steps, other.pnp_conv_steps
@@ -312,7 +419,7 @@ class ControlPlan:
     def applies(self, B: int) -> bool:
         if self.kind == "empty" or self.muted:
             return False
-        if self.kind in ("masactrl", "masactrl_mask", "pnp"):
+        if self.kind in self.MASA_KINDS or self.kind == "pnp":
             return True
         if B != self.batch:
             raise RuntimeError(
@@ -332,7 +439,7 @@ class ControlPlan:
         if self.kind == "p2p":
             hip.select_step(self.coef_table, self.coef_cur, self.step)
             hip.select_step(self.self_table, self.self_cur, self.step)
-        elif self.kind in ("masactrl", "masactrl_mask"):
+        elif self.kind in self.MASA_KINDS:
             if B not in self._masa:
                 if self.captured:
                     raise RuntimeError("ControlPlan.prepare(B) must run before graph capture")
@@ -341,7 +448,7 @@ class ControlPlan:
             if not self.captured and int(self.controller.cur_step) >= tab.shape[0]:
                 self.step.fill_(tab.shape[0] - 1)   # past the last controlled step: identity row
             hip.select_step(tab, cur, self.step)
-            if self.kind == "masactrl_mask":        # the gate table has the same rows: 0 in the identity row past the end
+            if self.kind in self.GATED_KINDS:       # the gate table has the same rows: 0 in the identity row past the end
                 hip.select_step(self._gate[0], self._gate[1], self.step)
         elif self.kind == "pnp":
             if B not in self._pnp:
@@ -355,7 +462,7 @@ class ControlPlan:
             hip.select_step(cv, cv_cur, self.step)
 
     def end_forward(self, B: int):
-        if self.kind in ("masactrl", "masactrl_mask", "pnp") and not self.muted:
+        if (self.kind in self.MASA_KINDS or self.kind == "pnp") and not self.muted:
             hip.advance_step(self.step)
         elif self.kind != "empty" and not self.muted and B == self.batch:
             hip.advance_step(self.step)
@@ -379,7 +486,7 @@ class ControlPlan:
     def self_sources(self, B: int, N: int, attn):
         if self.kind == "p2p" and self.applies(B) and N <= self.self_max_tokens:
             return self.self_cur, self.self_cur, None
-        if self.kind in ("masactrl", "masactrl_mask") and not self.muted and (attn._exec_index // 2) in self.masa_layers:
+        if self.kind in self.MASA_KINDS and not self.muted and (attn._exec_index // 2) in self.masa_layers:
             cur = self._masa[B][1]
             return None, cur, cur
         if self.kind == "pnp" and not self.muted and id(attn) in self.pnp_layers:

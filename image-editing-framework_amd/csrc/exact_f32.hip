@@ -471,7 +471,11 @@ extern "C" int ief_attn_flash_f32(const IefAttnF32Params* pp, void* stream) {
     if (!p.x3 && (!p.Out || (p.ldo & 3) || (p.sOb & 3))) return IEF_EINVAL;
     if (!p.x3 && p.lse) return IEF_EINVAL;                // only the split-operand kernels write the row log-sum-exp
     if (p.key_splits > 1 && (!p.x3 || !p.Qp)) return IEF_EINVAL;     // only the operand-planes kernel splits its keys over workgroups
-    if (p.q_idx || p.k_idx || p.gate) {                   // gathered rows: the operand-planes kernel only, both lists, no lse, no key split
+    if (p.q_cls || p.k_cls) {                             // class-masked: the operand-planes kernel only, both class words, no lse, no key split, no lists
+        if (!p.x3 || !p.Qp || !p.q_cls || !p.k_cls || p.lse || p.key_splits > 1 || p.q_idx || p.k_idx || (p.N & 31) || (p.L & 31))
+            return IEF_EINVAL;
+        if (((uintptr_t)p.q_cls | (uintptr_t)p.k_cls | (uintptr_t)p.gate) & 3) return IEF_EALIGN;
+    } else if (p.q_idx || p.k_idx || p.gate) {            // gathered rows: the operand-planes kernel only, both lists, no lse, no key split
         if (!p.x3 || !p.Qp || !p.q_idx || !p.k_idx || p.lse || p.key_splits > 1) return IEF_EINVAL;
         if (((uintptr_t)p.q_idx | (uintptr_t)p.k_idx | (uintptr_t)p.gate) & 3) return IEF_EALIGN;
     }

@@ -888,10 +888,20 @@ __global__ __launch_bounds__(256, (D > 80) ? 1 : 2) void attn_flash_x3_kernel(co
 // per-lane source address, so the gather costs one index read per piece and nothing in LDS); p.N / p.L are the list lengths and
 // the tails qi >= N, row >= L are handled as ever.  *gate == 0: the workgroup returns before it touches anything (a captured step
 // graph keeps the launch in every step and the plan's gate table switches it off in the uncontrolled ones).
-template <int D, int KS, int NWV, bool LSE = false, bool SPLIT = false, bool IDX = false>
+// CLS (one more instantiation of its own; not with LSE, SPLIT or IDX): CLASS-MASKED attention over ALL keys -- every query and every
+// key carries one class bit (p.q_cls / p.k_cls, one word per 32 consecutive tokens; N and L are multiples of 32), and a score whose
+// two classes differ is dropped.  A wave's 32 queries share one word of q_cls and a 32-key sub-tile one word of k_cls, both
+// wave-uniform: the lane's query bit XOR the key word are the mismatch bits of its column, and accumulator r (key 8 (r >> 2) + 4 lh
+// + (r & 3)) is set to -inf where its bit is set, so exp2 makes it exactly 0.  A query can meet tiles in which EVERY key is
+// masked, the first included: its running maximum starts at a large finite negative number instead of -inf (-inf - -inf in the
+// rescale factor and in the exponent's bias would be NaN); exp2(-1e30 - m) is still exactly 0 once a real score arrives.  The gate
+// as for IDX.  What the form is for: masks that are DATA (made on the device per step and layer), where the gathered lists'
+// lengths cannot be launch arguments -- one launch for both classes.
+template <int D, int KS, int NWV, bool LSE = false, bool SPLIT = false, bool IDX = false, bool CLS = false>
 __global__ __launch_bounds__(64 * NWV, D <= 40 ? 4 : 2) void attn_flash_x3p_kernel(const IefAttnF32Params p) {
     static_assert(!IDX || (!LSE && !SPLIT), "the gathered launch writes no lse and does not split its keys");
-    if constexpr (IDX) {
+    static_assert(!CLS || (!LSE && !SPLIT && !IDX), "the class-masked launch writes no lse, does not split its keys and gathers nothing");
+    if constexpr (IDX || CLS) {
         if (p.gate && *p.gate == 0) return;      // uniform over the grid: nobody reaches a barrier
     }
     constexpr int DG = (D + 15) / 16, DT = (D + 31) / 32;
@@ -996,8 +1006,11 @@ __global__ __launch_bounds__(64 * NWV, D <= 40 ? 4 : 2) void attn_flash_x3p_kern
     for (int t = 0; t < DT; ++t)
 #pragma unroll
         for (int r = 0; r < 16; ++r) o[t][r] = 0.f;
-    float m_run = -INFINITY, l_run = 0.f;
+    float m_run = CLS ? -1e30f : -INFINITY, l_run = 0.f;
     const float sc2 = p.scale * 1.44269504088896341f;      // scores in log2 units (operand scale 1)
+    // CLS: the class word of this wave's 32 queries (q0 is a multiple of 32; a wave past N reads nothing and stores nothing)
+    unsigned qw = 0;
+    if constexpr (CLS) qw = q0 < p.N ? p.q_cls[q0 >> 5] : 0u;
     int nt = (p.L + KT - 1) / KT, t_beg = 0;
     if constexpr (SPLIT) {
         const int T = (nt + (int)gridDim.z - 1) / (int)gridDim.z;
@@ -1050,6 +1063,19 @@ __global__ __launch_bounds__(64 * NWV, D <= 40 ? 4 : 2) void attn_flash_x3p_kern
                 for (int r = 0; r < 16; ++r) {
                     const int key = t * KT + u * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
                     if (key >= p.L) sacc[u][r] = -INFINITY;
+                }
+            }
+        }
+        if constexpr (CLS) {
+#pragma unroll
+            for (int u = 0; u < KS; ++u) {
+                const int w = t * KS + u;                                    // wave-uniform: the word of this 32-key sub-tile
+                const unsigned kw = w * 32 < p.L ? p.k_cls[w] : 0u;          // (a sub-tile past L is masked above)
+                const unsigned mm = (kw ^ (0u - ((qw >> li) & 1u))) >> (4 * lh);      // bit 8 (r >> 2) + (r & 3): accumulator r mismatches
+                if (__builtin_amdgcn_ballot_w64(mm != 0u) != 0) {        // wave-uniform skip; straight-line selects instead spill 51 registers at d = 40, these 27
+#pragma unroll
+                    for (int r = 0; r < 16; ++r)
+                        if (mm & (1u << (8 * (r >> 2) + (r & 3)))) sacc[u][r] = -INFINITY;
                 }
             }
         }
@@ -1235,6 +1261,17 @@ int ief_attn_flash_x3_dispatch(const IefAttnF32Params& p, hipStream_t st) {
         if (!p.Kp || !p.Vp || !p.zeros) return IEF_EINVAL;
         if ((p.ldq & 7) || (p.ldk & 7) || (p.ldv & 7) || (p.sQb & 7) || (p.sKb & 7) || (p.sVb & 7) || (p.planeQ & 7) || (p.planeK & 7) ||
             (p.planeV & 7) || (((uintptr_t)p.Qp | (uintptr_t)p.Kp | (uintptr_t)p.Vp) & 15)) return IEF_EALIGN;
+        if (p.q_cls || p.k_cls) {                // class-masked (ief_attn_flash_f32 has refused lse, key_splits > 1, lists, a missing pointer, N or L % 32)
+#define FLASHP_CLS_GO(D_, KS_, NWV_, G_) hipLaunchKernelGGL((attn_flash_x3p_kernel<D_, KS_, NWV_, false, false, false, true>), G_, dim3(64 * NWV_), 0, st, p)
+            switch (p.d) {
+                case 40: FLASHP_CLS_GO(40, 2, 8, grid8); break;
+                case 64: FLASHP_CLS_GO(64, 1, 4, grid); break;
+                case 80: FLASHP_CLS_GO(80, 1, 4, grid); break;
+                default: return IEF_ESHAPE;
+            }
+            IEF_LAUNCH_CHECK();
+            return IEF_OK;
+        }
         if (p.q_idx || p.k_idx || p.gate) {      // gathered rows (ief_attn_flash_f32 has refused lse, key_splits > 1 and a missing list)
 #define FLASHP_IDX_GO(D_, KS_, NWV_, G_) hipLaunchKernelGGL((attn_flash_x3p_kernel<D_, KS_, NWV_, false, false, true>), G_, dim3(64 * NWV_), 0, st, p)
             switch (p.d) {

@@ -111,6 +111,7 @@ class IefAttnF32Params(Structure):
         ("Qp", c_void_p), ("Kp", c_void_p), ("Vp", c_void_p), ("planeQ", c_longlong), ("planeK", c_longlong), ("planeV", c_longlong),
         ("zeros", c_void_p), ("lse", c_void_p),
         ("key_splits", c_int), ("ws", c_void_p), ("ws_floats", c_longlong),
+        ("k_cls", c_void_p), ("q_cls", c_void_p),
         ("q_idx", c_void_p), ("k_idx", c_void_p), ("gate", c_void_p),
     ]
 
@@ -174,6 +175,8 @@ EXPORTS = [
     "ief_attn_flash_ws_floats",
     # CFG step with a shared prefix: conv_in that writes its planes, the batch repeat
     "ief_conv_in_f32act_planes", "ief_repeat_batch",
+    # MasaCtrl's masks from cross-attention (csrc/masa_auto.hip)
+    "ief_cross_token_mass_f32", "ief_masa_auto_classes",
 ]
 
 
@@ -302,6 +305,8 @@ def load():
     lib.ief_groupnorm_silu_x3p_small.argtypes = [c_void_p, c_void_p, c_int, c_int, c_void_p, c_longlong, c_void_p, c_void_p,
                                                  c_int, c_int, c_int, c_float, c_int, c_void_p]
     lib.ief_layernorm_x3p.argtypes = [c_void_p, c_void_p, c_longlong, c_void_p, c_void_p, c_longlong, c_int, c_float, c_void_p]
+    lib.ief_cross_token_mass_f32.argtypes = [c_void_p] * 4 + [c_int] * 8 + [c_longlong, c_longlong, c_float, c_void_p]
+    lib.ief_masa_auto_classes.argtypes = [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]
     if lib.ief_abi_version() != ABI_VERSION:
         raise HipExtensionMissing("libief_hip.so ABI version mismatch; rebuild")
     lib.ief_struct_size.argtypes = [c_int]
@@ -1885,6 +1890,61 @@ def select_step(table, out, step):
 def advance_step(step):
     lib = load()
     _check(lib.ief_advance_step(_devi32(step, "step").data_ptr(), _stream()), "ief_advance_step")
+
+
+def cross_token_mass(q, k, heads, scale, rows, w, out):
+    """out[r][n] = (1 / heads) sum_h sum_l w[r][l] softmax_l(scale q_h[rows[r]][n] . k_h[rows[r]][l]), r = 0, 1: the head-mean
+    cross-attention map of two batch rows, summed over prompt tokens with multiplicities w, without the map (csrc/masa_auto.hip).
+    q fp32 [B, N, heads*d], k fp32 [B, L, heads*d] (column slices are fine), w fp32 [2, L], out fp32 [2, N] (both contiguous);
+    rows: two host ints.  d any multiple of 8, L <= 128."""
+    lib = load()
+    _act32(q, "q"), _act32(k, "k"), _dev32(w, "w"), _dev32(out, "out")
+    B, N, C = q.shape
+    L = k.shape[1]
+    if q.dim() != 3 or k.dim() != 3 or k.shape[0] != B or k.shape[2] != C or C % heads:
+        raise ValueError("cross_token_mass: q [B, N, heads*d] and k [B, L, heads*d]")
+    r0, r1 = int(rows[0]), int(rows[1])
+    if not (0 <= r0 < B and 0 <= r1 < B):
+        raise ValueError(f"cross_token_mass: rows {tuple(rows)} outside the batch of {B}")
+    if tuple(w.shape) != (2, L) or tuple(out.shape) != (2, N):
+        raise ValueError(f"cross_token_mass: w must be [2, {L}] and out [2, {N}]")
+    with _Timed("cross_token_mass_f32_kernel", 4.0 * heads * N * L * (C // heads), 4.0 * 2 * C * (N + L)):
+        _check(lib.ief_cross_token_mass_f32(q.data_ptr(), k.data_ptr(), w.data_ptr(), out.data_ptr(), r0, r1, heads, N, L, C // heads,
+                                            q.stride(1), k.stride(1), q.stride(0), k.stride(0), float(scale), _stream()),
+               "ief_cross_token_mass_f32")
+    return out
+
+
+def masa_auto_classes(slots, c, thres, res, k_cls, q_cls, gate=None):
+    """class bits of a res x res layer from the first c slots of `slots` (fp32 [K, 2, 256], what `cross_token_mass` wrote for the
+    16 x 16 level): mean over the slots, per-row (v - min) / (max - min), nearest pixel, >= thres (device fp32 [1]); k_cls from row
+    0 and q_cls from row 1, int32 [res*res / 32] holding one bit per token.  A row with max == min makes every token of both rows
+    background.  gate (device int32 [1]): nothing is written while it holds 0."""
+    lib = load()
+    _dev32(slots, "slots"), _dev32(thres, "thres"), _devi32(k_cls, "k_cls"), _devi32(q_cls, "q_cls"), _devi32(gate, "gate")
+    c, res = int(c), int(res)
+    if slots.dim() != 3 or tuple(slots.shape[1:]) != (2, 256) or not 1 <= c <= slots.shape[0]:
+        raise ValueError("masa_auto_classes: slots must be [K, 2, 256] with 1 <= c <= K")
+    if (res * res) % 32 or k_cls.numel() != res * res // 32 or q_cls.numel() != res * res // 32:
+        raise ValueError("masa_auto_classes: k_cls / q_cls hold res*res / 32 words each")
+    _check(lib.ief_masa_auto_classes(slots.data_ptr(), c, thres.data_ptr(), res, k_cls.data_ptr(), q_cls.data_ptr(), _ptr(gate),
+                                     _stream()), "ief_masa_auto_classes")
+
+
+def unpack_class_bits(words, n):
+    """packed class words (int32, bit i of word w = token 32 w + i) -> bool [n] on the host"""
+    w = words.detach().cpu().to(torch.int64) & 0xFFFFFFFF
+    return ((w[:, None] >> torch.arange(32)) & 1).flatten()[:n].bool()
+
+
+def pack_class_bits(bits, device=None):
+    """bool [n] (n a multiple of 32) -> packed int32 class words for `planes.attn_flash(q_cls= / k_cls=)`"""
+    b = bits.detach().cpu().flatten().to(torch.int64)
+    if b.numel() % 32:
+        raise ValueError("pack_class_bits: the token count must be a multiple of 32")
+    w = (b.reshape(-1, 32) << torch.arange(32)).sum(1)
+    w = torch.where(w >= 2 ** 31, w - 2 ** 32, w).to(torch.int32)
+    return w if device is None else w.to(device)
 
 
 # ------------------------------------------------------------------------------- activation gradients (null-text inversion)

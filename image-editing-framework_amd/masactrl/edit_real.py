@@ -12,7 +12,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 from _bootstrap import load_pipe, seed_everything  # noqa: E402
 
 from ief_amd.masactrl.model.attention_control import (MutualSelfAttentionControl, MutualSelfAttentionControlMask,  # noqa: E402
-                                                      load_mask_png)
+                                                      MutualSelfAttentionControlMaskAuto, load_mask_png)
 from ief_amd.masactrl.model.register import regiter_attention_editor_diffusers, unregister_attention_control  # noqa: E402
 from ief_amd.masactrl.model.sd_utils import MasaCtrl, MasaCtrl_NTI, MasaCtrl_XL, MasaCtrl_XL_NTI  # noqa: E402
 from ief_amd.p2p.inversion.ddim import ddim_inversion, ddim_inversion_xl  # noqa: E402
@@ -30,15 +30,23 @@ parser.add_argument("--inversion_type", type=str, default="null-text")
 # optional, both or neither: foreground masks of the source / target image (PNG, thresholded at 0.5) -> mask-guided MasaCtrl
 parser.add_argument("--mask_s", type=str, default=None)
 parser.add_argument("--mask_t", type=str, default=None)
+# --mask_auto: the masks come from the step's own cross-attention maps of the prompt tokens --ref_token_idx (source prompt) and
+# --cur_token_idx (target prompt), thresholded at --thres (MutualSelfAttentionControlMaskAuto); not together with --mask_s / --mask_t
+parser.add_argument("--mask_auto", action="store_true")
+parser.add_argument("--thres", type=float, default=0.1)
+parser.add_argument("--ref_token_idx", type=int, nargs="+", default=[1])
+parser.add_argument("--cur_token_idx", type=int, nargs="+", default=[1])
+parser.add_argument("--mask_save_dir", type=str, default=None)
 
 STEP, LAYPER = 4, 10
 NUM_INNER_STEPS, EARLY_STOP_EPSILON = 10, 1e-5
 
 
 def edit_one(pipe, editor, invertor, image, source_prompt, target_prompt, inversion_type, device, size,
-             num_inference_steps=50, guidance_scale=7.5, masks=None):
+             num_inference_steps=50, guidance_scale=7.5, masks=None, auto=None):
     """invert + MasaCtrl-edit one PIL image -> uint8 images [2,H,W,3] (reconstruction, edit); :128-153 of the reference.
-    masks: optional (mask_s, mask_t) fp32 [h, w] in {0, 1} -> the mask-guided editor"""
+    masks: optional (mask_s, mask_t) fp32 [h, w] in {0, 1} -> the mask-guided editor; auto: optional dict(thres=, ref_token_idx=,
+    cur_token_idx=, mask_save_dir=) -> the editor that makes its masks from cross-attention"""
     latent = invertor.image2latent(model=pipe, image=image, device=device, dtype=torch.float32)
     latents, context = invertor.ddim_inversion_loop(pipe, latent, source_prompt)
     extra = {}
@@ -50,7 +58,9 @@ def edit_one(pipe, editor, invertor, image, source_prompt, target_prompt, invers
         raise ValueError("Please choose right inversion type")
     init_latent = torch.cat([latents[-1], latents[-1]])
     xl = pipe.__class__.__name__ == "StableDiffusionXLPipeline"          # model_type / LAYPER switch of edit_real.py:96-115
-    if masks is not None:
+    if auto is not None:
+        controller = MutualSelfAttentionControlMaskAuto(STEP, 54 if xl else LAYPER, model_type="SDXL" if xl else "SD", **auto)
+    elif masks is not None:
         controller = MutualSelfAttentionControlMask(STEP, 54 if xl else LAYPER, mask_s=masks[0], mask_t=masks[1],
                                                     model_type="SDXL" if xl else "SD")
     else:
@@ -78,6 +88,8 @@ def main(argv=None):
     args = parser.parse_args(argv)
     if (args.mask_s is None) != (args.mask_t is None):
         parser.error("--mask_s and --mask_t go together")
+    if args.mask_auto and args.mask_s is not None:
+        parser.error("--mask_auto makes its own masks: not together with --mask_s / --mask_t")
     device = torch.device("cuda:{}".format(args.device))
     seed_everything(args.seed)
     num_inference_steps = 50
@@ -90,7 +102,9 @@ def main(argv=None):
     original_image.save(os.path.join(out_path, "source.png"))
     masks = None if args.mask_s is None else (load_mask_png(args.mask_s, device), load_mask_png(args.mask_t, device))
     images = edit_one(pipe, editor, invertor, original_image, [args.source_prompt], [args.target_prompt],
-                      args.inversion_type, device, size, num_inference_steps, masks=masks)
+                      args.inversion_type, device, size, num_inference_steps, masks=masks,
+                      auto=dict(thres=args.thres, ref_token_idx=args.ref_token_idx, cur_token_idx=args.cur_token_idx,
+                                mask_save_dir=args.mask_save_dir) if args.mask_auto else None)
     save_img(images[0], os.path.join(out_path, "inversion.png"))
     save_img(images[1], os.path.join(out_path, "edit.png"))
 

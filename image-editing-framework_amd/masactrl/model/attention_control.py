@@ -9,8 +9,12 @@ From `start_step` on, in transformer layers >= `start_layer` (layer = cur_att_la
 source rows attend to themselves; each target row attends to its half's source keys twice -- "fg" with every key outside
 `mask_s` pushed to `finfo.min`, "bg" with every key inside it -- and the two outputs are blended per query by `mask_t`.
 Here the CLIs reach it through `--mask_s / --mask_t`.  With binary masks in the f16x3 mode `register.py` lowers it to
-gathered flash-attention launches; everywhere else the bodies below run on the generic path.  The Union and MaskAuto
-variants are not ported.
+gathered flash-attention launches; everywhere else the bodies below run on the generic path.
+
+`MutualSelfAttentionControlMaskAuto` (:192-330) needs no masks from the user: per controlled layer it makes them from the
+16 x 16 cross-attention maps the step has computed so far (`--mask_auto`).  In the f16x3 mode `register.py` lowers it to one
+class-masked flash-attention launch per controlled layer (`control.py`, kind 'masactrl_mask_auto').  The Union variant is
+not ported.
 """
 import os
 
@@ -118,6 +122,78 @@ class MutualSelfAttentionControlMask(MutualSelfAttentionControl):
             out_u_target = out_u_fg * mask + out_u_bg * (1 - mask)
             out_c_target = out_c_fg * mask + out_c_bg * (1 - mask)
         return torch.cat([out_u_source, out_u_target, out_c_source, out_c_target], dim=0)
+
+
+class MutualSelfAttentionControlMaskAuto(MutualSelfAttentionControl):
+    MAP_TOKENS = 16 * 16       # the cross-attention level whose maps make the masks
+
+    def __init__(self, start_step=4, start_layer=10, layer_idx=None, step_idx=None, total_steps=50, thres=0.1, ref_token_idx=[1],
+                 cur_token_idx=[1], mask_save_dir=None, model_type="SD"):
+        """the masks of `MutualSelfAttentionControlMask` made from the prompt instead of two images: the head-mean of every
+        16 x 16 cross-attention map of the CURRENT step so far, summed over the prompt tokens `ref_token_idx` (source, keys) /
+        `cur_token_idx` (target, queries; a token listed twice counts twice), normalised to [0, 1] per batch row and
+        thresholded at `thres`.  A map that is constant over the image (max == min) gives NaN and with it an all-background
+        mask here; the fused plan (`control.py`, kind 'masactrl_mask_auto') makes every token background in that case, which
+        is plain mutual attention"""
+        super().__init__(start_step, start_layer, layer_idx, step_idx, total_steps, model_type)
+        print("Using MutualSelfAttentionControlMaskAuto")
+        self.thres = thres
+        self.ref_token_idx = ref_token_idx
+        self.cur_token_idx = cur_token_idx
+        self.cross_attns = []          # head-mean maps [B, 256, L] of this step, in execution order
+        self.mask_s = None             # binary masks [res, res] of the last controlled call that had maps (None before)
+        self.mask_t = None
+        self.mask_save_dir = mask_save_dir
+        if mask_save_dir is not None:
+            os.makedirs(mask_save_dir, exist_ok=True)
+
+    def after_step(self):
+        self.cross_attns = []
+
+    def token_image(self, idx):
+        """[B, 16, 16]: mean of the collected maps, summed over the tokens `idx`, each batch row scaled to min 0 / max 1"""
+        a = torch.stack(self.cross_attns).mean(0)
+        res = int(a.shape[1] ** 0.5)
+        img = a.reshape(a.shape[0], res, res, a.shape[-1])[..., list(idx) if isinstance(idx, (list, tuple)) else [idx]].sum(-1)
+        lo, hi = img.amin(dim=(1, 2), keepdim=True), img.amax(dim=(1, 2), keepdim=True)
+        return (img - lo) / (hi - lo)
+
+    def _layer_mask(self, img, res, name):
+        soft = F.interpolate(img[None, None], (res, res))[0, 0]
+        if self.mask_save_dir is not None:
+            _save_mask_png(soft, os.path.join(self.mask_save_dir, f"{name}_{self.cur_step}_{self.cur_att_layer}.png"))
+        return (soft >= self.thres).to(img.dtype)
+
+    def masked_target(self, q, k, v, key_mask, query_mask, num_heads, scale):
+        """one target row over its half's source keys: q, k, v [h, n, d]; queries inside `query_mask` take the softmax over
+        the keys inside `key_mask`, the others over the keys outside it -> [1, n, h*d]"""
+        s = torch.bmm(q, k.transpose(1, 2)) * scale
+        lowest = torch.finfo(s.dtype).min
+        km = key_mask.flatten()
+        fg = torch.bmm((s + km.masked_fill(km == 0, lowest)).softmax(-1), v)
+        bg = torch.bmm((s + km.masked_fill(km == 1, lowest)).softmax(-1), v)
+        qm = query_mask.reshape(-1, 1)
+        out = fg * qm + bg * (1 - qm)
+        return out.permute(1, 0, 2).reshape(1, q.shape[1], -1)
+
+    def forward(self, q, k, v, sim, attn, is_cross, place_in_unet, num_heads, **kwargs):
+        if is_cross and attn.shape[1] == self.MAP_TOKENS:
+            self.cross_attns.append(attn.reshape(-1, num_heads, *attn.shape[-2:]).mean(1))
+        if is_cross or self.cur_step not in self.step_idx or self.cur_att_layer // 2 not in self.layer_idx or not self.cross_attns:
+            return super().forward(q, k, v, sim, attn, is_cross, place_in_unet, num_heads, **kwargs)
+        h, n = num_heads, q.shape[1]
+        if q.shape[0] != 4 * h:
+            raise RuntimeError(f"MaskAuto acts on the UNet batch [u_src, u_tgt, c_src, c_tgt]; got batch {q.shape[0] // h}")
+        res = int(n ** 0.5)
+        self.mask_s = self._layer_mask(self.token_image(self.ref_token_idx)[-2].to(q.dtype), res, "mask_s")
+        self.mask_t = self._layer_mask(self.token_image(self.cur_token_idx)[-1].to(q.dtype), res, "mask_t")
+        outs = []
+        for half in (0, 2):        # rows (src, tgt) of the uncond, then of the cond half
+            src, tgt = slice(half * h, (half + 1) * h), slice((half + 1) * h, (half + 2) * h)
+            outs.append(MutualSelfAttentionControl.attn_batch(self, q[src], k[src], v[src], None, None, is_cross, place_in_unet, h,
+                                                              **kwargs))
+            outs.append(self.masked_target(q[tgt], k[src], v[src], self.mask_s, self.mask_t, h, kwargs.get("scale")))
+        return torch.cat(outs, dim=0)
 
 
 def load_mask_png(path, device="cpu"):

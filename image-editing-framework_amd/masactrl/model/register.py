@@ -7,9 +7,12 @@ the reference CLIs use — `AttentionBase` (plain attention) and `MutualSelfAtte
 device plan: the fused flash-attention kernel takes per-batch K/V source rows, which IS mutual self-attention
 (`ief_attn_flash_f16`, k_src / v_src).  `MutualSelfAttentionControlMask` with two binary masks is lowered too where
 the planes attention runs (f16x3): the mutual launch plus two launches over gathered row lists (`control.py`,
-kind 'masactrl_mask'); `lower_editor` prints why when it cannot.  Any OTHER editor (a user subclass of `AttentionBase`,
-the store / auto-mask variants) takes the GENERIC path: a closure with the reference's dataflow (:10-48) on our kernels materialises `sim` and
-`attn` ([B*heads, N, L]) and calls the editor's Python, exactly as `p2p/model/register.py` does for controllers.
+kind 'masactrl_mask'), and so is `MutualSelfAttentionControlMaskAuto`, whose masks come from the step's own 16 x 16
+cross-attention maps: two small kernels make packed class bits on the device and ONE class-masked launch per controlled layer
+reads them (kind 'masactrl_mask_auto').  `lower_editor` prints why when it cannot.  Any OTHER editor (a user subclass of
+`AttentionBase` or of the classes above, the Union variant) takes the GENERIC path: a closure with the reference's dataflow
+(:10-48) on our kernels materialises `sim` and `attn` ([B*heads, N, L]) and calls the editor's Python, exactly as
+`p2p/model/register.py` does for controllers.
 """
 import torch
 
@@ -45,6 +48,68 @@ def _controlled_self_layers(unet, layers):
         if blk.upsamplers is not None:
             res *= 2
     return out
+
+
+def _attention_order(unet):
+    """(module, tokens) of every attention module in execution order, at the UNet's configured sample size"""
+    out, res = [], int(unet.cfg.sample_size)
+
+    def visit(block):
+        out.extend((m, res * res) for m in block.modules() if m.__class__.__name__ == "Attention")
+
+    for blk in unet.down_blocks:
+        visit(blk)
+        if blk.downsamplers is not None:
+            res //= 2
+    visit(unet.mid_block)
+    for blk in unet.up_blocks:
+        visit(blk)
+        if blk.upsamplers is not None:
+            res *= 2
+    return sorted(out, key=lambda e: e[0]._exec_index)
+
+
+def auto_mask_refusal(editor, precision, x3p, flash_planes, layer_shapes, batch=4):
+    """the host part of the decision to lower `MutualSelfAttentionControlMaskAuto`: None, or the reason it takes the generic
+    path.  layer_shapes: (head dim, tokens) of the controlled self-attention layers; batch: the UNet batch it will see"""
+    if precision != "f16x3" or not x3p or not flash_planes:
+        return "the fused rule runs on the planes attention of the f16x3 mode only"
+    if editor.mask_save_dir is not None:
+        return "mask_save_dir writes every layer's masks to disk, which the fused plan never brings to the host"
+    if not (isinstance(editor.thres, (int, float)) and 0 < editor.thres <= 1):
+        return f"thres = {editor.thres!r} is outside (0, 1]: a key class could be empty"
+    for idx, nm in ((editor.ref_token_idx, "ref_token_idx"), (editor.cur_token_idx, "cur_token_idx")):
+        if not isinstance(idx, (list, tuple)) or not idx or not all(isinstance(i, int) and 0 <= i < ControlPlan.CTX_TOKENS for i in idx):
+            return f"{nm} = {idx!r} is not a non-empty list of token indices in [0, {ControlPlan.CTX_TOKENS})"
+    if batch != 4:
+        return f"the rule is stated for the UNet batch [u_src, u_tgt, c_src, c_tgt]; got batch {batch}"
+    for d, N in layer_shapes:
+        if d not in planes.FLASH_PLANES_DIMS:
+            return f"a controlled layer has head dim {d}, outside the planes attention's {planes.FLASH_PLANES_DIMS}"
+        if N < ControlPlan.MAP_TOKENS:
+            return f"a controlled layer has {N} tokens, fewer than the {ControlPlan.MAP_TOKENS} of the maps the masks come from"
+        if N % 32:
+            return f"a controlled layer has {N} tokens, no multiple of the 32 a class word covers"
+    return None
+
+
+def _lower_auto_editor(editor, device, unet):
+    """the fused plan of `MutualSelfAttentionControlMaskAuto`, or None with one printed line saying why not.  Which modules have
+    256 queries, and how many of them precede each controlled layer, is counted at the UNet's configured sample size"""
+    layers = set(int(l) for l in editor.layer_idx)
+    why = auto_mask_refusal(editor, getattr(unet, "precision", None), getattr(unet, "x3p", False), planes.FLASH_PLANES,
+                            _controlled_self_layers(unet, layers) if unet is not None else ())
+    if why is not None:
+        print(f"auto-mask MasaCtrl takes the generic path: {why}")
+        return None
+    slots, counts = {}, {}
+    for m, N in _attention_order(unet):
+        if m.is_cross and N == ControlPlan.MAP_TOKENS:
+            slots[m._exec_index] = len(slots)
+        elif not m.is_cross and (m._exec_index // 2) in layers:
+            counts[m._exec_index] = (len(slots), N)
+    return ControlPlan(editor, "masactrl_mask_auto", device, masa_steps=editor.step_idx, masa_layers=layers, auto_slots=slots,
+                       auto_layers=counts, auto_thres=editor.thres, auto_ref=editor.ref_token_idx, auto_cur=editor.cur_token_idx)
 
 
 def _lower_mask_editor(editor, device, unet):
@@ -87,6 +152,8 @@ def lower_editor(editor, device, unet=None):
         return ControlPlan(editor, "masactrl", device, masa_steps=editor.step_idx, masa_layers=editor.layer_idx)
     if name == "MutualSelfAttentionControlMask":
         return _lower_mask_editor(editor, device, unet)
+    if name == "MutualSelfAttentionControlMaskAuto":
+        return _lower_auto_editor(editor, device, unet)
     return None
 
 

@@ -569,7 +569,7 @@ def attn_key_splits(B, heads, N, L, d, cus=None, setting="auto") -> int:
 
 
 def attn_flash(q, k, v, heads, scale, q_src=None, k_src=None, v_src=None, out=None, out_planes=True, lse=None, key_splits=1,
-               q_idx=None, k_idx=None, gate=None):
+               q_idx=None, k_idx=None, gate=None, q_cls=None, k_cls=None):
     """fused attention on operand planes: q [B,N,h*d], k / v [B,L,h*d] as Planes (column slices of the q|k|v GEMM's output are
     fine); K / V tiles are staged by LDS-DMA, nothing is split in the kernel (`attn_flash_x3p_kernel`).  Returns Planes (for
     to_out's GEMM) or, with out_planes=False, fp32.
@@ -581,21 +581,36 @@ def attn_flash(q, k, v, heads, scale, q_src=None, k_src=None, v_src=None, out=No
     so the destination must exist: `out=` an fp32 tensor or `out_planes=` a Planes, [Bo, rows, heads*d] (batch-strided views are
     fine); the launch's batch is Bo and q_src / k_src / v_src (Bo entries each) pick the operands' batch rows.  Every index must
     be a row of the operand it addresses: the lists live on the device and are NOT checked here.  gate: optional int32 device
-    scalar; the launch writes nothing while it holds 0.  No lse and no key split with lists (ValueError)."""
+    scalar; the launch writes nothing while it holds 0.  No lse and no key split with lists (ValueError).
+    q_cls / k_cls (int32 device words, both or neither; `hip.pack_class_bits`): CLASS-MASKED attention -- bit i of word w is the
+    class of token 32 w + i (N / 32 and L / 32 words, N and L multiples of 32, shared by all batch rows), and every query attends
+    to the keys of its own class only, in ONE launch over all keys.  The destination must exist as for the lists (`out=` /
+    `out_planes=` a Planes, [Bo, N, heads*d]); all its rows are written, q_src / k_src / v_src pick the operands' batch rows, gate
+    as above.  Not with lists, lse or a key split (ValueError)."""
     lib = hip.load()
     idx = q_idx is not None or k_idx is not None
+    cls = q_cls is not None or k_cls is not None
     if idx and (q_idx is None or k_idx is None):
         raise ValueError("planes.attn_flash: q_idx and k_idx go together")
-    if gate is not None and not idx:
-        raise ValueError("planes.attn_flash: gate needs q_idx / k_idx")
+    if cls and (q_cls is None or k_cls is None):
+        raise ValueError("planes.attn_flash: q_cls and k_cls go together")
+    if cls and (idx or lse is not None or key_splits != 1):
+        raise ValueError("planes.attn_flash: a class-masked launch (q_cls / k_cls) takes no lists, writes no lse and does not "
+                         "split its keys")
+    if gate is not None and not (idx or cls):
+        raise ValueError("planes.attn_flash: gate needs q_idx / k_idx or q_cls / k_cls")
     if idx and (lse is not None or key_splits != 1):
         raise ValueError("planes.attn_flash: a gathered launch (q_idx / k_idx) writes no lse and does not split its keys")
     dest_p = out_planes if isinstance(out_planes, Planes) else None
     if idx and dest_p is None and out is None:
         raise ValueError("planes.attn_flash: with q_idx / k_idx only the listed rows are written: pass the existing destination "
                          "as out= (fp32) or out_planes= (Planes)")
-    if dest_p is not None and not idx:
-        raise ValueError("planes.attn_flash: out_planes=<Planes> is the destination of a gathered launch (q_idx / k_idx)")
+    if cls and dest_p is None and out is None:
+        raise ValueError("planes.attn_flash: a class-masked launch overwrites rows of an existing destination: pass it as out= "
+                         "(fp32) or out_planes= (Planes)")
+    if dest_p is not None and not (idx or cls):
+        raise ValueError("planes.attn_flash: out_planes=<Planes> is the destination of a gathered launch (q_idx / k_idx) or a "
+                         "class-masked one (q_cls / k_cls)")
     for t, nm in ((q, "q"), (k, "k"), (v, "v")):
         if not isinstance(t, Planes) or t.dim() != 3:
             raise TypeError(f"planes.attn_flash: {nm} must be Planes [B, rows, heads*d]")
@@ -629,6 +644,21 @@ def attn_flash(q, k, v, heads, scale, q_src=None, k_src=None, v_src=None, out=No
                 raise ValueError(f"planes.attn_flash: a destination of {B} batch rows over operands of {q.shape[0]} needs {nm}")
         p.B, p.N, p.L = B, N, L
         p.q_idx, p.k_idx, p.gate = q_idx.data_ptr(), k_idx.data_ptr(), _ptr(gate)
+    if cls:
+        hip._devi32(q_cls, "q_cls"), hip._devi32(k_cls, "k_cls"), hip._devi32(gate, "gate")
+        if N % 32 or L % 32 or q_cls.numel() != N // 32 or k_cls.numel() != L // 32:
+            raise ValueError(f"planes.attn_flash: q_cls / k_cls hold one word per 32 tokens ({N} queries, {L} keys: multiples of 32)")
+        dest = dest_p.hi if dest_p is not None else hip._act32(out, "out")
+        if dest.dim() != 3 or dest.shape[1] != N or dest.shape[2] != C:
+            raise ValueError(f"planes.attn_flash: the destination must be [Bo, {N}, {C}]")
+        B = dest.shape[0]
+        for t, nm in ((q_src, "q_src"), (k_src, "k_src"), (v_src, "v_src")):
+            if t is not None and t.numel() != B:
+                raise ValueError(f"planes.attn_flash: {nm} must have one entry per destination batch row ({B})")
+            if t is None and B != q.shape[0]:
+                raise ValueError(f"planes.attn_flash: a destination of {B} batch rows over operands of {q.shape[0]} needs {nm}")
+        p.B = B
+        p.q_cls, p.k_cls, p.gate = q_cls.data_ptr(), k_cls.data_ptr(), _ptr(gate)
     p.q_src, p.k_src, p.v_src = _ptr(hip._devi32(q_src, "q_src")), _ptr(hip._devi32(k_src, "k_src")), _ptr(hip._devi32(v_src, "v_src"))
     p.x3, p.zeros = 1, _zeros(q.device)
     if lse is not None:
@@ -645,7 +675,7 @@ def attn_flash(q, k, v, heads, scale, q_src=None, k_src=None, v_src=None, out=No
             if tuple(hip._act32(out, "out").shape) != tuple(h_.shape):
                 raise ValueError("planes.attn_flash: out and out_planes must have one shape")
             p.Out, p.sOb, p.ldo = out.data_ptr(), out.stride(0), out.stride(1)
-    elif out_planes and not idx:
+    elif out_planes and not idx and not cls:
         op, _ = attn_out_args(p, B, N, C, q.device)
     else:
         if out is None:
@@ -655,6 +685,8 @@ def attn_flash(q, k, v, heads, scale, q_src=None, k_src=None, v_src=None, out=No
     name, nbytes = f"attn_flash_x3p_kernel<{d}>", 4.0 * B * heads * d * (2 * N + 2 * L)
     if idx:
         name = f"attn_flash_x3p_kernel<{d}, idx>"
+    elif cls:
+        name = f"attn_flash_x3p_kernel<{d}, cls>"
     elif S > 1:
         nws = lib.ief_attn_flash_ws_floats(B, heads, N, L, d, S)
         ws = torch.empty(nws, dtype=torch.float32, device=q.device)

@@ -297,7 +297,9 @@ class Attention(nn.Module):
             if plan is not None:
                 qs, ks, vs = plan.self_sources(B, N, self)
             if cfg_rows is not None and (qs is not None or ks is not None or vs is not None
-                                         or (plan is not None and plan.mask_launches(B, N, self) is not None)):
+                                         or (plan is not None and plan.mask_launches(B, N, self) is not None)
+                                         or (plan is not None and plan.kind == "masactrl_mask_auto"
+                                             and (self._exec_index // 2) in plan.masa_layers)):
                 raise RuntimeError(f"{self.layer_name}: the control plan acts on a self-attention that runs in the shared prefix of a "
                                    "CFG step (ControlPlan.controls_first_self must say so)")
             if planes.FLASH_PLANES and self.dim_head in planes.FLASH_PLANES_DIMS:
@@ -314,9 +316,17 @@ class Attention(nn.Module):
                     for q_idx, k_idx in pairs:
                         planes.attn_flash(qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:], self.heads, self.scale, q_src=tgt,
                                           k_src=src, v_src=src, out_planes=o[1::2], q_idx=q_idx, k_idx=k_idx, gate=gate)
+                al = plan.auto_launch(B, N, self) if plan is not None else None
+                if al is not None:
+                    # masks from cross-attention: the class kernel has just turned the maps this step collected so far into class
+                    # bits; ONE class-masked launch over all source keys overwrites both target rows (a query attends to the
+                    # source keys of its own class), nothing written while the step's gate is 0
+                    tgt, src, gate, k_cls, q_cls = al
+                    planes.attn_flash(qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:], self.heads, self.scale, q_src=tgt,
+                                      k_src=src, v_src=src, out_planes=o[1::2], q_cls=q_cls, k_cls=k_cls, gate=gate)
             else:
                 qkv = planes.gemm(xp, w_in, bias=b_in, ln=ln)
-                if plan is not None and plan.mask_launches(B, N, self) is not None:
+                if plan is not None and (plan.mask_launches(B, N, self) is not None or plan.auto_launch(B, N, self) is not None):
                     raise RuntimeError(f"mask-guided MasaCtrl was lowered onto a layer of head dim {self.dim_head} that has no "
                                        "planes attention")
                 o = hip.attn_flash(qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:], self.heads, self.scale, q_src=qs, k_src=ks,
@@ -327,6 +337,8 @@ class Attention(nn.Module):
             args = plan.cross_edit(B, self) if plan is not None else {}
             if self.map_out is not None:
                 hip.attn_probs(q, kv[..., :C], self.heads, self.scale, out=self.map_out)
+            if plan is not None:
+                plan.cross_mass(B, N, self, q, kv[..., :C])
             o = hip.attn_cross_p2p(q, kv[..., :C], kv[..., C:], self.heads, self.scale, out_planes=True, q_src=cfg_rows, **args)
         if plan is not None:
             plan.layer_done(self)

@@ -326,6 +326,15 @@ typedef struct IefAttnF32Params {
      * until the stream passes; ws_floats: its size.  Without Qp or with x3 == 0, key_splits > 1 is IEF_EINVAL; so are a null or
      * short ws; a misaligned one is IEF_EALIGN. */
     int key_splits; float* ws; long long ws_floats;
+    /* operand planes in (Qp set) only, ABI 4; both null = the launches above (the pair sits in FRONT of the gathered-rows
+     * fields, which stay the last three of the block; callers set fields by name and the library checks ief_struct_size(6)).  CLASS-MASKED attention: every query
+     * and every key carries one class bit, packed one uint32 per 32 consecutive tokens (bit i of word w = token 32 w + i): q_cls
+     * [N / 32] and k_cls [L / 32], shared by every batch row of the launch.  A score whose query and key differ in class
+     * contributes exactly nothing: query i takes softmax attention over the keys of its own class (a query whose class has no
+     * key gets NaN).  All N rows of every batch row of Out / OutP are written; gate as below.  Both pointers or neither, N
+     * and L multiples of 32, no lse, no key_splits > 1, no q_idx / k_idx, Qp set and x3 != 0: IEF_EINVAL otherwise; a
+     * pointer that is not 4-byte aligned: IEF_EALIGN.  Nothing is launched by a refused call.  d in {40, 64, 80}. */
+    const unsigned* k_cls; const unsigned* q_cls;
     /* operand planes in (Qp set) only, appended to ABI 4; all null = the launch above.  Attention over GATHERED token rows:
      * q_idx int32 [N]: query slot i reads row q_idx[i] of Q and its output goes to that same row of Out / OutP (rows not listed
      * are not written); k_idx int32 [L]: key slot j is row k_idx[j] of K and of V.  N and L are the LIST lengths; every index
@@ -336,6 +345,23 @@ typedef struct IefAttnF32Params {
     const int* q_idx; const int* k_idx; const int* gate;
 } IefAttnF32Params;
 int ief_attn_flash_f32(const IefAttnF32Params* p, void* stream);
+/* MasaCtrl's masks from cross-attention (masactrl/model/attention_control.py, MutualSelfAttentionControlMaskAuto), two launches.
+ * ief_cross_token_mass_f32: out[r][n] = (1 / heads) sum_h sum_l w[r][l] softmax_l(scale q_h[rows[r]][n] . k_h[rows[r]][l]) for
+ * r = 0, 1 -- the head-mean cross-attention map of batch row rows[r], summed over prompt tokens with the multiplicities w[r][l]
+ * (fp32 [2][L]); q [B][N][heads*d] (row stride ldq, batch stride sQb), k likewise over L <= 128 keys; out fp32 [2][N], every
+ * element written once, nothing accumulated.  Plain fp32 arithmetic in a fixed order; d any multiple of 8.  q, k 16-byte
+ * aligned with strides that are multiples of 4 floats, w / out 4-byte aligned: IEF_EALIGN otherwise; a null pointer IEF_EINVAL;
+ * L > 128, heads > 64, d % 8 != 0 or a non-positive size IEF_ESHAPE.  Nothing is launched by a refused call.
+ * ief_masa_auto_classes: slots fp32 [c][2][256] (what c calls of the above wrote for the 16 x 16 level) -> class bits of a layer
+ * of res x res tokens: img = (slot 0 + slot 1 + ... in slot order) / c, per row (img - min) / (max - min), token (y, x) reads
+ * pixel (floor(16 y / res), floor(16 x / res)) and its bit is (value >= *thres); k_cls from row 0, q_cls from row 1, one
+ * uint32 per 32 consecutive tokens (res * res / 32 words each; 1 <= res <= 256 with res * res a multiple of 32 and 1 <= c, else IEF_ESHAPE).  A row with
+ * max == min (NaN in the reference) makes EVERY token of both rows background.  thres: device fp32; gate: optional device
+ * int32, *gate == 0 writes nothing.  One workgroup. */
+int ief_cross_token_mass_f32(const float* q, const float* k, const float* w, float* out, int row_ref, int row_cur, int heads,
+                             int N, int L, int d, int ldq, int ldk, long long sQb, long long sKb, float scale, void* stream);
+int ief_masa_auto_classes(const float* slots, int c, const float* thres, int res, unsigned* k_cls, unsigned* q_cls,
+                          const int* gate, void* stream);
 /* fp32 elements of IefAttnF32Params.ws that the launch needs after clamping key_splits; 0 when it would not split */
 long long ief_attn_flash_ws_floats(int B, int heads, int N, int L, int d, int key_splits);
 int ief_softmax_rows_f32(float* x, long long rows, int L, void* stream);
