@@ -502,10 +502,12 @@ extern "C" int ief_conv_out_bwd_f32(const float* d_eps, const ief_half* w, ief_h
 
 // ---------------------------------------------------------------------------------------------------
 // NTI objective and its gradient w.r.t. eps_u, normalised to max |.| = grad_scale for the fp16 backward pass
-__global__ __launch_bounds__(1024) void nti_loss_grad_kernel(const float* __restrict__ eu, const float* __restrict__ ec,
-                                                             const float* __restrict__ x, const float* __restrict__ target,
-                                                             const float* __restrict__ coef, float* __restrict__ d_eps,
-                                                             float* __restrict__ stats, int n, float grad_scale) {
+// One workgroup of 1024 threads does one image: the single-image kernel and the batched one (one workgroup per image) share
+// this body, so an image's d_eps and stats do not depend on which of the two launched it.
+__device__ __forceinline__ void nti_loss_grad_body(const float* __restrict__ eu, const float* __restrict__ ec,
+                                                   const float* __restrict__ x, const float* __restrict__ target,
+                                                   const float* __restrict__ coef, float* __restrict__ d_eps,
+                                                   float* __restrict__ stats, int n, float grad_scale) {
     // same operation order as cfg_ddim_kernel (elementwise.hip): x0 = (x - sqrt(1-a_f) e) / sqrt(a_f); rec = sqrt(a_t) x0 + sqrt(1-a_t) e
     const float a_f = coef[0], a_t = coef[1], g = coef[2];
     const float sb_f = sqrtf(1.0f - a_f), sa_f = sqrtf(a_f), sa_t = sqrtf(a_t), sb_t = sqrtf(1.0f - a_t);
@@ -538,6 +540,22 @@ __global__ __launch_bounds__(1024) void nti_loss_grad_kernel(const float* __rest
     }
 }
 
+__global__ __launch_bounds__(1024) void nti_loss_grad_kernel(const float* __restrict__ eu, const float* __restrict__ ec,
+                                                             const float* __restrict__ x, const float* __restrict__ target,
+                                                             const float* __restrict__ coef, float* __restrict__ d_eps,
+                                                             float* __restrict__ stats, int n, float grad_scale) {
+    nti_loss_grad_body(eu, ec, x, target, coef, d_eps, stats, n, grad_scale);
+}
+
+// K images [K][n] at one DDIM timestep (one coef): workgroup k does image k, stats [K][2]
+__global__ __launch_bounds__(1024) void nti_loss_grad_batched_kernel(const float* __restrict__ eu, const float* __restrict__ ec,
+                                                                     const float* __restrict__ x, const float* __restrict__ target,
+                                                                     const float* __restrict__ coef, float* __restrict__ d_eps,
+                                                                     float* __restrict__ stats, int n, float grad_scale) {
+    const long long o = (long long)blockIdx.x * n;
+    nti_loss_grad_body(eu + o, ec + o, x + o, target + o, coef, d_eps + o, stats + 2 * blockIdx.x, n, grad_scale);
+}
+
 extern "C" int ief_nti_loss_grad_f32(const float* eps_u, const float* eps_c, const float* x, const float* target,
                                      const float* coef, float* d_eps, float* stats, int n, float grad_scale, void* stream) {
     if (!eps_u || !eps_c || !x || !target || !coef || !d_eps || !stats) return IEF_EINVAL;
@@ -548,11 +566,27 @@ extern "C" int ief_nti_loss_grad_f32(const float* eps_u, const float* eps_c, con
     return IEF_OK;
 }
 
+static inline bool misaligned(const void* p, unsigned a) { return ((unsigned long long)p & (a - 1)) != 0; }
+
+extern "C" int ief_nti_loss_grad_batched_f32(const float* eps_u, const float* eps_c, const float* x, const float* target,
+                                             const float* coef, float* d_eps, float* stats, int n, int K, float grad_scale,
+                                             void* stream) {
+    if (!eps_u || !eps_c || !x || !target || !coef || !d_eps || !stats) return IEF_EINVAL;
+    if (n <= 0 || n > (1 << 20) || K < 1 || K > 65535 || !(grad_scale > 0.f)) return IEF_ESHAPE;
+    if (misaligned(eps_u, 4) || misaligned(eps_c, 4) || misaligned(x, 4) || misaligned(target, 4) || misaligned(coef, 4) ||
+        misaligned(d_eps, 4) || misaligned(stats, 4))
+        return IEF_EALIGN;
+    hipLaunchKernelGGL(nti_loss_grad_batched_kernel, dim3(K), dim3(1024), 0, (hipStream_t)stream, eps_u, eps_c, x, target, coef,
+                       d_eps, stats, n, grad_scale);
+    IEF_LAUNCH_CHECK();
+    return IEF_OK;
+}
+
 // torch.optim.Adam (single-tensor form, no weight decay / amsgrad), t = step[0] + 1
-__global__ __launch_bounds__(256) void nti_adam_kernel(float* __restrict__ param, float* __restrict__ m, float* __restrict__ v,
-                                                       const half_t* __restrict__ grad16, const float* __restrict__ stats,
-                                                       const float* __restrict__ hyper, const int* __restrict__ step,
-                                                       half_t* __restrict__ param16, int n) {
+__device__ __forceinline__ void nti_adam_rows(float* __restrict__ param, float* __restrict__ m, float* __restrict__ v,
+                                              const half_t* __restrict__ grad16, const float* __restrict__ stats,
+                                              const float* __restrict__ hyper, const int* __restrict__ step,
+                                              half_t* __restrict__ param16, int n) {
     const float lr = hyper[0], b1 = hyper[1], b2 = hyper[2], eps = hyper[3];
     const float t = (float)(step[0] + 1);
     const float bc1 = 1.0f - powf(b1, t), bc2 = 1.0f - powf(b2, t);
@@ -569,6 +603,24 @@ __global__ __launch_bounds__(256) void nti_adam_kernel(float* __restrict__ param
         param16[i] = (half_t)pn;
     }
 }
+__global__ __launch_bounds__(256) void nti_adam_kernel(float* __restrict__ param, float* __restrict__ m, float* __restrict__ v,
+                                                       const half_t* __restrict__ grad16, const float* __restrict__ stats,
+                                                       const float* __restrict__ hyper, const int* __restrict__ step,
+                                                       half_t* __restrict__ param16, int n) {
+    nti_adam_rows(param, m, v, grad16, stats, hyper, step, param16, n);
+}
+// K parameters [K][n] with one Adam state each and ONE step counter: grid (blocks, K); image k scales its gradient by its own
+// stats[k][1]; an image with active[k] == 0 is left exactly as it is (param, m, v, param16 unwritten)
+__global__ __launch_bounds__(256) void nti_adam_batched_kernel(float* __restrict__ param, float* __restrict__ m,
+                                                               float* __restrict__ v, const half_t* __restrict__ grad16,
+                                                               const float* __restrict__ stats, const int* __restrict__ active,
+                                                               const float* __restrict__ hyper, const int* __restrict__ step,
+                                                               half_t* __restrict__ param16, int n) {
+    const int k = blockIdx.y;
+    if (active[k] == 0) return;
+    const long long o = (long long)k * n;
+    nti_adam_rows(param + o, m + o, v + o, grad16 + o, stats + 2 * k, hyper, step, param16 + o, n);
+}
 __global__ void nti_step_inc_kernel(int* step) { step[0] += 1; }
 
 extern "C" int ief_nti_adam_f32(float* param, float* m, float* v, const ief_half* grad16, const float* stats,
@@ -577,6 +629,22 @@ extern "C" int ief_nti_adam_f32(float* param, float* m, float* v, const ief_half
     if (n <= 0) return IEF_ESHAPE;
     hipLaunchKernelGGL(nti_adam_kernel, dim3(ew_grid(n)), dim3(256), 0, (hipStream_t)stream, param, m, v, grad16, stats, hyper,
                        step, param16, n);
+    IEF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(nti_step_inc_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, step);
+    IEF_LAUNCH_CHECK();
+    return IEF_OK;
+}
+
+extern "C" int ief_nti_adam_batched_f32(float* param, float* m, float* v, const ief_half* grad16, const float* stats,
+                                        const int* active, const float* hyper, int* step, ief_half* param16, int n, int K,
+                                        void* stream) {
+    if (!param || !m || !v || !grad16 || !stats || !active || !hyper || !step || !param16) return IEF_EINVAL;
+    if (n <= 0 || K < 1 || K > 65535) return IEF_ESHAPE;
+    if (misaligned(param, 4) || misaligned(m, 4) || misaligned(v, 4) || misaligned(stats, 4) || misaligned(active, 4) ||
+        misaligned(hyper, 4) || misaligned(step, 4) || misaligned(grad16, 2) || misaligned(param16, 2))
+        return IEF_EALIGN;
+    hipLaunchKernelGGL(nti_adam_batched_kernel, dim3(ew_grid(n), K), dim3(256), 0, (hipStream_t)stream, param, m, v,
+                       (const half_t*)grad16, stats, active, hyper, step, (half_t*)param16, n);
     IEF_LAUNCH_CHECK();
     hipLaunchKernelGGL(nti_step_inc_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, step);
     IEF_LAUNCH_CHECK();

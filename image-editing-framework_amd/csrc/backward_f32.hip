@@ -326,9 +326,9 @@ extern "C" int ief_map_loss_rows_f32(const float* P, const float* ref, float* dP
 
 // ---------------------------------------------------------------------------------------------------
 // torch.optim.Adam (single-tensor form, no weight decay / amsgrad) on an fp32 gradient; g = grad * stats[1]; t = step[0] + 1
-__global__ __launch_bounds__(256) void nti_adam_f32g_kernel(float* __restrict__ param, float* __restrict__ m, float* __restrict__ v,
-                                                            const float* __restrict__ grad, const float* __restrict__ stats,
-                                                            const float* __restrict__ hyper, const int* __restrict__ step, int n) {
+__device__ __forceinline__ void nti_adam_f32g_rows(float* __restrict__ param, float* __restrict__ m, float* __restrict__ v,
+                                                   const float* __restrict__ grad, const float* __restrict__ stats,
+                                                   const float* __restrict__ hyper, const int* __restrict__ step, int n) {
     const float lr = hyper[0], b1 = hyper[1], b2 = hyper[2], eps = hyper[3];
     const float t = (float)(step[0] + 1);
     const float bc1 = 1.0f - powf(b1, t), bc2 = 1.0f - powf(b2, t);
@@ -343,6 +343,22 @@ __global__ __launch_bounds__(256) void nti_adam_f32g_kernel(float* __restrict__ 
         param[i] = param[i] - step_size * (mi / denom);
     }
 }
+__global__ __launch_bounds__(256) void nti_adam_f32g_kernel(float* __restrict__ param, float* __restrict__ m, float* __restrict__ v,
+                                                            const float* __restrict__ grad, const float* __restrict__ stats,
+                                                            const float* __restrict__ hyper, const int* __restrict__ step, int n) {
+    nti_adam_f32g_rows(param, m, v, grad, stats, hyper, step, n);
+}
+// K parameters [K][n], one step counter: grid (blocks, K); image k uses stats[k][1]; active[k] == 0 leaves image k unwritten
+__global__ __launch_bounds__(256) void nti_adam_batched_f32g_kernel(float* __restrict__ param, float* __restrict__ m,
+                                                                    float* __restrict__ v, const float* __restrict__ grad,
+                                                                    const float* __restrict__ stats, const int* __restrict__ active,
+                                                                    const float* __restrict__ hyper, const int* __restrict__ step,
+                                                                    int n) {
+    const int k = blockIdx.y;
+    if (active[k] == 0) return;
+    const long long o = (long long)k * n;
+    nti_adam_f32g_rows(param + o, m + o, v + o, grad + o, stats + 2 * k, hyper, step, n);
+}
 __global__ void nti_step_inc_f32g_kernel(int* step) { step[0] += 1; }
 extern "C" int ief_nti_adam_f32g(float* param, float* m, float* v, const float* grad, const float* stats, const float* hyper,
                                  int* step, int n, void* stream) {
@@ -350,6 +366,20 @@ extern "C" int ief_nti_adam_f32g(float* param, float* m, float* v, const float* 
     if (n <= 0) return IEF_ESHAPE;
     hipLaunchKernelGGL(nti_adam_f32g_kernel, dim3(ewf_grid(n)), dim3(256), 0, (hipStream_t)stream, param, m, v, grad, stats, hyper,
                        step, n);
+    IEF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(nti_step_inc_f32g_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, step);
+    IEF_LAUNCH_CHECK();
+    return IEF_OK;
+}
+extern "C" int ief_nti_adam_batched_f32g(float* param, float* m, float* v, const float* grad, const float* stats, const int* active,
+                                         const float* hyper, int* step, int n, int K, void* stream) {
+    if (!param || !m || !v || !grad || !stats || !active || !hyper || !step) return IEF_EINVAL;
+    if (n <= 0 || K < 1 || K > 65535) return IEF_ESHAPE;
+    if ((((unsigned long long)param | (unsigned long long)m | (unsigned long long)v | (unsigned long long)grad |
+          (unsigned long long)stats | (unsigned long long)active | (unsigned long long)hyper | (unsigned long long)step) & 3) != 0)
+        return IEF_EALIGN;
+    hipLaunchKernelGGL(nti_adam_batched_f32g_kernel, dim3(ewf_grid(n), K), dim3(256), 0, (hipStream_t)stream, param, m, v, grad,
+                       stats, active, hyper, step, n);
     IEF_LAUNCH_CHECK();
     hipLaunchKernelGGL(nti_step_inc_f32g_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, step);
     IEF_LAUNCH_CHECK();

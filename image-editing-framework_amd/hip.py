@@ -177,6 +177,8 @@ EXPORTS = [
     "ief_conv_in_f32act_planes", "ief_repeat_batch",
     # MasaCtrl's masks from cross-attention (csrc/masa_auto.hip)
     "ief_cross_token_mass_f32", "ief_masa_auto_classes",
+    # null-text optimisation of K images in one UNet batch (nti.BatchedNullTextOptimizer)
+    "ief_nti_loss_grad_batched_f32", "ief_nti_adam_batched_f32", "ief_nti_adam_batched_f32g",
 ]
 
 
@@ -307,6 +309,9 @@ def load():
     lib.ief_layernorm_x3p.argtypes = [c_void_p, c_void_p, c_longlong, c_void_p, c_void_p, c_longlong, c_int, c_float, c_void_p]
     lib.ief_cross_token_mass_f32.argtypes = [c_void_p] * 4 + [c_int] * 8 + [c_longlong, c_longlong, c_float, c_void_p]
     lib.ief_masa_auto_classes.argtypes = [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.ief_nti_loss_grad_batched_f32.argtypes = [c_void_p] * 7 + [c_int, c_int, c_float, c_void_p]
+    lib.ief_nti_adam_batched_f32.argtypes = [c_void_p] * 9 + [c_int, c_int, c_void_p]
+    lib.ief_nti_adam_batched_f32g.argtypes = [c_void_p] * 8 + [c_int, c_int, c_void_p]
     if lib.ief_abi_version() != ABI_VERSION:
         raise HipExtensionMissing("libief_hip.so ABI version mismatch; rebuild")
     lib.ief_struct_size.argtypes = [c_int]
@@ -2411,3 +2416,47 @@ def nti_adam(param, m, v, grad16, stats, hyper, step, param16):
         raise ValueError("nti_adam: shape mismatch")
     _check(lib.ief_nti_adam_f32(param.data_ptr(), m.data_ptr(), v.data_ptr(), grad16.data_ptr(), stats.data_ptr(),
                                 hyper.data_ptr(), step.data_ptr(), param16.data_ptr(), n, _stream()), "ief_nti_adam_f32")
+
+
+def nti_loss_grad_batched(eps_u, eps_c, x, target, coef, d_eps, stats, grad_scale=1.0):
+    """`nti_loss_grad` for K images [K, ...] at one timestep (one `coef`): stats fp32 [K, 2] <- (loss, factor) per image;
+    image k's d_eps and stats are bit-identical to `nti_loss_grad` on its slice."""
+    lib = load()
+    for t, nm in ((eps_u, "eps_u"), (eps_c, "eps_c"), (x, "x"), (target, "target"), (coef, "coef"), (d_eps, "d_eps"),
+                  (stats, "stats")):
+        _dev32(t, nm)
+    K = eps_u.shape[0] if eps_u.dim() >= 2 else 0
+    total = eps_u.numel()
+    if K < 1 or any(t.numel() != total for t in (eps_c, x, target, d_eps)) or coef.numel() < 3 or tuple(stats.shape) != (K, 2):
+        raise ValueError("nti_loss_grad_batched: operands must be [K, ...] of one shape, coef [>= 3], stats [K, 2]")
+    _check(lib.ief_nti_loss_grad_batched_f32(eps_u.data_ptr(), eps_c.data_ptr(), x.data_ptr(), target.data_ptr(),
+                                             coef.data_ptr(), d_eps.data_ptr(), stats.data_ptr(), total // K, K, grad_scale,
+                                             _stream()), "ief_nti_loss_grad_batched_f32")
+
+
+def nti_adam_batched(param, m, v, grad, stats, active, hyper, step, param16):
+    """`nti_adam` for K parameters [K, ...] with one Adam state each, shared `hyper` and `step` (advanced once): image k
+    takes g = grad[k] * stats[k, 1]; active int32 [K], an image with active[k] == 0 is left unwritten.  fp16 `grad` writes
+    the fp16 copy `param16` too; an fp32 `grad` (fp32-storage modes) does not look at it."""
+    lib = load()
+    for t, nm in ((param, "param"), (m, "m"), (v, "v"), (stats, "stats"), (hyper, "hyper")):
+        _dev32(t, nm)
+    _devi32(step, "step"), _devi32(active, "active")
+    K = param.shape[0] if param.dim() >= 2 else 0
+    total = param.numel()
+    if step is None or active is None:
+        raise TypeError("nti_adam_batched: step and active are required")
+    if K < 1 or any(t.numel() != total for t in (m, v, grad)) or tuple(stats.shape) != (K, 2) or active.numel() != K \
+            or hyper.numel() < 4 or not grad.is_contiguous():
+        raise ValueError("nti_adam_batched: param / m / v / grad must be [K, ...] of one shape, stats [K, 2], active [K]")
+    if _is32(grad):
+        _check(lib.ief_nti_adam_batched_f32g(param.data_ptr(), m.data_ptr(), v.data_ptr(), _act32(grad, "grad").data_ptr(),
+                                             stats.data_ptr(), active.data_ptr(), hyper.data_ptr(), step.data_ptr(), total // K,
+                                             K, _stream()), "ief_nti_adam_batched_f32g")
+        return
+    _dev16(grad, "grad"), _dev16(param16, "param16")
+    if param16.numel() != total or not param16.is_contiguous():
+        raise ValueError("nti_adam_batched: param16 shape mismatch")
+    _check(lib.ief_nti_adam_batched_f32(param.data_ptr(), m.data_ptr(), v.data_ptr(), grad.data_ptr(), stats.data_ptr(),
+                                        active.data_ptr(), hyper.data_ptr(), step.data_ptr(), param16.data_ptr(), total // K, K,
+                                        _stream()), "ief_nti_adam_batched_f32")

@@ -7,7 +7,7 @@ activation-gradient pass -> Adam) and reads the loss back for the reference's ea
 The numerics of the loop are pinned in the oracle against the reference (`oracle/p2p_ref.py:
 null_optimization`, fixture G8); `tests/test_gpu_grad.py` holds this class to that oracle.
 """
-from ...nti import NullTextOptimizer, run_many
+from ...nti import BatchedNullTextOptimizer, NullTextOptimizer, groups_of, run_many
 from .ddim import ddim_inversion, ddim_inversion_xl
 
 
@@ -38,6 +38,40 @@ class NTI(ddim_inversion):
                 o.release()
         self.inner_steps_run = [o.inner_steps_run for o in opts]
         return outs
+
+    _batched, _batched_key = None, None
+
+    def null_optimization_batched(self, model, latents_list, contexts, num_inner_steps, epsilon, guidance_scale, batch=None):
+        """`null_optimization` for several independent images through ONE UNet batch (`ief_amd.nti.BatchedNullTextOptimizer`):
+        the images run in groups of `batch` (default: all of them in one group; a smaller last group is padded), every image
+        with its own early stop.  Returns what `null_optimization_many` returns: per image the list of [1,77,C]; sets
+        `inner_steps_run[k]`, the Adam steps image k took per timestep.  The optimiser and its three graphs are kept for the
+        next call with the same model, batch, latent size and guidance scale (a driver's next groups) until
+        `release_batched()`.  SDXL pipelines are not served (`NTI_XL.null_optimization_many`)."""
+        K = int(batch or len(latents_list))
+        hw = tuple(latents_list[0][-1].shape[-2:])
+        # what the kept optimiser's buffers, tables and graphs were built for (the model itself is held and compared by identity)
+        key = (K, hw, float(guidance_scale), tuple(model.scheduler.timesteps.tolist()), model.unet.precision)
+        if self._batched is None or self._batched.model is not model or self._batched_key != key:
+            self.release_batched()
+            self._batched = BatchedNullTextOptimizer(model, contexts[0].chunk(2)[1], guidance_scale, hw, K)
+            self._batched_key = key
+        opt, outs, steps = self._batched, [], []
+        try:
+            for part in groups_of(len(latents_list), K):
+                ctx = [contexts[j].chunk(2) for j in part]
+                outs += opt.run([latents_list[j] for j in part], [u for u, _ in ctx], num_inner_steps, epsilon,
+                                cond=[c for _, c in ctx])
+                steps += opt.inner_steps_run
+        finally:
+            opt.suspend()
+        self.inner_steps_run = steps
+        return outs
+
+    def release_batched(self):
+        if self._batched is not None:
+            self._batched.release()
+        self._batched, self._batched_key = None, None
 
 
 class NTI_XL(ddim_inversion_xl):

@@ -17,6 +17,9 @@ by one: at batch 1 the UNet is bound by per-kernel latency, so K = 4 nearly quar
 `--in_flight E` keeps E images in flight on the GPU, for the edits (`P2P.edit_many`) and for the null-text
 optimisations (`NTI.null_optimization_many`): a step is hundreds of dependent launches, and E independent chains fill
 each other's dispatch gaps.  Both change the schedule, not the results.
+`--nti_batch K` (with `--inversion_type null-text`) runs the null-text optimisations of a shard in groups of K through ONE
+UNet batch (`NTI.null_optimization_batched`: one optimiser and three graphs for the whole run, every image with its own
+early stop) instead of `--in_flight` chains at batch 1; `--in_flight` keeps governing the edits.  Not for SDXL pipelines.
 """
 import argparse
 import json
@@ -48,73 +51,85 @@ def edit_type_of(source_prompt: str, target_prompt: str) -> str:
     return "replace" if len(source_prompt.split(" ")) == len(target_prompt.split(" ")) else "refine"
 
 
-def run_items(pipe, editor, invertor, items, size, device, inversion_type="ddim", invert_batch=1, in_flight=1, save=None):
+def run_items(pipe, editor, invertor, items, size, device, inversion_type="ddim", invert_batch=1, in_flight=1, save=None,
+              nti_batch=1):
     """the per-image loop of `/root/reference/p2p/test.py:116-181` over `items` = [(image path, source prompt, target
     prompt)]; `save(image_path, original PIL image, uint8 images [2,H,W,3])` is called per image.  invert_batch /
     in_flight = 1 is the reference's order (invert one image, edit it, next); see the module docstring for the others.
+    nti_batch > 1: the null-text optimisations run in groups of nti_batch through one batched optimiser.
     Also what `bench.py` times for its images/sec figures."""
     save = save or (lambda *a: None)
     nti = inversion_type == "null-text"
     bs = max(1, invert_batch)
     E = max(1, in_flight)
-    group = max(bs, E)
-    for c0 in range(0, len(items), group):
-        chunk = items[c0:c0 + group]
-        originals = [Image.open(path).convert("RGB").resize((size, size)) for path, _, _ in chunk]
-        if group == 1:
-            image_path, source_prompt, target_prompt = chunk[0]
-            images = edit_one(pipe, editor, invertor, originals[0], [source_prompt], [target_prompt], inversion_type,
-                              edit_type_of(source_prompt, target_prompt), device)
-            save(image_path, originals[0], images)
-            continue
-        # inversion: batched over `bs` images at a time (the DDIM loop is the same for both inversion types)
-        traj, ctxs = [], []
-        for b0 in range(0, len(chunk), bs):
-            latent = torch.cat([invertor.image2latent(model=pipe, image=im, device=device, dtype=torch.float32)
-                                for im in originals[b0:b0 + bs]])
-            latents, context = invertor.ddim_inversion_loop(pipe, latent, [src for _, src, _ in chunk[b0:b0 + bs]])
-            k = latent.shape[0]
-            for j in range(k):
-                traj.append([t[j:j + 1].clone() for t in latents])
-                if isinstance(context, tuple):       # SDXL family: (prompt, negative, pooled, negative pooled) embeddings
-                    ctxs.append(tuple(t[j:j + 1] for t in context))
-                else:
-                    unc, cnd = context.chunk(2)
-                    ctxs.append(torch.cat([unc[j:j + 1], cnd[j:j + 1]]))
-        x_T = [t[-1] for t in traj]
-        # null-text optimisation: E images in flight
-        uncond = [None] * len(chunk)
-        if nti:
+    nb = max(1, nti_batch) if nti else 1
+    group = max(bs, E, nb)
+    try:
+        for c0 in range(0, len(items), group):
+            chunk = items[c0:c0 + group]
+            originals = [Image.open(path).convert("RGB").resize((size, size)) for path, _, _ in chunk]
+            if group == 1:
+                image_path, source_prompt, target_prompt = chunk[0]
+                images = edit_one(pipe, editor, invertor, originals[0], [source_prompt], [target_prompt], inversion_type,
+                                  edit_type_of(source_prompt, target_prompt), device)
+                save(image_path, originals[0], images)
+                continue
+            # inversion: batched over `bs` images at a time (the DDIM loop is the same for both inversion types)
+            traj, ctxs = [], []
+            for b0 in range(0, len(chunk), bs):
+                latent = torch.cat([invertor.image2latent(model=pipe, image=im, device=device, dtype=torch.float32)
+                                    for im in originals[b0:b0 + bs]])
+                latents, context = invertor.ddim_inversion_loop(pipe, latent, [src for _, src, _ in chunk[b0:b0 + bs]])
+                k = latent.shape[0]
+                for j in range(k):
+                    traj.append([t[j:j + 1].clone() for t in latents])
+                    if isinstance(context, tuple):       # SDXL family: (prompt, negative, pooled, negative pooled) embeddings
+                        ctxs.append(tuple(t[j:j + 1] for t in context))
+                    else:
+                        unc, cnd = context.chunk(2)
+                        ctxs.append(torch.cat([unc[j:j + 1], cnd[j:j + 1]]))
+            x_T = [t[-1] for t in traj]
+            # null-text optimisation: E images in flight
+            uncond = [None] * len(chunk)
+            if nti and nb > 1:
+                uncond = invertor.null_optimization_batched(pipe, traj, ctxs, 10, 1e-5, 7.5, batch=nb)
+            elif nti:
+                for e0 in range(0, len(chunk), E):
+                    part = list(range(e0, min(e0 + E, len(chunk))))
+                    outs = invertor.null_optimization_many(pipe, [traj[j] for j in part], [ctxs[j] for j in part], 10, 1e-5, 7.5)
+                    for j, o in zip(part, outs):
+                        uncond[j] = o
+            # edits: E in flight
             for e0 in range(0, len(chunk), E):
                 part = list(range(e0, min(e0 + E, len(chunk))))
-                outs = invertor.null_optimization_many(pipe, [traj[j] for j in part], [ctxs[j] for j in part], 10, 1e-5, 7.5)
-                for j, o in zip(part, outs):
-                    uncond[j] = o
-        # edits: E in flight
-        for e0 in range(0, len(chunk), E):
-            part = list(range(e0, min(e0 + E, len(chunk))))
-            if len(part) == 1:
-                j = part[0]
-                _, src, tgt = chunk[j]
-                extra = {"uncond_embeddings_list": uncond[j]} if nti else None
-                results = [edit_latent(pipe, editor, x_T[j], [src], [tgt], edit_type_of(src, tgt), device, extra)]
-            else:
-                jobs, ctrls = [], []
-                for j in part:
+                if len(part) == 1:
+                    j = part[0]
                     _, src, tgt = chunk[j]
-                    cls = AttentionReplace if edit_type_of(src, tgt) == "replace" else AttentionRefine
-                    ctrl = cls(prompts=[src, tgt], tokenizer=pipe.tokenizer, num_steps=50, cross_replace_steps=0.8,
-                               self_replace_steps=0.6, device=device)
-                    ctrls.append(ctrl)
-                    jobs.append(([src, tgt], ctrl, x_T[j]) + ((uncond[j],) if nti else ()))
-                results = [im for im, _ in editor.edit_many(pipe, jobs, num_inference_steps=50, guidance_scale=7.5)]
-                for ctrl in ctrls:
-                    ctrl.reset()
-            for j, images in zip(part, results):
-                save(chunk[j][0], originals[j], images)
+                    extra = {"uncond_embeddings_list": uncond[j]} if nti else None
+                    results = [edit_latent(pipe, editor, x_T[j], [src], [tgt], edit_type_of(src, tgt), device, extra)]
+                else:
+                    jobs, ctrls = [], []
+                    for j in part:
+                        _, src, tgt = chunk[j]
+                        cls = AttentionReplace if edit_type_of(src, tgt) == "replace" else AttentionRefine
+                        ctrl = cls(prompts=[src, tgt], tokenizer=pipe.tokenizer, num_steps=50, cross_replace_steps=0.8,
+                                   self_replace_steps=0.6, device=device)
+                        ctrls.append(ctrl)
+                        jobs.append(([src, tgt], ctrl, x_T[j]) + ((uncond[j],) if nti else ()))
+                    results = [im for im, _ in editor.edit_many(pipe, jobs, num_inference_steps=50, guidance_scale=7.5)]
+                    for ctrl in ctrls:
+                        ctrl.reset()
+                for j, images in zip(part, results):
+                    save(chunk[j][0], originals[j], images)
+    finally:
+        if nb > 1:
+            invertor.release_batched()          # the optimiser that served every group of this run
 
 
-def main(argv=None):
+XL_VERSIONS = ("xl-base", "smallxl")       # the `StableDiffusionXLPipeline` branch of `_bootstrap._build_pipe`
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser("PIE-Bench P2P")
     ap.add_argument("--sd_version", type=str, default="1.5")
     ap.add_argument("--dataset_path", type=str, default="./PIE")
@@ -131,7 +146,19 @@ def main(argv=None):
                          "on batch-1 inversion steps); unset: the IEF_X3P_KEY_SPLITS environment variable, else 1")
     ap.add_argument("--in_flight", type=int, default=1,
                     help="independent images stepped concurrently on one GPU (null-text optimisations and edits)")
+    ap.add_argument("--nti_batch", type=int, default=1,
+                    help="null-text optimisations per UNet batch (1: per image, --in_flight of them at a time); not for SDXL")
     args = ap.parse_args(argv)
+    if args.nti_batch < 1:
+        ap.error("--nti_batch must be >= 1")
+    if args.nti_batch > 1 and args.sd_version in XL_VERSIONS:
+        ap.error("--nti_batch: the SDXL null-text optimiser restarts per timestep with per-image added conditions and is not "
+                 "batched; use --in_flight")
+    return args
+
+
+def main(argv=None):
+    args = parse_args(argv)
 
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -178,7 +205,7 @@ def main(argv=None):
             writer.save_img(images[1], os.path.join(out_path, "edit.png"))
 
         run_items(pipe, editor, invertor, [items[i] for i in mine], size, device, args.inversion_type, args.invert_batch,
-                  args.in_flight, save)
+                  args.in_flight, save, nti_batch=args.nti_batch)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     n = torch.tensor([float(len(mine)), dt], device=device)

@@ -627,6 +627,20 @@ int ief_nti_loss_grad_f32(const float* eps_u, const float* eps_c, const float* x
  * (incremented here), hyper: DEVICE fp32 {lr, beta1, beta2, eps}; also writes the fp16 copy the next forward reads. */
 int ief_nti_adam_f32(float* param, float* m, float* v, const ief_half* grad16, const float* stats, const float* hyper,
                      int* step, ief_half* param16, int n, void* stream);
+/* K images at ONE DDIM timestep through the same three steps (`nti.BatchedNullTextOptimizer`): coef, hyper and the step counter
+ * are shared, everything else is [K][n] with n elements PER IMAGE.
+ * ief_nti_loss_grad_batched_f32: one workgroup per image runs the body of ief_nti_loss_grad_f32 on image k's slice and writes
+ * stats[k][0..1]; image k's d_eps and stats are bit-identical to the single-image call on that slice.  n <= 2^20, K >= 1.
+ * ief_nti_adam_batched_f32 (fp16 gradient, also writes param16) / ief_nti_adam_batched_f32g (fp32 gradient): image k's Adam
+ * step with g = grad[k] * stats[k][1]; active int32 [K]: an image with active[k] == 0 is not touched (param, m, v, param16
+ * unwritten).  step[0] += 1 once per call.  A null pointer is IEF_EINVAL, a non-positive size or K > 65535 IEF_ESHAPE, a pointer
+ * that is not aligned to its element IEF_EALIGN; nothing is launched by a refused call. */
+int ief_nti_loss_grad_batched_f32(const float* eps_u, const float* eps_c, const float* x, const float* target, const float* coef,
+                                  float* d_eps, float* stats, int n, int K, float grad_scale, void* stream);
+int ief_nti_adam_batched_f32(float* param, float* m, float* v, const ief_half* grad16, const float* stats, const int* active,
+                             const float* hyper, int* step, ief_half* param16, int n, int K, void* stream);
+int ief_nti_adam_batched_f32g(float* param, float* m, float* v, const float* grad, const float* stats, const int* active,
+                              const float* hyper, int* step, int n, int K, void* stream);
 
 #ifdef __cplusplus
 }
