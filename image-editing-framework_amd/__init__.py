@@ -2,7 +2,8 @@
 
 Layout
   csrc/         hand-written HIP kernels for gfx950 + the C-ABI (`include/ief_hip.h`)
-  hip.py        ctypes binding of that C-ABI (fails loudly when the library is absent)
+  cabi.py       structs, argtypes and constants of that C-ABI, parsed from `include/ief_hip.h` (pure Python, strict)
+  hip.py        ctypes binding of that C-ABI, declared by cabi.py (fails loudly when the library is absent)
   unet.py       diffusers-shaped module tree whose forwards launch the HIP kernels
   scheduler.py  DDIM scheduler with the reference's config
   pipeline.py   duck-typed `StableDiffusionPipeline` the reference's editors expect

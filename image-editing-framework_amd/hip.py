@@ -4,15 +4,21 @@ This is the ONLY route from the host code to compute: every function below launc
 hand-written gfx950 kernel on torch's current HIP stream, with torch tensors used purely as
 device-memory handles (`data_ptr()`).  There is no CPU or eager-PyTorch fallback: if the library
 is missing, or a tensor is not an fp16/fp32 device tensor of the documented layout, the call raises.
+
+Nothing of the ABI is declared here by hand: the parameter structs, every entry point's `restype` /
+`argtypes` and the header's constants are derived from `include/ief_hip.h` by `cabi.py`.
 """
 import ctypes
 import os
-from ctypes import POINTER, Structure, byref, c_char_p, c_float, c_int, c_longlong, c_void_p
+from ctypes import byref
 
 import torch
 
+from . import cabi
+
 # IEF_HIP_LIB / IEF_PLAN_FILE: A/B two builds of the library (and their tuned tables) on one GPU box
-ABI_VERSION = 4   # include/ief_hip.h IEF_ABI_VERSION
+ABI_VERSION = cabi.defines["IEF_ABI_VERSION"]
+REPEAT_MAX_JOBS = cabi.defines["IEF_REPEAT_MAX_JOBS"]
 _LIB_PATH = os.environ.get("IEF_HIP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libief_hip.so")
 _lib = None
 
@@ -21,165 +27,17 @@ class HipExtensionMissing(RuntimeError):
     pass
 
 
-class IefGemmParams(Structure):
-    _fields_ = [
-        ("A", c_void_p), ("A2", c_void_p), ("W", c_void_p), ("Out", c_void_p),
-        ("bias", c_void_p), ("rowvec", c_void_p), ("residual", c_void_p),
-        ("M", c_int), ("N", c_int), ("K", c_int),
-        ("lda", c_int), ("ldw", c_int), ("ldo", c_int), ("ldr", c_int),
-        ("strideA", c_longlong), ("strideW", c_longlong), ("strideO", c_longlong), ("strideR", c_longlong),
-        ("H", c_int), ("Wd", c_int), ("C1", c_int), ("C2", c_int), ("Ho", c_int), ("Wo", c_int),
-        ("stride", c_int), ("ups", c_int), ("batch_images", c_int),
-        ("rows_per_batch", c_int), ("out_scale", c_float), ("tile_hint", c_int),
-        ("E1", c_void_p), ("E2", c_void_p), ("CE1", c_int), ("CE2", c_int),
-        ("splits", c_int), ("ws", c_void_p), ("flags", c_int), ("zeros", c_void_p), ("stages", c_int),
-        ("pad_hi_only", c_int),
-        ("rstat_out", c_void_p), ("rstat_in", c_void_p), ("rstat_slots", c_int), ("colsum", c_void_p), ("ln_eps", c_float),
-        ("cstat_out", c_void_p), ("cnt", c_void_p),
-    ]
-
-
-class IefAttnParams(Structure):
-    _fields_ = [
-        ("Q", c_void_p), ("K", c_void_p), ("V", c_void_p), ("Out", c_void_p),
-        ("B", c_int), ("heads", c_int), ("N", c_int), ("L", c_int), ("d", c_int),
-        ("ldq", c_int), ("ldk", c_int), ("ldv", c_int), ("ldo", c_int),
-        ("scale", c_float),
-        ("q_src", c_void_p), ("k_src", c_void_p), ("v_src", c_void_p), ("lse", c_void_p), ("variant", c_int),
-    ]
-
-
-class IefAttnBwdParams(Structure):
-    _fields_ = [
-        ("Q", c_void_p), ("K", c_void_p), ("V", c_void_p), ("dO", c_void_p), ("lse", c_void_p), ("delta", c_void_p),
-        ("dQ", c_void_p), ("dK", c_void_p), ("dV", c_void_p),
-        ("B", c_int), ("heads", c_int), ("N", c_int), ("L", c_int), ("d", c_int),
-        ("ldq", c_int), ("ldk", c_int), ("ldv", c_int), ("ldo", c_int), ("lddq", c_int), ("lddk", c_int), ("lddv", c_int),
-        ("scale", c_float), ("ds_mul", c_float), ("kv_splits", c_int), ("ws", c_void_p),
-    ]
-
-
-class IefMapLossParams(Structure):
-    _fields_ = [
-        ("Q", c_void_p), ("K", c_void_p), ("ref", c_void_p), ("dQ", c_void_p), ("loss", c_void_p),
-        ("B", c_int), ("heads", c_int), ("N", c_int), ("L", c_int), ("d", c_int),
-        ("ldq", c_int), ("ldk", c_int), ("lddq", c_int),
-        ("scale", c_float), ("gcoef", c_float), ("loss_coef", c_float), ("accumulate", c_int),
-    ]
-
-
-class IefCrossParams(Structure):
-    _fields_ = [
-        ("Q", c_void_p), ("K", c_void_p), ("V", c_void_p), ("Out", c_void_p),
-        ("B", c_int), ("heads", c_int), ("N", c_int), ("L", c_int), ("d", c_int),
-        ("ldq", c_int), ("ldk", c_int), ("ldv", c_int), ("ldo", c_int),
-        ("scale", c_float),
-        ("edit_src", c_void_p), ("edit_slot", c_void_p), ("MT", c_void_p), ("coef", c_void_p),
-    ]
-
-
-class IefGemmF32Params(Structure):
-    _fields_ = [
-        ("A", c_void_p), ("A2", c_void_p), ("W", c_void_p), ("Out", c_void_p),
-        ("bias", c_void_p), ("rowvec", c_void_p), ("residual", c_void_p),
-        ("M", c_int), ("N", c_int), ("K", c_int),
-        ("lda", c_int), ("ldw", c_int), ("ldo", c_int), ("ldr", c_int),
-        ("rows_per_batch", c_int), ("out_scale", c_float),
-        ("conv", c_int), ("H", c_int), ("Wd", c_int), ("C1", c_int), ("C2", c_int), ("Ho", c_int), ("Wo", c_int),
-        ("stride", c_int), ("ups", c_int), ("batch_images", c_int), ("pad_hi_only", c_int),
-        ("E1", c_void_p), ("E2", c_void_p), ("CE1", c_int), ("CE2", c_int),
-        ("batch", c_int), ("heads", c_int),
-        ("sAb", c_longlong), ("sAh", c_longlong), ("sWb", c_longlong), ("sWh", c_longlong), ("sOb", c_longlong), ("sOh", c_longlong),
-        ("a_src", c_void_p), ("w_src", c_void_p), ("transb", c_int), ("a_scalar", c_int),
-        ("splits", c_int), ("ws", c_void_p),
-        ("x3", c_int), ("sa", c_float), ("sb", c_float), ("vec_out", c_int), ("al32", c_int), ("fast_ok", c_int),
-        ("bytesA", ctypes.c_uint), ("bytesW", ctypes.c_uint), ("bytesA2", ctypes.c_uint), ("bytesE1", ctypes.c_uint),
-        ("bytesE2", ctypes.c_uint), ("Wp", c_void_p), ("geglu", c_int),
-    ]
-
-
-class IefAttnF32Params(Structure):
-    _fields_ = [
-        ("Q", c_void_p), ("K", c_void_p), ("V", c_void_p), ("Out", c_void_p),
-        ("B", c_int), ("heads", c_int), ("N", c_int), ("L", c_int), ("d", c_int),
-        ("ldq", c_int), ("ldk", c_int), ("ldv", c_int), ("ldo", c_int),
-        ("sQb", c_longlong), ("sKb", c_longlong), ("sVb", c_longlong), ("sOb", c_longlong),
-        ("scale", c_float),
-        ("q_src", c_void_p), ("k_src", c_void_p), ("v_src", c_void_p),
-        ("x3", c_int),
-        ("OutP", c_void_p), ("planeO", c_longlong), ("sOPb", c_longlong), ("ldp", c_int), ("p_scale", c_float),
-        ("Qp", c_void_p), ("Kp", c_void_p), ("Vp", c_void_p), ("planeQ", c_longlong), ("planeK", c_longlong), ("planeV", c_longlong),
-        ("zeros", c_void_p), ("lse", c_void_p),
-        ("key_splits", c_int), ("ws", c_void_p), ("ws_floats", c_longlong),
-        ("k_cls", c_void_p), ("q_cls", c_void_p),
-        ("q_idx", c_void_p), ("k_idx", c_void_p), ("gate", c_void_p),
-    ]
-
-
-class IefAttnBwdF32Params(Structure):
-    _fields_ = [
-        ("Q", c_void_p), ("K", c_void_p), ("V", c_void_p), ("dO", c_void_p), ("lse", c_void_p), ("delta", c_void_p),
-        ("dQ", c_void_p), ("dK", c_void_p), ("dV", c_void_p),
-        ("B", c_int), ("heads", c_int), ("N", c_int), ("L", c_int), ("d", c_int),
-        ("ldq", c_int), ("ldk", c_int), ("ldv", c_int), ("ldo", c_int), ("lddq", c_int), ("lddk", c_int), ("lddv", c_int),
-        ("scale", c_float), ("ds_mul", c_float),
-    ]
-
-
-class IefRepeatJob(Structure):
-    _fields_ = [("src", c_void_p), ("dst", c_void_p), ("bytes", c_longlong), ("blocks", c_int)]
-
-
-REPEAT_MAX_JOBS = 4   # include/ief_hip.h IEF_REPEAT_MAX_JOBS
-
-
-class IefGemmX3pParams(Structure):
-    _fields_ = [
-        ("A", c_void_p), ("planeA", c_longlong), ("A2", c_void_p), ("planeA2", c_longlong),
-        ("E1", c_void_p), ("planeE1", c_longlong), ("E2", c_void_p), ("planeE2", c_longlong),
-        ("W", c_void_p), ("planeW", c_longlong),
-        ("Out", c_void_p), ("OutP", c_void_p), ("planeO", c_longlong),
-        ("bias", c_void_p), ("rowvec", c_void_p), ("residual", c_void_p),
-        ("M", c_int), ("N", c_int), ("K", c_int),
-        ("lda", c_int), ("ldw", c_int), ("ldo", c_int), ("ldp", c_int), ("ldr", c_int),
-        ("conv", c_int), ("H", c_int), ("Wd", c_int), ("C1", c_int), ("C2", c_int), ("Ho", c_int), ("Wo", c_int),
-        ("stride", c_int), ("ups", c_int), ("batch_images", c_int), ("pad_hi_only", c_int), ("CE1", c_int), ("CE2", c_int),
-        ("rows_per_batch", c_int), ("out_scale", c_float), ("inv_scale", c_float),
-        ("tile", c_int), ("splits", c_int), ("ws", c_void_p), ("geglu", c_int), ("zeros", c_void_p),
-        ("rstat_out", c_void_p), ("cstat_out", c_void_p), ("rstat_in", c_void_p), ("colsum", c_void_p),
-        ("rstat_slots", c_int), ("rstat_cnt", c_int), ("ln_eps", c_float),
-    ]
-
-
-EXPORTS = [
-    "ief_abi_version", "ief_target_arch", "ief_gemm_f16", "ief_conv3x3_f16", "ief_conv_in_f32",
-    "ief_conv_out_f32", "ief_gn_splits", "ief_groupnorm_silu_f16", "ief_layernorm_f16", "ief_geglu_f16",
-    "ief_attn_flash_f16", "ief_attn_cross_p2p_f16", "ief_attn_probs_f16", "ief_attn_apply_f16",
-    "ief_cfg_ddim_step_f32", "ief_timestep_embedding_f16", "ief_silu_f16", "ief_cast_f32_to_f16",
-    "ief_cast_f16_to_f32", "ief_select_step", "ief_advance_step", "ief_add_f16", "ief_struct_size",
-    "ief_softmax_rows_f16", "ief_transpose_f16", "ief_pointwise_f32",
-    "ief_attn_bwd_delta_f32", "ief_attn_bwd_f16", "ief_groupnorm_bwd_f16", "ief_layernorm_bwd_f16", "ief_geglu_il_f16",
-    "ief_geglu_il_bwd_f16", "ief_zero_insert2x_f16", "ief_pool2x2_sum_f16", "ief_conv_out_bwd_f32",
-    "ief_nti_loss_grad_f32", "ief_nti_adam_f32", "ief_gemm_tile_bn", "ief_gather_rows_f16",
-    "ief_attn_map_loss_bwd_f16", "ief_axpy_f32", "ief_map_loss_blocks", "ief_groupnorm_cstat_f16", "ief_gemm_tile_bm",
-    # reference-precision (fp32) mode
-    "ief_gemm_f32", "ief_softmax_rows_f32", "ief_p2p_cross_edit_f32", "ief_attn_cross_p2p_f32", "ief_groupnorm_silu_f32", "ief_layernorm_f32",
-    "ief_add_f32", "ief_silu_f32", "ief_geglu_il_f32", "ief_timestep_embedding_f32", "ief_gather_rows_f32",
-    "ief_conv_in_f32act", "ief_conv_out_f32act", "ief_image_u8", "ief_gemm_f32_bn", "ief_attn_flash_f32", "ief_gemm_x3_bn", "ief_gemm_x3_bm", "ief_gemm_x3_bn_k", "ief_gemm_x3_set_variant", "ief_x3_split_weights", "ief_groupnorm_f32_ws_floats", "ief_groupnorm_silu_f32_ws", "ief_groupnorm_bwd_f32_ws_floats", "ief_groupnorm_bwd_f32_ws",
-    # activation gradients of the fp32-storage modes (csrc/backward_f32.hip)
-    "ief_groupnorm_bwd_f32", "ief_layernorm_bwd_f32", "ief_geglu_il_bwd_f32", "ief_zero_insert2x_f32", "ief_pool2x2_sum_f32",
-    "ief_conv_out_bwd_f32w", "ief_softmax_bwd_rows_f32", "ief_transpose_batched_f32", "ief_map_loss_rows_blocks",
-    "ief_map_loss_rows_f32", "ief_nti_adam_f32g",
-    # ABI 4: split-operand contractions on pre-split planes (csrc/gemm_x3p.hip)
-    "ief_gemm_x3p", "ief_gemm_x3p_tile_bm", "ief_gemm_x3p_tile_bn", "ief_gemm_x3p_tile_wn", "ief_x3_split_act", "ief_groupnorm_silu_x3p_ws", "ief_layernorm_x3p", "ief_groupnorm_silu_x3p_small", "ief_groupnorm_silu_reg", "ief_groupnorm_reg_fits", "ief_attn_bwd_x3", "ief_attn_bwd_delta_f32in",
-    "ief_attn_flash_ws_floats",
-    # CFG step with a shared prefix: conv_in that writes its planes, the batch repeat
-    "ief_conv_in_f32act_planes", "ief_repeat_batch",
-    # MasaCtrl's masks from cross-attention (csrc/masa_auto.hip)
-    "ief_cross_token_mass_f32", "ief_masa_auto_classes",
-    # null-text optimisation of K images in one UNet batch (nti.BatchedNullTextOptimizer)
-    "ief_nti_loss_grad_batched_f32", "ief_nti_adam_batched_f32", "ief_nti_adam_batched_f32g",
-]
+# the parameter blocks callers fill in: the very classes the entry points' POINTER(...) argtypes name
+IefGemmParams = cabi.structs["IefGemmParams"]
+IefAttnParams = cabi.structs["IefAttnParams"]
+IefCrossParams = cabi.structs["IefCrossParams"]
+IefGemmF32Params = cabi.structs["IefGemmF32Params"]
+IefAttnF32Params = cabi.structs["IefAttnF32Params"]
+IefRepeatJob = cabi.structs["IefRepeatJob"]
+IefGemmX3pParams = cabi.structs["IefGemmX3pParams"]
+IefAttnBwdParams = cabi.structs["IefAttnBwdParams"]
+IefAttnBwdF32Params = cabi.structs["IefAttnBwdF32Params"]
+IefMapLossParams = cabi.structs["IefMapLossParams"]
 
 
 def lib_path() -> str:
@@ -197,124 +55,13 @@ def load():
             "(or `make -C image-editing-framework_amd/csrc`).  There is no CPU fallback."
         )
     lib = ctypes.CDLL(_LIB_PATH)
-    for name in EXPORTS:
-        getattr(lib, name)  # AttributeError here = header / library mismatch
-    lib.ief_abi_version.restype = c_int
-    lib.ief_target_arch.restype = c_char_p
-    lib.ief_gn_splits.restype = c_int
-    lib.ief_gn_splits.argtypes = [c_int]
-    lib.ief_gemm_f16.argtypes = [POINTER(IefGemmParams), c_int, c_void_p]
-    lib.ief_conv3x3_f16.argtypes = [POINTER(IefGemmParams), c_void_p]
-    lib.ief_conv_in_f32.argtypes = [c_void_p] * 4 + [c_int] * 5 + [c_void_p]
-    lib.ief_conv_out_f32.argtypes = [c_void_p] * 4 + [c_int] * 5 + [c_void_p]
-    lib.ief_groupnorm_silu_f16.argtypes = [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                                           c_int, c_int, c_int, c_float, c_int, c_void_p]
-    lib.ief_layernorm_f16.argtypes = [c_void_p] * 4 + [c_int, c_int, c_float, c_void_p]
-    lib.ief_geglu_f16.argtypes = [c_void_p, c_void_p, c_int, c_int, c_void_p]
-    lib.ief_attn_flash_f16.argtypes = [POINTER(IefAttnParams), c_void_p]
-    lib.ief_attn_cross_p2p_f16.argtypes = [POINTER(IefCrossParams), c_void_p]
-    lib.ief_attn_probs_f16.argtypes = [POINTER(IefAttnParams), c_void_p, c_void_p]
-    lib.ief_attn_apply_f16.argtypes = [POINTER(IefAttnParams), c_void_p, c_void_p]
-    lib.ief_cfg_ddim_step_f32.argtypes = [c_void_p] * 6 + [c_longlong, c_void_p]
-    lib.ief_timestep_embedding_f16.argtypes = [c_void_p, c_void_p, c_int, c_int, c_void_p]
-    lib.ief_silu_f16.argtypes = [c_void_p, c_void_p, c_longlong, c_void_p]
-    lib.ief_cast_f32_to_f16.argtypes = [c_void_p, c_void_p, c_longlong, c_void_p]
-    lib.ief_cast_f16_to_f32.argtypes = [c_void_p, c_void_p, c_longlong, c_void_p]
-    lib.ief_select_step.argtypes = [c_void_p, c_void_p, c_void_p, c_longlong, c_int, c_void_p]
-    lib.ief_advance_step.argtypes = [c_void_p, c_void_p]
-    lib.ief_add_f16.argtypes = [c_void_p, c_void_p, c_void_p, c_longlong, c_void_p]
-    lib.ief_softmax_rows_f16.argtypes = [c_void_p, c_int, c_int, c_void_p]
-    lib.ief_transpose_f16.argtypes = [c_void_p, c_void_p, c_int, c_int, c_void_p]
-    lib.ief_pointwise_f32.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]
-    lib.ief_attn_bwd_delta_f32.argtypes = [c_void_p] * 3 + [c_int] * 6 + [c_void_p]
-    lib.ief_attn_bwd_f16.argtypes = [POINTER(IefAttnBwdParams), c_int, c_void_p]
-    lib.ief_attn_map_loss_bwd_f16.argtypes = [POINTER(IefMapLossParams), c_void_p]
-    lib.ief_axpy_f32.argtypes = [c_void_p, c_void_p, c_float, c_longlong, c_void_p]
-    lib.ief_map_loss_blocks.restype = c_int
-    lib.ief_map_loss_blocks.argtypes = [c_int, c_int]
-    lib.ief_groupnorm_cstat_f16.argtypes = [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-                                            c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p]
-    lib.ief_gemm_tile_bm.restype = c_int
-    lib.ief_gemm_tile_bm.argtypes = [c_int]
-    lib.ief_groupnorm_bwd_f16.argtypes = [c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 8 + [c_int, c_int, c_int, c_float,
-                                                                                              c_int, c_void_p]
-    lib.ief_layernorm_bwd_f16.argtypes = [c_void_p] * 5 + [c_int, c_int, c_float, c_void_p]
-    lib.ief_geglu_il_f16.argtypes = [c_void_p, c_void_p, c_int, c_int, c_void_p]
-    lib.ief_geglu_il_bwd_f16.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]
-    lib.ief_zero_insert2x_f16.argtypes = [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p]
-    lib.ief_pool2x2_sum_f16.argtypes = [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p]
-    lib.ief_conv_out_bwd_f32.argtypes = [c_void_p] * 3 + [c_int] * 5 + [c_void_p]
-    lib.ief_nti_loss_grad_f32.argtypes = [c_void_p] * 7 + [c_int, c_float, c_void_p]
-    lib.ief_nti_adam_f32.argtypes = [c_void_p] * 8 + [c_int, c_void_p]
-    lib.ief_gather_rows_f16.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_longlong, c_void_p]
-    lib.ief_gemm_f32.argtypes = [POINTER(IefGemmF32Params), c_void_p]
-    lib.ief_softmax_rows_f32.argtypes = [c_void_p, c_longlong, c_int, c_void_p]
-    lib.ief_attn_flash_f32.argtypes = [POINTER(IefAttnF32Params), c_void_p]
-    lib.ief_p2p_cross_edit_f32.argtypes = [c_void_p] * 5 + [c_int] * 4 + [c_void_p]
-    lib.ief_attn_cross_p2p_f32.argtypes = [POINTER(IefAttnF32Params)] + [c_void_p] * 5
-    lib.ief_groupnorm_silu_f32.argtypes = [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
-                                           c_float, c_int, c_void_p]
-    lib.ief_gemm_x3_bm.argtypes = [c_int, c_int]
-    lib.ief_gemm_x3_bn_k.argtypes = [c_int, c_int, c_int]
+    for name, (restype, argtypes) in cabi.functions.items():
+        fn = getattr(lib, name)  # AttributeError here = header / library mismatch
+        fn.restype, fn.argtypes = restype, argtypes
     if os.environ.get("IEF_X3_WIDE"):          # A/B runs: bit 0 clear = keep every launch on the 128 x 80 tile; bit 1 set = 32-key flash tiles
-        lib.ief_gemm_x3_set_variant.argtypes = [c_int]
         lib.ief_gemm_x3_set_variant(int(os.environ["IEF_X3_WIDE"]))
-    lib.ief_x3_split_weights.argtypes = [c_void_p, c_void_p, c_longlong, c_float, c_void_p]
-    lib.ief_groupnorm_bwd_f32.argtypes = [c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 6 + [c_int, c_int, c_int, c_float, c_int, c_void_p]
-    lib.ief_layernorm_bwd_f32.argtypes = [c_void_p] * 5 + [c_longlong, c_int, c_float, c_void_p]
-    lib.ief_geglu_il_bwd_f32.argtypes = [c_void_p] * 3 + [c_longlong, c_int, c_void_p]
-    lib.ief_zero_insert2x_f32.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]
-    lib.ief_pool2x2_sum_f32.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]
-    lib.ief_conv_out_bwd_f32w.argtypes = [c_void_p] * 3 + [c_int] * 5 + [c_void_p]
-    lib.ief_softmax_bwd_rows_f32.argtypes = [c_void_p, c_void_p, c_longlong, c_int, c_float, c_void_p]
-    lib.ief_transpose_batched_f32.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]
-    lib.ief_map_loss_rows_blocks.argtypes = [c_longlong]
-    lib.ief_map_loss_rows_f32.argtypes = [c_void_p] * 4 + [c_longlong, c_int, c_float, c_float, c_void_p]
-    lib.ief_nti_adam_f32g.argtypes = [c_void_p] * 7 + [c_int, c_void_p]
-    lib.ief_attn_flash_ws_floats.argtypes = [c_int] * 6
-    lib.ief_attn_flash_ws_floats.restype = c_longlong
-    lib.ief_groupnorm_f32_ws_floats.argtypes = [c_int, c_int, c_int]
-    lib.ief_groupnorm_f32_ws_floats.restype = c_longlong
-    lib.ief_groupnorm_silu_f32_ws.argtypes = [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
-                                              c_float, c_int, c_void_p, c_longlong, c_void_p]
-    lib.ief_groupnorm_bwd_f32_ws_floats.argtypes = [c_int, c_int, c_int]
-    lib.ief_groupnorm_bwd_f32_ws_floats.restype = c_longlong
-    lib.ief_groupnorm_bwd_f32_ws.argtypes = [c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 6 + [c_int, c_int, c_int, c_float, c_int,
-                                             c_void_p, c_longlong, c_void_p]
-    lib.ief_layernorm_f32.argtypes = [c_void_p] * 4 + [c_longlong, c_int, c_float, c_void_p]
-    lib.ief_add_f32.argtypes = [c_void_p, c_void_p, c_void_p, c_longlong, c_void_p]
-    lib.ief_silu_f32.argtypes = [c_void_p, c_void_p, c_longlong, c_void_p]
-    lib.ief_geglu_il_f32.argtypes = [c_void_p, c_void_p, c_longlong, c_int, c_void_p]
-    lib.ief_timestep_embedding_f32.argtypes = [c_void_p, c_void_p, c_int, c_int, c_void_p]
-    lib.ief_gather_rows_f32.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_longlong, c_void_p]
-    lib.ief_conv_in_f32act.argtypes = [c_void_p] * 4 + [c_int] * 5 + [c_void_p]
-    lib.ief_conv_out_f32act.argtypes = [c_void_p] * 4 + [c_int] * 5 + [c_void_p]
-    lib.ief_conv_in_f32act_planes.argtypes = [c_void_p] * 5 + [c_longlong] + [c_int] * 5 + [c_void_p]
-    lib.ief_repeat_batch.argtypes = [POINTER(IefRepeatJob), c_int, c_void_p]
-    lib.ief_image_u8.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]
-    lib.ief_gemm_x3p.argtypes = [POINTER(IefGemmX3pParams), c_void_p]
-    lib.ief_gemm_x3p_tile_bm.argtypes = [c_int]
-    lib.ief_gemm_x3p_tile_bn.argtypes = [c_int]
-    lib.ief_gemm_x3p_tile_wn.argtypes = [c_int]
-    lib.ief_x3_split_act.argtypes = [c_void_p, c_void_p, c_longlong, c_longlong, c_int, c_int, c_int, c_float, c_void_p]
-    lib.ief_groupnorm_silu_x3p_ws.argtypes = [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_longlong, c_void_p, c_void_p,
-                                              c_int, c_int, c_int, c_float, c_int, c_void_p, c_longlong, c_void_p]
-    lib.ief_attn_bwd_x3.argtypes = [POINTER(IefAttnBwdF32Params), c_int, c_void_p]
-    lib.ief_attn_bwd_delta_f32in.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]
-    lib.ief_groupnorm_reg_fits.argtypes = [c_int] * 4
-    lib.ief_groupnorm_silu_reg.argtypes = [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_longlong, c_void_p, c_void_p,
-                                           c_int, c_int, c_int, c_float, c_int, c_void_p]
-    lib.ief_groupnorm_silu_x3p_small.argtypes = [c_void_p, c_void_p, c_int, c_int, c_void_p, c_longlong, c_void_p, c_void_p,
-                                                 c_int, c_int, c_int, c_float, c_int, c_void_p]
-    lib.ief_layernorm_x3p.argtypes = [c_void_p, c_void_p, c_longlong, c_void_p, c_void_p, c_longlong, c_int, c_float, c_void_p]
-    lib.ief_cross_token_mass_f32.argtypes = [c_void_p] * 4 + [c_int] * 8 + [c_longlong, c_longlong, c_float, c_void_p]
-    lib.ief_masa_auto_classes.argtypes = [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]
-    lib.ief_nti_loss_grad_batched_f32.argtypes = [c_void_p] * 7 + [c_int, c_int, c_float, c_void_p]
-    lib.ief_nti_adam_batched_f32.argtypes = [c_void_p] * 9 + [c_int, c_int, c_void_p]
-    lib.ief_nti_adam_batched_f32g.argtypes = [c_void_p] * 8 + [c_int, c_int, c_void_p]
     if lib.ief_abi_version() != ABI_VERSION:
         raise HipExtensionMissing("libief_hip.so ABI version mismatch; rebuild")
-    lib.ief_struct_size.argtypes = [c_int]
     for which, st in ((0, IefGemmParams), (1, IefAttnParams), (2, IefCrossParams), (3, IefAttnBwdParams), (4, IefMapLossParams),
                       (5, IefGemmF32Params), (6, IefAttnF32Params), (7, IefGemmX3pParams)):
         if lib.ief_struct_size(which) != ctypes.sizeof(st):

@@ -12,7 +12,7 @@ import torch.multiprocessing as mp
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-from ief_amd import config, hip, weights  # noqa: E402
+from ief_amd import cabi, config, hip, weights  # noqa: E402
 from ief_amd.dist import broadcast_tensors, shard_indices  # noqa: E402
 
 
@@ -27,7 +27,9 @@ def test_library_exports_every_declared_symbol():
     assert len(names) >= 20
     for n in names:
         assert hasattr(lib, n), f"{n} declared in include/ief_hip.h but not exported"
-    assert sorted(hip.EXPORTS) == names, "binding and header disagree on the entry-point list"
+    assert sorted(cabi.functions) == names, "this test's regex and cabi.py disagree on the header's entry-point list"
+    for n in names:
+        assert getattr(lib, n).argtypes is not None, f"{n} is bound without argtypes"
     assert lib.ief_abi_version() == 4 and lib.ief_target_arch() == b"gfx950"
 
 
@@ -588,9 +590,7 @@ def test_x3_tile_geometry_rule_is_host_side_and_callable_without_a_gpu():
     """`ief_gemm_x3_bn_k` (what the split-K policy of the split-operand mode counts tiles with) is plain host code: every 3x3
     convolution whose width is a multiple of 160 takes the 128 x 160 tile, linears only where N <= 1280 or K >= 1280, everything
     else the 80- or 64-wide tile; `ief_gemm_x3_set_variant(0)` switches the wide tile off"""
-    import ctypes
     lib = hip.load()
-    lib.ief_gemm_x3_set_variant.argtypes = [ctypes.c_int]
     f = lib.ief_gemm_x3_bn_k
     assert f(1, 320, 2880) == 160 and f(1, 1280, 11520) == 160 and f(1, 4, 2880) == 64
     assert f(0, 320, 320) == 160 and f(0, 1280, 5120) == 160 and f(0, 10240, 1280) == 160

@@ -124,9 +124,7 @@ def test_gemm_x3_fused_geglu(M, Ch, K, monkeypatch):
 def test_gemm_x3_wide_tile_equals_the_narrow_tile():
     """the launches that take the 128 x 160 tile on 8 waves (`ief_gemm_x3_bn_k`) run the same MFMA sequence per output
     element as on the 128 x 80 tile: bit-identical results, linear (+ fused GEGLU) and 3x3 with concat and 1x1 extra sources"""
-    import ctypes
     lib = hip.load()
-    lib.ief_gemm_x3_set_variant.argtypes = [ctypes.c_int]
     assert lib.ief_gemm_x3_bn_k(0, 320, 256) == 160 and lib.ief_gemm_x3_bn_k(1, 160, 960) == 160 and lib.ief_gemm_x3_bn_k(0, 200, 64) == 64
     a, w, bias = f32(1000, 256, seed=1), f32(320, 256, seed=2, scale=0.06), f32(320, seed=3, scale=0.1)
     x, x2 = f32(2, 16, 16, 64, seed=4), f32(2, 16, 16, 32, seed=5)
