@@ -12,6 +12,12 @@ the same effect is expressed as small device tables, so no map is ever written t
       num_self_replace[0] <= step < num_self_replace[1]:
       target rows take the source row's Q and K (=> identical map), keep their own V
       source-row table int32 [steps+1, 2B]  (identity rows outside the window)
+  LocalBlend of an edit controller (p2p/model/ptp_utils.py, LocalBlend.__call__; the 'p2p' plan with a blend part): the masks
+      come from the EDITED maps of the five 16 x 16 cross-attention modules, summed over the blend words, over heads, modules
+      and all steps so far.  The edit is linear in the two softmax rows it mixes, so that sum is  P_src . u_i + P_i . v_i  with
+      per-step vectors fp32 [steps+1, Bp, 2, 96] the lowering folds from the tables above and the blend words; each of the five
+      modules adds it into one accumulator fp32 [Bp, 256] (`ief_cross_blend_mass_f32`), and after the step's latent update one
+      launch makes the masks and blends the latents in place (`ief_local_blend_f32`)
   MasaCtrl mutual self-attention (/root/reference/masactrl/model/attention_control.py:37-68):
       K,V source rows per (step, layer)
   MasaCtrl mask-guided mutual self-attention (/root/reference/masactrl/model/attention_control.py:134-189), binary masks,
@@ -92,10 +98,12 @@ class ControlPlan:
                  self_window=(0, 0), self_max_tokens: int = 256, masa_steps=(), masa_layers=(),
                  pnp_layers=(), pnp_qk_steps: int = 0, pnp_conv_steps: int = 0, cond_only: bool = False,
                  mask_s: Optional[torch.Tensor] = None, mask_t: Optional[torch.Tensor] = None, mask_tokens=(),
-                 auto_slots=None, auto_layers=None, auto_thres: float = 0.1, auto_ref=(), auto_cur=()):
+                 auto_slots=None, auto_layers=None, auto_thres: float = 0.1, auto_ref=(), auto_cur=(), blend=None):
         """cond_only: the UNet batch holds ONLY the conditional rows [cond_src, cond_tgt...] — the half a controller acts
         on (`attention_base.py:20-22`) — as on the conditional rank of a 2-GPU CFG split (`denoise.CfgSplitDenoiser`) and
-        in the reference's LOW_RESOURCE protocol (:18-19)"""
+        in the reference's LOW_RESOURCE protocol (:18-19)
+        blend ('p2p' only): None, or (execution indices of the five modules LocalBlend reads, per-step weights fp32
+        [steps+1, Bp, 2, XL] = (u_i, v_i), threshold)"""
         self.controller = controller
         self.kind = kind
         self.device = torch.device(device)
@@ -110,6 +118,16 @@ class ControlPlan:
         dev = self.device
         self.step = torch.zeros(1, dtype=torch.int32, device=dev)
         B, Bp = self.batch, num_prompts
+        self.blend_modules = ()
+        self.blend_w = self.blend_w_cur = self.blend_acc = self.blend_thres = None
+        if blend is not None:
+            mods, bw, thres = blend
+            assert kind == "p2p" and not cond_only and tuple(bw.shape) == (num_steps + 1, Bp, 2, XL)
+            self.blend_modules = tuple(int(i) for i in mods)
+            self.blend_w = bw.to(device=dev, dtype=torch.float32).contiguous()
+            self.blend_w_cur = torch.zeros(Bp, 2, XL, dtype=torch.float32, device=dev)
+            self.blend_acc = torch.zeros(Bp, self.MAP_TOKENS, dtype=torch.float32, device=dev)
+            self.blend_thres = torch.tensor([float(thres)], dtype=torch.float32, device=dev)
         if kind == "p2p":
             slots = Bp - 1
             assert mt.shape == (slots, XL, XL) and coef_table.shape == (num_steps + 1, slots, 2, XL)
@@ -286,6 +304,8 @@ class ControlPlan:
     def cross_mass(self, B: int, N: int, attn, q, k):
         """under 'masactrl_mask_auto' a cross-attention module with 256 queries writes its slot: the head-mean map of row c_src
         summed over the reference tokens, that of row c_tgt over the current tokens (q fp32 [B, N, C], k fp32 [B, 77, C])"""
+        if self.blend_w is not None:
+            return self._blend_mass(B, N, attn, q, k)
         if self.kind != "masactrl_mask_auto":
             return
         slot = self.auto_slots.get(attn._exec_index)
@@ -300,6 +320,33 @@ class ControlPlan:
                                f"stated for the batch [u_src, u_tgt, c_src, c_tgt] and {self.CTX_TOKENS} prompt tokens")
         slots, w, _ = self._auto
         hip.cross_token_mass(q, k, attn.heads, attn.scale, (B // 2, B - 1), w, slots[slot])
+
+    # ------------------------------------------------------------------ LocalBlend ('p2p' with a blend part)
+    def _blend_mass(self, B: int, N: int, attn, q, k):
+        """one of the five modules LocalBlend reads adds the word-masked, head-mean sum of its edited maps into the accumulator"""
+        if attn._exec_index not in self.blend_modules:
+            return
+        if N != self.MAP_TOKENS:
+            raise RuntimeError(f"{attn.layer_name}: the blend was lowered for the UNet's configured sample size, where this module has "
+                               f"{self.MAP_TOKENS} queries; it runs at {N}, where LocalBlend's 16 x 16 reshape does not hold")
+        if self.muted or not self.applies(B):
+            return
+        if q.shape[0] != B or k.shape[0] != B or k.shape[1] != self.CTX_TOKENS:
+            raise RuntimeError(f"LocalBlend: cross-attention of batch {tuple(q.shape)} x {tuple(k.shape)}; the rule is stated for the "
+                               f"full CFG batch of {B} rows and {self.CTX_TOKENS} prompt tokens")
+        hip.cross_blend_mass(q, k, attn.heads, attn.scale, self.num_prompts, self.blend_w_cur, self.blend_acc)
+
+    def blend_latents(self, x):
+        """LocalBlend on the latents x fp32 [Bp, C, H, W], in place, from what the steps so far accumulated; nothing without a
+        blend part or in a muted warm-up step"""
+        if self.blend_w is not None and not self.muted:
+            hip.local_blend(self.blend_acc, self.blend_thres, x)
+        return x
+
+    def _rewound(self, step: int):
+        """the step counter was set from outside a forward: at step 0 a new run begins and the blend accumulator starts empty"""
+        if self.blend_acc is not None and step == 0:
+            self.blend_acc.zero_()
 
     def auto_launch(self, B: int, N: int, attn):
         """a controlled self-attention layer under 'masactrl_mask_auto', after the mutual launch: None (not controlled, or no
@@ -336,7 +383,8 @@ class ControlPlan:
             return False
         first = blk.attentions[0].transformer_blocks[0].attn1
         if self.kind == "p2p":         # `/root/reference/p2p/model/attention_base.py:133`: self-attention replace at <= 16^2 keys
-            return tokens <= self.self_max_tokens
+            # a blend module reads the q and k rows of the conditional half of the FULL batch
+            return tokens <= self.self_max_tokens or (first._exec_index + 1) in self.blend_modules
         if self.kind == "masactrl_mask_auto" and (first._exec_index + 1) in self.auto_slots:
             return True                # the first transformer's cross-attention writes a slot from rows c_src / c_tgt of the FULL batch
         if self.kind in self.MASA_KINDS:
@@ -350,8 +398,11 @@ class ControlPlan:
         """everything about this plan that is BAKED into a captured step graph (which kernels run, on which modules,
         with tables of which shape); two plans with equal signatures differ only in table contents"""
         if self.kind == "p2p":
-            return ("p2p", self.num_prompts, self.num_steps, self.self_max_tokens, tuple(self.mt.shape), self.cond_only,
-                    hip.map_split_scale(self.coef_bound))
+            sig = ("p2p", self.num_prompts, self.num_steps, self.self_max_tokens, tuple(self.mt.shape), self.cond_only,
+                   hip.map_split_scale(self.coef_bound))
+            # the blend's launches (which modules accumulate, the blend after the latent update) are baked in; its words and
+            # threshold are data
+            return sig if self.blend_w is None else sig + ("blend", self.blend_modules)
         if self.kind == "masactrl":
             return ("masactrl", tuple(sorted(self.masa_layers)), (max(self.masa_steps) + 2) if self.masa_steps else 1)
         if self.kind == "masactrl_mask":      # the list LENGTHS are launch arguments (grid, N, L); their contents are data
@@ -383,6 +434,11 @@ class ControlPlan:
             self.coef_bound = other.coef_bound       # same split scale (the signatures matched), possibly another bound below it
             self.self_table.copy_(other.self_table)
             self.self_window = other.self_window
+            if self.blend_w is not None:         # equal signatures: `other` has a blend part on the same modules
+                self.blend_w.copy_(other.blend_w)
+                self.blend_thres.copy_(other.blend_thres)
+                if hasattr(self.controller, "_device_blend"):
+                    self.controller._device_blend = self       # its step_callback blends from THIS plan's accumulator
         elif self.kind == "masactrl":
             other.prepare(B)
             self.masa_steps = set(other.masa_steps)
@@ -436,9 +492,12 @@ class ControlPlan:
             if cs > self.num_steps and self.kind == "p2p":
                 raise IndexError(f"cur_step {cs} exceeds the controller's {self.num_steps}-step tables")
             self.step.fill_(cs)
+            self._rewound(cs)
         if self.kind == "p2p":
             hip.select_step(self.coef_table, self.coef_cur, self.step)
             hip.select_step(self.self_table, self.self_cur, self.step)
+            if self.blend_w is not None:
+                hip.select_step(self.blend_w, self.blend_w_cur, self.step)
         elif self.kind in self.MASA_KINDS:
             if B not in self._masa:
                 if self.captured:
@@ -474,6 +533,7 @@ class ControlPlan:
     def sync_step(self):
         """device step counter <- controller.cur_step (before the first replay of a captured loop)"""
         self.step.fill_(int(self.controller.cur_step))
+        self._rewound(int(self.controller.cur_step))
 
     def replay_done(self):
         """one whole forward was replayed from a graph: num_att_layers controller calls happened"""

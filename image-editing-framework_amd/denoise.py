@@ -9,6 +9,7 @@ overhead would exceed the GPU time.  Here the whole step is captured once:
     select_step(time-embedding row)  select_step(DDIM coefficients)     <- read a DEVICE step counter
     [P2P plan: select_step(gate coefficients), select_step(self-replace sources)]
     latents -> CFG batch copy -> UNet (fused attention control) -> fused CFG + DDIM update (in place)
+    [P2P plan with a LocalBlend: the word-masked blend of the updated latents, in place]
     advance_step
 (on the f16x3 planes trunk the UNet takes the latents themselves and runs what both halves of the CFG batch share once: no copy;
 `cfg_shared_prefix_reason`)
@@ -218,6 +219,10 @@ class FusedDenoiser:
             hip.cfg_ddim_step(eps[: self.Bp], eps[self.Bp:], self.lat, self.coef_cur, out=self.lat)
         else:
             hip.cfg_ddim_step(None, eps, self.lat, self.coef_cur, out=self.lat)
+        if self.plan is not None and self.cfg:
+            # the reference's `controller.step_callback` (p2p/model/sd_utils.py, diffusion_step): a lowered LocalBlend blends the
+            # updated latents in place from the maps this and the earlier steps accumulated; nothing for any other plan
+            self.plan.blend_latents(self.lat)
         hip.advance_step(self.step)
 
     def _set_kv_cache(self, on: bool):

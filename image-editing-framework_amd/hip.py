@@ -1683,6 +1683,42 @@ def masa_auto_classes(slots, c, thres, res, k_cls, q_cls, gate=None):
                                      _stream()), "ief_masa_auto_classes")
 
 
+def cross_blend_mass(q, k, heads, scale, row0, w, acc):
+    """acc[i][n] += (1 / heads) sum_h (sum_l v_i[l] softmax_l(scale q_h[row0+i][n] . k_h[row0+i][l]) + sum_l u_i[l] softmax_l(scale
+    q_h[row0][n] . k_h[row0][l])): the head-mean EDITED cross-attention map of the prompt rows row0 .. row0 + Bp - 1, summed over
+    the blend words, without the map (csrc/local_blend.hip).  q fp32 [B, N, heads*d], k fp32 [B, L, heads*d] (column slices are
+    fine), w fp32 [Bp, 2, >= L] = (u_i, v_i) and acc fp32 [Bp, N] (both contiguous).  d any multiple of 8, L <= 128, Bp <= 8."""
+    lib = load()
+    _act32(q, "q"), _act32(k, "k"), _dev32(w, "w"), _dev32(acc, "acc")
+    if q.dim() != 3 or k.dim() != 3 or k.shape[0] != q.shape[0] or k.shape[2] != q.shape[2] or q.shape[2] % heads:
+        raise ValueError("cross_blend_mass: q [B, N, heads*d] and k [B, L, heads*d]")
+    B, N, C = q.shape
+    L = k.shape[1]
+    if w.dim() != 3 or w.shape[1] != 2 or w.shape[2] < L or acc.dim() != 2 or tuple(acc.shape) != (w.shape[0], N):
+        raise ValueError(f"cross_blend_mass: w must be [Bp, 2, >= {L}] and acc [Bp, {N}]")
+    Bp, row0 = w.shape[0], int(row0)
+    if not (0 <= row0 and row0 + Bp <= B):
+        raise ValueError(f"cross_blend_mass: rows {row0} .. {row0 + Bp - 1} outside the batch of {B}")
+    with _Timed("cross_blend_mass_f32_kernel", 2.0 * (2 * Bp - 1) * heads * N * L * (C // heads), 4.0 * Bp * C * (N + L)):
+        _check(lib.ief_cross_blend_mass_f32(q.data_ptr(), k.data_ptr(), w.data_ptr(), acc.data_ptr(), row0, Bp, heads, N, L, w.shape[2],
+                                            C // heads, q.stride(1), k.stride(1), q.stride(0), k.stride(0), float(scale), _stream()),
+               "ief_cross_blend_mass_f32")
+    return acc
+
+
+def local_blend(acc, thres, x):
+    """LocalBlend's last lines on the device, in place on the latents x fp32 [Bp, C, H, W]: acc fp32 [Bp, 256] (what `cross_blend_mass`
+    accumulated) -> 3 x 3 max pool, / image maximum, > thres (device fp32 [1]), mask_i |= mask_0, nearest pixel,
+    x[i] = x[0] + m (x[i] - x[0]) for i >= 1.  H, W multiples of 16."""
+    lib = load()
+    _dev32(acc, "acc"), _dev32(thres, "thres"), _dev32(x, "x")
+    if x.dim() != 4 or acc.dim() != 2 or tuple(acc.shape) != (x.shape[0], 256):
+        raise ValueError("local_blend: x must be [Bp, C, H, W] and acc [Bp, 256]")
+    Bp, C, H, W = x.shape
+    _check(lib.ief_local_blend_f32(acc.data_ptr(), thres.data_ptr(), x.data_ptr(), Bp, C, H, W, _stream()), "ief_local_blend_f32")
+    return x
+
+
 def unpack_class_bits(words, n):
     """packed class words (int32, bit i of word w = token 32 w + i) -> bool [n] on the host"""
     w = words.detach().cpu().to(torch.int64) & 0xFFFFFFFF

@@ -1,7 +1,8 @@
 """Invert a real image, then edit it with Prompt-to-Prompt — CLI of `/root/reference/p2p/edit_real.py`.
 
 Same flags and defaults (`--inversion_type` defaults to "null-text" as in the reference, :26), same outputs:
-`./exp/source.png`, `./exp/inversion.png`, `./exp/edit.png`.
+`./exp/source.png`, `./exp/inversion.png`, `./exp/edit.png`; plus `--blend_source_words` / `--blend_target_words` /
+`--blend_threshold` for `LocalBlend`.
 """
 import argparse
 import os
@@ -14,6 +15,7 @@ from _bootstrap import load_pipe, seed_everything
 from ief_amd.p2p.inversion.ddim import ddim_inversion, ddim_inversion_xl
 from ief_amd.p2p.inversion.nti import NTI, NTI_XL
 from ief_amd.p2p.model.attention_control import AttentionRefine, AttentionReplace
+from ief_amd.p2p.model.ptp_utils import local_blend_from_words
 from ief_amd.p2p.model.register import unregister_attention_control
 from ief_amd.p2p.model.sd_utils import P2P, P2P_NTI, P2P_XL, P2P_XL_NTI
 from ief_amd.p2p.utils.save_image import save_img
@@ -32,13 +34,20 @@ parser.add_argument("--precision", type=str, default=os.environ.get("IEF_PRECISI
 # not a reference flag; "f16x3": keys of the planes self-attention over several workgroups (the batch-1 inversion steps leave
 # most of the chip idle); unset = the IEF_X3P_KEY_SPLITS environment variable, else 1
 parser.add_argument("--attn_key_splits", type=str, default=None, choices=["1", "2", "4", "8", "auto"])
+# not reference flags (its CLIs pass local_blend=None): word-masked latent blending.  Both word lists or neither: the words of the
+# source / the target prompt whose cross-attention marks the region the edit may change; outside it the edited latents are the
+# source's after every step (`ptp_utils.LocalBlend`)
+parser.add_argument("--blend_source_words", type=str, nargs="+", default=None)
+parser.add_argument("--blend_target_words", type=str, nargs="+", default=None)
+parser.add_argument("--blend_threshold", type=float, default=0.3)
 
 
 def edit_latent(pipe, editor, x_T, source_prompt, target_prompt, edit_type, device, extra=None, num_inference_steps=50,
-                guidance_scale=7.5, cross_replace_steps=0.8, self_replace_steps=0.6):
+                guidance_scale=7.5, cross_replace_steps=0.8, self_replace_steps=0.6, local_blend=None):
     """Prompt-to-Prompt edit from an inverted latent x_T [1,4,h,w] -> uint8 images [2,H,W,3] (reconstruction, edit)"""
     kw = dict(prompts=source_prompt + target_prompt, tokenizer=pipe.tokenizer, num_steps=num_inference_steps,
-              cross_replace_steps=cross_replace_steps, self_replace_steps=self_replace_steps, device=device)
+              cross_replace_steps=cross_replace_steps, self_replace_steps=self_replace_steps, device=device,
+              local_blend=local_blend)
     if edit_type == "replace":
         controller = AttentionReplace(**kw)
     elif edit_type == "refine":
@@ -55,7 +64,7 @@ def edit_latent(pipe, editor, x_T, source_prompt, target_prompt, edit_type, devi
 
 def edit_one(pipe, editor, invertor, image, source_prompt, target_prompt, inversion_type, edit_type, device,
              num_inference_steps=50, guidance_scale=7.5, cross_replace_steps=0.8, self_replace_steps=0.6,
-             num_inner_steps=10, early_stop_epsilon=1e-5):
+             num_inner_steps=10, early_stop_epsilon=1e-5, local_blend=None):
     """invert + edit one PIL image -> uint8 images [2,H,W,3] (inversion reconstruction, edit)"""
     latent = invertor.image2latent(model=pipe, image=image, device=device, dtype=torch.float32)
     latents, context = invertor.ddim_inversion_loop(pipe, latent, source_prompt)
@@ -66,11 +75,13 @@ def edit_one(pipe, editor, invertor, image, source_prompt, target_prompt, invers
     elif inversion_type != "ddim":
         raise ValueError("Please choose right inversion type")
     return edit_latent(pipe, editor, latents[-1], source_prompt, target_prompt, edit_type, device, extra,
-                       num_inference_steps, guidance_scale, cross_replace_steps, self_replace_steps)
+                       num_inference_steps, guidance_scale, cross_replace_steps, self_replace_steps, local_blend)
 
 
 def main(argv=None):
     args = parser.parse_args(argv)
+    if (args.blend_source_words is None) != (args.blend_target_words is None):
+        parser.error("--blend_source_words and --blend_target_words go together")
     device = torch.device("cuda:{}".format(args.device))
     seed_everything(args.seed)
     out_path = "./exp"
@@ -90,7 +101,10 @@ def main(argv=None):
     os.makedirs(out_path, exist_ok=True)
     image.save(os.path.join(out_path, "source.png"))
     images = edit_one(pipe, editor, invertor, image, [args.source_prompt], [args.target_prompt], args.inversion_type,
-                      edit_type, device)
+                      edit_type, device,
+                      local_blend=local_blend_from_words(pipe.tokenizer, [args.source_prompt, args.target_prompt],
+                                                         args.blend_source_words, args.blend_target_words, args.blend_threshold,
+                                                         device))
     save_img(images[0], os.path.join(out_path, "inversion.png"))
     save_img(images[1], os.path.join(out_path, "edit.png"))
 

@@ -115,6 +115,13 @@ class AttentionStore(AttentionControl):
 
 
 class AttentionControlEdit(AttentionControl, abc.ABC):
+    """With a `LocalBlend` the controller also keeps the working store the blend reads (upstream prompt-to-prompt derives the edit
+    controllers from `AttentionStore`; the reference's restructuring dropped that base and with it `attention_store`):
+    `step_store` / `attention_store` with `AttentionStore`'s six keys, filled only with the cross-attention maps of <= 32^2 queries,
+    AS EDITED -- nothing reads the self-attention maps.  Without a `LocalBlend` neither attribute exists and nothing is kept.
+    Where the blend was lowered to the device plan (`register.lower_controller`) no map exists; `step_callback` then blends from
+    the plan's accumulator (`_device_blend`, set at registration)."""
+
     def __init__(self, prompts, tokenizer, num_steps: int,
                  cross_replace_steps: Union[float, Tuple[float, float], Dict[str, Tuple[float, float]]],
                  self_replace_steps: Union[float, Tuple[float, float]],
@@ -128,8 +135,36 @@ class AttentionControlEdit(AttentionControl, abc.ABC):
             self_replace_steps = 0, self_replace_steps
         self.num_self_replace = int(num_steps * self_replace_steps[0]), int(num_steps * self_replace_steps[1])
         self.local_blend = local_blend
+        self._device_blend = None
+        if local_blend is not None:
+            self.step_store = AttentionStore.get_empty_store()
+            self.attention_store = {}
 
     def forward(self, attn, is_cross: bool, place_in_unet: str):
+        attn = self._edit(attn, is_cross, place_in_unet)
+        if self.local_blend is not None and is_cross and attn.shape[1] <= 32 ** 2:
+            # a copy: `attn` aliases the caller's maps, which are the module's to reuse once it has applied them
+            self.step_store[f"{place_in_unet}_cross"].append(attn.detach().clone())
+        return attn
+
+    def between_steps(self):
+        if self.local_blend is None:
+            return
+        if len(self.attention_store) == 0:
+            self.attention_store = self.step_store
+        else:
+            for key, maps in self.attention_store.items():
+                for i in range(len(maps)):
+                    maps[i] += self.step_store[key][i]
+        self.step_store = AttentionStore.get_empty_store()
+
+    def reset(self):
+        super().reset()
+        if self.local_blend is not None:
+            self.step_store = AttentionStore.get_empty_store()
+            self.attention_store = {}
+
+    def _edit(self, attn, is_cross: bool, place_in_unet: str):
         lo, hi = self.num_self_replace
         if is_cross or (lo <= self.cur_step < hi):
             heads = attn.shape[0] // self.batch_size
@@ -146,6 +181,8 @@ class AttentionControlEdit(AttentionControl, abc.ABC):
 
     def step_callback(self, x_t):
         if self.local_blend is not None:
+            if self._device_blend is not None:
+                return self._device_blend.blend_latents(x_t.float().contiguous())
             x_t = self.local_blend(x_t, self.attention_store)
         return x_t
 

@@ -54,8 +54,10 @@ def get_time_words_attention_alpha(prompts, num_steps,
 class LocalBlend:
     """Word-masked latent blending from the stored 16x16 cross-attention maps (:6-32).
 
-    Not reachable from the reference CLIs (they pass `local_blend=None`, SURVEY.md §8a A14);
-    kept because `AttentionControlEdit.step_callback` accepts one.
+    The reference CLIs pass `local_blend=None`; here `edit_syn.py` / `edit_real.py` build one from
+    `--blend_source_words` / `--blend_target_words`, and every edit controller takes one: `AttentionControlEdit` keeps the store
+    this class reads, and on the f16x3 planes path the blend is lowered to the device plan (`register.lower_controller`).
+    `__call__` broadcasts its masks over the rows after the first, so it serves TWO prompts (source, target), as upstream's does.
     """
 
     def __init__(self, tokenizer, prompts: List[str], words, threshold: float = 0.3,
@@ -82,3 +84,15 @@ class LocalBlend:
         mask = mask.gt(self.threshold)
         mask = (mask[:1] + mask[1:]).to(x_t.dtype)
         return x_t[:1] + mask * (x_t - x_t[:1])
+
+
+def local_blend_from_words(tokenizer, prompts: List[str], source_words, target_words, threshold: float = 0.3,
+                           device=torch.device("cuda:0")) -> Optional[LocalBlend]:
+    """the `LocalBlend` of a (source, target) prompt pair from the word lists of the CLIs; None when neither list is given"""
+    if source_words is None and target_words is None:
+        return None
+    if source_words is None or target_words is None:
+        raise ValueError("LocalBlend needs the blend words of both prompts")
+    if len(prompts) != 2:
+        raise ValueError("LocalBlend blends one target prompt against one source prompt")
+    return LocalBlend(tokenizer, prompts, [list(source_words), list(target_words)], threshold=threshold, device=device)

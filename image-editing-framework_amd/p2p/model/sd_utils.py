@@ -63,7 +63,8 @@ def _fusable(model, controller, low_resource) -> bool:
     plan = getattr(model.unet, "_plan", None)
     if controller is None:
         return all(m.is_native() for m in model.unet.attention_modules())
-    # a plan exists only for controller classes whose step_callback is the identity (register.lower_controller)
+    # a plan exists only for controller classes whose step_callback is the identity, or a LocalBlend the step graph applies itself
+    # after the latent update (register.lower_controller, denoise.FusedDenoiser._step_body)
     return plan is not None and plan.controller is controller
 
 

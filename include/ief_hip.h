@@ -362,6 +362,24 @@ int ief_cross_token_mass_f32(const float* q, const float* k, const float* w, flo
                              int N, int L, int d, int ldq, int ldk, long long sQb, long long sKb, float scale, void* stream);
 int ief_masa_auto_classes(const float* slots, int c, const float* thres, int res, unsigned* k_cls, unsigned* q_cls,
                           const int* gate, void* stream);
+/* Prompt-to-Prompt's LocalBlend on the fused path (p2p/model/ptp_utils.py, LocalBlend.__call__), two launches (csrc/local_blend.hip).
+ * ief_cross_blend_mass_f32: for one cross-attention module and the Bp prompt rows row0 .. row0 + Bp - 1 of its batch
+ *   acc[i][n] += (1 / heads) sum_h ( sum_l v_i[l] softmax_l(scale q_h[row0 + i][n] . k_h[row0 + i][l])
+ *                                   + sum_l u_i[l] softmax_l(scale q_h[row0][n] . k_h[row0][l]) )
+ * -- the head-mean of the EDITED map P' = c1 (P_src M) + c2 P_i summed over the blend words, which is linear in the two plain
+ * softmax rows: w fp32 [Bp][2][ldw] holds (u_i, v_i) per row, ldw >= L.  q [B][N][heads*d] (row stride ldq, batch stride sQb), k
+ * likewise over L <= 128 keys; acc fp32 [Bp][N], every element read and written by one thread.  The source row's softmax is computed
+ * once per (query, head).  Plain fp32 arithmetic in a fixed order; d any multiple of 8, Bp <= 8.  q, k 16-byte aligned with strides
+ * that are multiples of 4 floats, w / acc 4-byte aligned: IEF_EALIGN otherwise; a null pointer IEF_EINVAL; L > 128, ldw < L, heads >
+ * 64, d % 8 != 0, Bp outside [1, 8] or a non-positive size IEF_ESHAPE.  Nothing is launched by a refused call.
+ * ief_local_blend_f32: acc fp32 [Bp][256] (16 x 16 images) and latents x fp32 [Bp][C][H][W], updated in place.  Per row: 3 x 3
+ * max pool with -inf padding, the image maximum, value / maximum, > *thres (device fp32); an all-zero row gives 0 / 0, which is not
+ * greater: its mask is empty.  mask_i = mask_0 OR mask_i; pixel (y, x) reads cell (floor(16 y / H), floor(16 x / W)); for i >= 1
+ * x[i] = x[0] + m (x[i] - x[0]) with m in {0, 1}, every operation rounded; row 0 is not written.  H, W multiples of 16, Bp >= 2, C >= 1:
+ * IEF_ESHAPE otherwise; a null pointer IEF_EINVAL; a pointer off the 4-byte grid IEF_EALIGN.  One workgroup per (row, channel). */
+int ief_cross_blend_mass_f32(const float* q, const float* k, const float* w, float* acc, int row0, int Bp, int heads, int N, int L,
+                             int ldw, int d, int ldq, int ldk, long long sQb, long long sKb, float scale, void* stream);
+int ief_local_blend_f32(const float* acc, const float* thres, float* x, int Bp, int C, int H, int W, void* stream);
 /* fp32 elements of IefAttnF32Params.ws that the launch needs after clamping key_splits; 0 when it would not split */
 long long ief_attn_flash_ws_floats(int B, int heads, int N, int L, int d, int key_splits);
 int ief_softmax_rows_f32(float* x, long long rows, int L, void* stream);
