@@ -22,6 +22,7 @@
 //   parity is a compile-time constant).
 //   UPS: the nearest-2x upsample of Upsample2D fused in: the super-tile is the SOURCE pixel range the tile touches, the fragment
 //   row is computed per lane and tap; tiles lie inside one image (H W a multiple of 256, W | 256).
+//   PHASE (conv3x3_halo_x3p_kernel_phase, below): the same layer as four 2x2 convolutions of the low-resolution image, 4 taps of 9.
 //
 // Epilogue: a lane holds one output row and four consecutive columns of each block (x3p_common.h, xp_store); split-K = ranges of
 // channel blocks, fp32 slabs summed by x3p_reduce_kernel.
@@ -280,9 +281,250 @@ __global__ __launch_bounds__(768) void conv3x3_halo_x3p_kernel(const IefGemmX3pP
     }
 }
 
-// tiles 11 (plain) / 12 (nearest-2x fused); called by ief_gemm_x3p after its argument checks
+// PHASE form of the fused nearest-2x (tile 13).  Output pixel (2y + py, 2x + px) of nearest-2x + 3x3 / pad 1 sees only the 2x2
+// low-resolution window of taps ty = py .. py + 1, tx = px .. px + 1 (3x3 indexing on the low-res image), with weights that are
+// sums of the nine (ief_x3_upsample_phase_weights): four 2x2 convolutions, 4 MFMA steps per channel block instead of 9.
+// The plain kernel above on the LOW-RESOLUTION image, except:
+//   a workgroup owns 256 consecutive low-res pixels x 80 output channels x ONE phase (grid.z; workgroup-uniform, run time): the
+//   four tap row offsets and zero-row selects of a lane are derived from it once, before the loop;
+//   a channel block is 4 steps.  The weight ring's 4-step lead is exactly one block (step s loads step s of the next block from
+//   this phase's slice [phase][Cout][4 C], k = tap C + c); the next block's 50 super-tile pieces all go out in step 0 (13 per
+//   loader, AHEAD of that step's weight pieces), so the plain kernel's wait -- the groups of the last two steps stay in flight --
+//   still has them in LDS at the barrier of step 3, two full steps after they were requested;
+//   the input-fragment set of a step is the tap's parity (4 steps per block: no two-block unroll);
+//   the epilogue's row is the OUTPUT pixel m_out = (img 2Hi + 2y + py) 2Wi + 2x + px: bias / rowvec / residual / both stores and the
+//   split-K slab + x3p_reduce_kernel work on output rows as for every other tile (a pixel's 80 channels stay one contiguous run).
+__global__ __launch_bounds__(768) void conv3x3_halo_x3p_kernel_phase(const IefGemmX3pParams p) {
+    constexpr int BM = 256, BN = 80, BK = XP_BK, NW = 8, NL = 4;
+    constexpr int TM = 2, TN = 5;
+    constexpr int WMAX = 64;
+    constexpr int NPA = (BM + 2 * WMAX + 2 + 15) / 16;
+    constexpr int APL = NPA * 1024;
+    constexpr int AD = 2 * APL + 128;
+    constexpr int ZA = 2 * APL;
+    constexpr int NPB = BN / 16;
+    constexpr int BPL = NPB * 1024, BBUF = 2 * BPL, NSB = 5;
+    constexpr int BOFF = 2 * AD, DUMP = BOFF + NSB * BBUF;
+    constexpr int LDS_BYTES = DUMP + 1024;
+    constexpr int NU = 2 * NPA;
+    constexpr int NT = 4;                                    // steps (taps) per channel block
+    constexpr int APT = (NU + NL - 1) / NL;                  // 13 super-tile pieces per loader, all in step 0
+    static_assert(APT * NL >= NU && 3 * NL >= 2 * NPB, "loader schedule");
+    static_assert(LDS_BYTES <= 160 * 1024, "LDS");
+    __shared__ __attribute__((aligned(1024))) char smem[LDS_BYTES];
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int W = p.Wd >> 1, H = p.H >> 1;                   // the stored (low-resolution) image
+    const int Ms = p.batch_images * H * W;
+    const int tiles_n = (p.N + BN - 1) / BN, tiles_m = (Ms + BM - 1) / BM;
+    const int lid = xcd_remap(blockIdx.x, gridDim.x);        // tile order as the plain kernel
+    const int grp = lid / (XP_GROUP_M * tiles_n), within = lid - grp * (XP_GROUP_M * tiles_n);
+    const int gsz = min(XP_GROUP_M, tiles_m - grp * XP_GROUP_M);
+    const int tn = within / gsz, tm = grp * XP_GROUP_M + (within - tn * gsz);
+    const int m0 = tm * BM, n0 = tn * BN;
+    const int py = (int)blockIdx.z >> 1, px = (int)blockIdx.z & 1;
+    const int Ctot = p.C1 + p.C2;
+    const char* __restrict__ zp = (const char*)p.zeros;
+    const int st_row0 = m0 - (W + 1);
+
+    const int ncb = Ctot / BK;
+    int cb_lo = 0, cb_hi = ncb;
+    if (p.splits > 1) {
+        const int per = (ncb + p.splits - 1) / p.splits;
+        cb_lo = min(ncb, (int)blockIdx.y * per);
+        cb_hi = min(ncb, cb_lo + per);
+    }
+    const int nblk = cb_hi - cb_lo;
+
+    if (tid < 16) { ((float*)(smem + ZA))[tid] = 0.f; ((float*)(smem + ZA + AD))[tid] = 0.f; }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // the first s_barrier publishes the zero rows
+
+    if (wave >= NW) {
+        // ------------------------------------------------------------------------------------------------ loader waves
+        const int l = wave - NW;
+        const unsigned st_chunk = (unsigned)(XP_LANE_CHUNK(lane) * 16);
+        const int ms_lane = st_row0 + (lane >> 2);
+        const char* an_src = zp; long long an_pl = 0; unsigned an_cs = 0, an_c0 = 0; bool an_on = false;
+        auto set_next_block = [&](int cb, bool on) {
+            const bool first = cb * BK < p.C1;
+            an_src = (const char*)(first ? p.A : p.A2);
+            an_pl = (first ? p.planeA : p.planeA2) * 2;
+            an_cs = (unsigned)(first ? p.C1 : p.C2);
+            an_c0 = (unsigned)(first ? cb * BK : cb * BK - p.C1);
+            an_on = on;
+        };
+        auto issue_a = [&](int u, int buf_off) {              // super-tile piece u (wave-uniform) of the next block: plane u / NPA
+            const bool exists = u < NU;
+            const int pl = u >= NPA ? 1 : 0, q = u - pl * NPA;
+            const int ms = ms_lane + 16 * q;
+            const bool ok = exists && an_on && (unsigned)ms < (unsigned)Ms;
+            const char* g = ok ? an_src + ((long long)pl * an_pl + (long long)((unsigned)ms * an_cs + an_c0) * 2 + st_chunk) : zp;
+            glds16(g, (half_t*)(smem + (exists ? pl * AD + buf_off + q * 1024 : DUMP)));
+        };
+        // this phase's slice of the weight planes: [phase][N][K], K = 4 Ctot
+        const long long w_lane = ((long long)blockIdx.z * p.N + n0 + (lane >> 2)) * p.K * 2 + st_chunk;
+        auto issue_b = [&](int cb, int tap, bool on, int slot_off) {
+            const long long k0 = (long long)(tap * Ctot + cb * BK) * 2;
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                const int v = l + NL * j;                     // weight piece: plane v / NPB, rows 16 (v % NPB) ..
+                const bool exists = v < 2 * NPB;
+                const int pl = v >= NPB ? 1 : 0, q = v - pl * NPB;
+                const bool ok = exists && on && n0 + 16 * q + (lane >> 2) < p.N;
+                const char* g = ok ? (const char*)p.W + ((long long)pl * p.planeW * 2 + w_lane + (long long)(16 * q) * p.K * 2 + k0) : zp;
+                glds16(g, (half_t*)(smem + (exists ? BOFF + slot_off + pl * BPL + q * 1024 : DUMP)));
+            }
+        };
+        auto n_issued = [](int tap) constexpr -> int { return 3 + (tap == 0 ? APT : 0); };
+        if (nblk > 0) {
+            set_next_block(cb_lo, true);
+#pragma unroll
+            for (int j = 0; j < APT; ++j) issue_a(l + NL * j, 0);
+            issue_b(cb_lo, 0, true, 0);
+            issue_b(cb_lo, 1, true, BBUF);
+            issue_b(cb_lo, 2, true, 2 * BBUF);
+            issue_b(cb_lo, 3, true, 3 * BBUF);
+            asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
+            XP_BARRIER();
+        }
+        int bs_prev = 4 * BBUF, bs = 0, bs_next = BBUF;
+        for (int cbi = 0; cbi < nblk; ++cbi) {
+            const int cb = cb_lo + cbi;
+            const int abuf_n = APL - (cbi & 1) * APL;
+            const bool more = cb + 1 < cb_hi;
+            set_next_block(min(cb + 1, cb_hi - 1), more);
+            auto one_step = [&](auto tap_tag) {
+                constexpr int tap = decltype(tap_tag)::value;
+                asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n_issued((tap + NT - 1) % NT) + n_issued((tap + NT - 2) % NT)) : "memory");
+                XP_BARRIER();
+                if constexpr (tap == 0) {
+#pragma unroll
+                    for (int j = 0; j < APT; ++j) issue_a(l + NL * j, abuf_n);
+                }
+                issue_b(cb + 1, tap, more, bs_prev);          // the same tap of the next block: a lead of exactly four steps
+                bs_prev = bs; bs = bs_next; bs_next = bs_next == (NSB - 1) * BBUF ? 0 : bs_next + BBUF;
+            };
+            one_step(IntTag<0>{}); one_step(IntTag<1>{}); one_step(IntTag<2>{}); one_step(IntTag<3>{});
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // nothing of this launch may still be landing when the LDS is released
+        return;
+    }
+
+    // ---------------------------------------------------------------------------------------------------- compute waves
+    const int fr = lane & 15, fq = lane >> 4;
+    // byte offset inside a super-tile buffer of this lane's hi fragment for each of the phase's four taps, -1 = the zero row
+    int a_off[TM][NT];
+    int m_out[TM];                                           // the OUTPUT pixel of the lane's low-res row, -1 past the image batch
+#pragma unroll
+    for (int i = 0; i < TM; ++i) {
+        const int r = wave * 32 + i * 16 + fr, m = m0 + r;
+        const int img = m / (H * W), rem = m - img * (H * W);
+        const int y = rem / W, x = rem - y * W;
+        m_out[i] = m < Ms ? (img * 2 * H + 2 * y + py) * (2 * W) + 2 * x + px : -1;
+#pragma unroll
+        for (int s = 0; s < NT; ++s) {
+            const int ty = py + (s >> 1), tx = px + (s & 1);
+            const bool zero = m >= Ms || (tx == 0 && x == 0) || (tx == 2 && x == W - 1) || (ty == 0 && y == 0) || (ty == 2 && y == H - 1);
+            const int sr = r + ty * W + tx;
+            a_off[i][s] = zero ? -1 : sr * 64 + ((fq ^ xp_swz(sr)) << 4);
+        }
+    }
+    int b_off[TN];
+#pragma unroll
+    for (int j = 0; j < TN; ++j) {
+        const int row = j * 16 + fr;
+        b_off[j] = BOFF + row * 64 + ((fq ^ xp_swz(row)) << 4);
+    }
+    f32x4 acc[TN][TM];
+#pragma unroll
+    for (int j = 0; j < TN; ++j)
+#pragma unroll
+        for (int i = 0; i < TM; ++i) acc[j][i] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    half8 ah[2][TM], al[2][TM], bh[TN], bl[TN];
+    auto read_a = [&](half8 (&h)[TM], half8 (&l)[TM], int abuf, auto tap_tag) {
+        constexpr int s = decltype(tap_tag)::value;
+#pragma unroll
+        for (int i = 0; i < TM; ++i) {
+            const int ad = a_off[i][s] < 0 ? ZA : abuf + a_off[i][s];
+            h[i] = *(const half8*)(smem + ad);
+            l[i] = *(const half8*)(smem + ad + AD);
+        }
+    };
+    if (nblk > 0) {
+        XP_BARRIER();                                        // super-tile 0 and weight tile 0 have landed
+        read_a(ah[0], al[0], 0, IntTag<0>{});
+#pragma unroll
+        for (int j = 0; j < TN; ++j) { bh[j] = *(const half8*)(smem + b_off[j]); bl[j] = *(const half8*)(smem + b_off[j] + BPL); }
+    }
+    int bs_next = BBUF;                                      // ring slot (byte offset) of step t + 1
+    auto one_step = [&](auto tap_tag, int abuf, int abuf_n) {
+        constexpr int tap = decltype(tap_tag)::value, PAR = tap & 1;
+        XP_BARRIER();
+        // input fragments of step t + 1: next tap of this block, or tap 0 of the next block (other buffer)
+        read_a(ah[PAR ^ 1], al[PAR ^ 1], tap == NT - 1 ? abuf_n : abuf, IntTag<(tap + 1) % NT>{});
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+#pragma unroll
+            for (int i = 0; i < TM; ++i) {
+                acc[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bl[j], ah[PAR][i], acc[j][i], 0, 0, 0);
+                acc[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bh[j], al[PAR][i], acc[j][i], 0, 0, 0);
+                acc[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bh[j], ah[PAR][i], acc[j][i], 0, 0, 0);
+            }
+            // this block's weight fragments of step t + 1 take the registers just consumed
+            bh[j] = *(const half8*)(smem + bs_next + b_off[j]);
+            bl[j] = *(const half8*)(smem + bs_next + b_off[j] + BPL);
+        }
+        bs_next = bs_next == (NSB - 1) * BBUF ? 0 : bs_next + BBUF;
+    };
+    for (int cbi = 0; cbi < nblk; ++cbi) {
+        const int abuf = (cbi & 1) * APL, abuf_n = APL - abuf;
+        one_step(IntTag<0>{}, abuf, abuf_n); one_step(IntTag<1>{}, abuf, abuf_n);
+        one_step(IntTag<2>{}, abuf, abuf_n); one_step(IntTag<3>{}, abuf, abuf_n);
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // the trailing fragment requests of the last step (never used)
+
+    // ---------------- epilogue: a lane holds output row m_out, columns n .. n + 3 of each 16 x 16 block
+    const float inv = p.inv_scale;
+    if (p.splits > 1) {
+        float* slab = p.ws + (long long)blockIdx.y * p.M * p.N;
+#pragma unroll
+        for (int i = 0; i < TM; ++i) {
+            if (m_out[i] < 0) continue;
+#pragma unroll
+            for (int j = 0; j < TN; ++j) {
+                const int n = n0 + j * 16 + 4 * fq;
+                if (n < p.N) *(f32x4*)(slab + (long long)m_out[i] * p.N + n) = acc[j][i] * inv;
+            }
+        }
+        return;
+    }
+#pragma unroll
+    for (int i = 0; i < TM; ++i) {
+        if (m_out[i] < 0) continue;
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+            const int n = n0 + j * 16 + 4 * fq;
+            if (n < p.N) xp_store(p, acc[j][i] * inv, m_out[i], n);
+        }
+    }
+}
+
+// tiles 11 (plain) / 12 (nearest-2x fused) / 13 (nearest-2x, phase form); called by ief_gemm_x3p after its argument checks
 int ief_conv_halo_x3p_dispatch(const IefGemmX3pParams& p, hipStream_t st) {
     if (!p.conv || p.stride != 1 || p.pad_hi_only || p.CE1 || p.CE2 || p.Wd < 2 || p.H < 2 || p.geglu) return IEF_ESHAPE;
+    if (p.tile == 13) {
+        // the geometry limits of tile 11 on the SOURCE image; the weight is the phase form: K = 4 (C1 + C2), planes [2][4][N][K]
+        const int Wi = p.Wd >> 1, Hi = p.H >> 1;
+        if (!p.ups || Wi > 64 || Wi < 2 || Hi < 2 || p.K != 4 * (p.C1 + p.C2) || p.ldw != p.K) return IEF_ESHAPE;
+        const int ncb = (p.C1 + p.C2) / XP_BK;
+        if (p.splits > ncb) return IEF_ESHAPE;
+        const int tiles = ((p.M / 4 + 255) / 256) * ((p.N + 79) / 80);
+        hipLaunchKernelGGL(conv3x3_halo_x3p_kernel_phase, dim3(tiles, p.splits > 1 ? p.splits : 1, 4), dim3(768), 0, st, p);
+        IEF_LAUNCH_CHECK();
+        return IEF_OK;
+    }
     if (p.ups) {
         if (p.tile != 12 || p.Wd > 128 || (p.H * p.Wd) % 256 || 256 % p.Wd) return IEF_ESHAPE;
     } else if (p.tile != 11 || p.Wd > 64) return IEF_ESHAPE;

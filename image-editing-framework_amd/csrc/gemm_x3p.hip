@@ -497,7 +497,7 @@ extern "C" int ief_x3_split_act(const float* x, ief_half* planes, long long plan
 extern "C" int ief_gemm_x3p_tile_bm(int tile) {
     switch (tile) {
         case 1: case 2: case 3: case 7: return 128;
-        case 4: case 8: case 11: case 12: return 256;
+        case 4: case 8: case 11: case 12: case 13: return 256;
         case 5: return 64;
         case 6: return 128;
         default: return 0;
@@ -507,7 +507,7 @@ extern "C" int ief_gemm_x3p_tile_wn(int tile) { return tile == 6 ? 64 : tile == 
 extern "C" int ief_gemm_x3p_tile_bn(int tile) {
     switch (tile) {
         case 1: case 2: case 4: case 5: case 7: return 160;
-        case 3: case 11: case 12: return 80;
+        case 3: case 11: case 12: case 13: return 80;
         case 6: return 64;
         case 8: return 320;
         default: return 0;
@@ -540,7 +540,7 @@ extern "C" int ief_gemm_x3p(const IefGemmX3pParams* pp, void* stream) {
     if ((p.bias && ((uintptr_t)p.bias & 15)) || (p.rowvec && ((uintptr_t)p.rowvec & 15)) ||
         (p.residual && (((uintptr_t)p.residual & 15) || (p.ldr & 3)))) return IEF_EALIGN;
     if (p.geglu && ((p.N & 15) || p.residual || p.rowvec)) return IEF_EINVAL;
-    if (p.rstat_out && (p.splits > 1 || p.geglu || p.tile == 11 || p.tile == 12 || (p.N % ief_gemm_x3p_tile_wn(p.tile)))) return IEF_EINVAL;
+    if (p.rstat_out && (p.splits > 1 || p.geglu || p.tile == 11 || p.tile == 12 || p.tile == 13 || (p.N % ief_gemm_x3p_tile_wn(p.tile)))) return IEF_EINVAL;
     if (p.rstat_in && (!p.colsum || p.rstat_slots <= 0 || p.rstat_cnt <= 0 || p.rstat_slots * p.rstat_cnt != p.K || p.splits > 1 ||
                        p.conv || !(p.ln_eps > 0.f) || ((uintptr_t)p.colsum & 15))) return IEF_EINVAL;
     if (p.conv) {
@@ -550,7 +550,9 @@ extern "C" int ief_gemm_x3p(const IefGemmX3pParams* pp, void* stream) {
         if (p.ups != 0 && p.ups != 1) return IEF_ESHAPE;
         if (p.ups && ((p.H | p.Wd) & 1)) return IEF_ESHAPE;
         if ((p.CE1 + p.CE2) > 0 && (p.stride != 1 || p.ups)) return IEF_ESHAPE;
-        if (p.K != 9 * (p.C1 + p.C2) + p.CE1 + p.CE2 || p.batch_images <= 0 || p.M != p.batch_images * p.Ho * p.Wo) return IEF_ESHAPE;
+        // tile 13 (phase form of the fused nearest-2x): the weight holds four 2x2 kernels, K = 4 (C1 + C2) per phase
+        const int ktaps = p.tile == 13 ? 4 : 9;
+        if (p.K != ktaps * (p.C1 + p.C2) + p.CE1 + p.CE2 || p.batch_images <= 0 || p.M != p.batch_images * p.Ho * p.Wo) return IEF_ESHAPE;
         const long long in_pix = (long long)p.batch_images * (p.H >> p.ups) * (p.Wd >> p.ups);
         const int cmax = p.C1 > p.C2 ? p.C1 : p.C2, emax = p.CE1 > p.CE2 ? p.CE1 : p.CE2;
         if (in_pix * cmax * 2 >= (1ll << 32) || (long long)p.M * emax * 2 >= (1ll << 32)) return IEF_ESHAPE;   // 32-bit pixel offsets
@@ -569,7 +571,7 @@ extern "C" int ief_gemm_x3p(const IefGemmX3pParams* pp, void* stream) {
         case 6: rc = launch_x3p<128, 64, 4, 1, 3, 0>(p, st); break;
         case 7: rc = launch_x3p<128, 160, 2, 2, 2, 0>(p, st); break;       // 4 waves (64 x 80 each), 72 KiB of LDS: two workgroups per CU
         case 8: rc = launch_x3p<256, 320, 4, 2, 2, 0>(p, st); break;       // 8 waves of 64 x 160: the fewest staged bytes per FLOP (wide N only)
-        case 11: case 12: rc = ief_conv_halo_x3p_dispatch(p, st); break;
+        case 11: case 12: case 13: rc = ief_conv_halo_x3p_dispatch(p, st); break;
         case 1: default: rc = launch_x3p<128, 160, 4, 2, 4, 0>(p, st); break;
     }
     if (rc) return rc;

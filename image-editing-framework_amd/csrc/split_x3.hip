@@ -58,6 +58,47 @@ extern "C" int ief_x3_split_weights(const float* w, void* planes, long long n, f
     return IEF_OK;
 }
 
+// Upsample2D's weight in PHASE form (conv_halo_x3p.hip, tile 13): nearest-2x followed by 3x3 / pad 1 makes output pixel
+// (2y + py, 2x + px) a 2x2 convolution of the low-resolution image whose weights are sums of the nine.  With tap t = low-res
+// row y + t - 1 (the 3x3 indexing), phase p uses taps p, p + 1, and the original rows fold as
+//     p = 0: tap 0 <- ky {0}, tap 1 <- ky {1, 2};      p = 1: tap 1 <- ky {0, 1}, tap 2 <- ky {2}           (the same in x)
+// w fp32 [Cout][3][3][C] -> planes [2][4 phases (py, px)][Cout][4 taps (sy, sx)][C]: the fp32 sum of the 1, 2 or 4 weights in
+// increasing (ky, kx) order, then the hi / lo split of x3_split_weights_kernel.  One thread per four channels of one output element.
+__global__ __launch_bounds__(256) void x3_upsample_phase_weights_kernel(const float* __restrict__ w, half_t* __restrict__ planes, int Cout,
+                                                                        int C4, float s) {
+    const long long n4 = 16ll * Cout * C4;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
+        const int c4 = (int)(i % C4);
+        long long r = i / C4;
+        const int tap = (int)(r & 3);
+        r >>= 2;
+        const int n = (int)(r % Cout), ph = (int)(r / Cout);
+        const int py = ph >> 1, px = ph & 1, sy = tap >> 1, sx = tap & 1;
+        const int ky0 = py ? 2 * sy : sy, ky1 = py ? 1 + sy : 2 * sy;
+        const int kx0 = px ? 2 * sx : sx, kx1 = px ? 1 + sx : 2 * sx;
+        const f32x4* src = (const f32x4*)w + (long long)n * 9 * C4 + c4;
+        f32x4 a = src[(ky0 * 3 + kx0) * C4];
+        for (int ky = ky0; ky <= ky1; ++ky)
+            for (int kx = kx0; kx <= kx1; ++kx)
+                if (ky != ky0 || kx != kx0) a = a + src[(ky * 3 + kx) * C4];
+        half4 h, l;
+        split4(a, s, h, l);
+        ((half4*)planes)[i] = h;
+        ((half4*)planes)[n4 + i] = l;
+    }
+}
+extern "C" int ief_x3_upsample_phase_weights(const float* w, void* planes, int Cout, int C, float scale, void* stream) {
+    if (!w || !planes) return IEF_EINVAL;
+    if (Cout <= 0 || C <= 0 || (C & 3) || !(scale > 0.f)) return IEF_ESHAPE;
+    if (((uintptr_t)w & 15) || ((uintptr_t)planes & 7)) return IEF_EALIGN;
+    long long grid = (16ll * Cout * (C / 4) + 255) / 256;
+    if (grid > 16384) grid = 16384;
+    hipLaunchKernelGGL(x3_upsample_phase_weights_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, w, (half_t*)planes, Cout,
+                       C / 4, scale);
+    IEF_LAUNCH_CHECK();
+    return IEF_OK;
+}
+
 // BPRE: the B operand comes as pre-split fp16 planes (p.Wp: [2][N][K] contiguous, ief_x3_split_weights); otherwise it is
 // fp32 and split while staged, like A (the batched attention products: both operands are activations).
 template <int WM, int WN, int TM, int TN, int KIND, bool TRANSB, bool BPRE>

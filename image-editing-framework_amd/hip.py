@@ -485,7 +485,8 @@ class f32_contraction:
         return False
 
 
-# (data_ptr, shape, scale) -> (weakref to the weight tensor, its _version, planes fp16 [2, N, K]).  The entry dies WITH the weight
+# (data_ptr, shape, scale[, "phase"]) -> (weakref to the weight tensor, its _version, planes fp16 [2, N, K]; "phase": the phase form
+# [2, 4, N, 4 C] of an Upsample2D weight, x3_upsample_phase_planes).  The entry dies WITH the weight
 # (weakref.finalize): a model that is dropped frees its planes (they are as large as the weights).  A captured graph bakes the
 # planes' address in: an in-place update of a weight after capture would replace the entry and free planes the graph still
 # reads, so weights are immutable once a graph over them exists (the weight broadcast runs before any forward).
@@ -509,6 +510,29 @@ def x3_weight_planes(w, scale=None):
     n = w.shape[0]
     planes = torch.empty(2, n, w.numel() // n, dtype=torch.float16, device=w.device)
     _check(lib.ief_x3_split_weights(w.data_ptr(), planes.data_ptr(), w.numel(), float(scale), _stream()), "ief_x3_split_weights")
+    import weakref
+    _x3_planes[key] = (weakref.ref(w), w._version, planes)
+    weakref.finalize(w, _x3_planes.pop, key, None)
+    return planes
+
+
+def x3_upsample_phase_planes(w, scale=None):
+    """the PHASE form of an Upsample2D weight [Cout, 3, 3, C] as fp16 planes [2, 4, Cout, 4 C] (`ief_x3_upsample_phase_weights`:
+    nearest-2x + 3x3 is four 2x2 convolutions of the low-resolution image whose taps are sums of the nine).  Cached per weight
+    tensor exactly as `x3_weight_planes` (its own key: a layer that runs the phase form never creates the 9-tap planes)."""
+    scale = X3_SCALE_W if scale is None else scale
+    key = (w.data_ptr(), tuple(w.shape), float(scale), "phase")
+    hit = _x3_planes.get(key)
+    if hit is not None and hit[0]() is w and hit[1] == w._version:
+        return hit[2]
+    if _capturing() or not w.is_contiguous():
+        return None
+    if w.dim() != 4 or tuple(w.shape[1:3]) != (3, 3) or w.shape[3] % 4:
+        raise ValueError("x3_upsample_phase_planes: weight must be [Cout, 3, 3, C] with C a multiple of 4")
+    lib = load()
+    n, c = w.shape[0], w.shape[3]
+    planes = torch.empty(2, 4, n, 4 * c, dtype=torch.float16, device=w.device)
+    _check(lib.ief_x3_upsample_phase_weights(w.data_ptr(), planes.data_ptr(), n, c, float(scale), _stream()), "ief_x3_upsample_phase_weights")
     import weakref
     _x3_planes[key] = (weakref.ref(w), w._version, planes)
     weakref.finalize(w, _x3_planes.pop, key, None)

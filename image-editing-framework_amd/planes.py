@@ -128,7 +128,8 @@ def save_plans(path=None):
 
 
 _TILES = {1: (128, 160), 2: (128, 160), 3: (128, 80), 4: (256, 160), 5: (64, 160), 6: (128, 64), 7: (128, 160), 8: (256, 320),
-          11: (256, 80), 12: (256, 80)}
+          11: (256, 80), 12: (256, 80), 13: (256, 80)}
+_HALO = (11, 12, 13)      # conv3x3_halo_x3p: 11 plain, 12 nearest-2x fused (nine taps), 13 nearest-2x in phase form (four 2x2 convolutions)
 
 
 def heuristic_plan(M, N, K, conv=False):
@@ -162,12 +163,12 @@ def pick_plan(M, N, K, conv=False, variant=""):
 AUTOTUNE = os.environ.get("IEF_AUTOTUNE_X3", "0") == "1"      # tune unseen shapes on first (eager) use: tests/tune_plans_x3.py
 
 
-def candidate_plans(M, N, K, conv=False, halo_ok=False, ncb=0, geglu=False):
-    """(tile, splits) worth timing for one shape"""
+def candidate_plans(M, N, K, conv=False, halo_ok=False, ncb=0, geglu=False, phase_ok=False):
+    """(tile, splits) worth timing for one shape (phase_ok: a `|u` shape whose source rows fit the phase form, tile 13)"""
     nk = K // 32
     out = []
     for t, (bm, bn) in _TILES.items():
-        if t in (11, 12):
+        if t in _HALO:
             continue
         if N % bn or (t == 6 and N % 80 == 0):
             continue
@@ -186,6 +187,14 @@ def candidate_plans(M, N, K, conv=False, halo_ok=False, ncb=0, geglu=False):
             if tiles * sp < 40 and sp < 16:
                 continue
             out.append((11, sp))
+    if conv and phase_ok:
+        tiles = -(-(M // 4) // 256) * (N // 80) * 4          # a workgroup = 256 source pixels x 80 columns x one phase
+        for sp in (1, 2, 3, 4, 5, 6, 8, 10, 12, 16, 20):
+            if sp > 1 and (sp > ncb // 2 or tiles * sp > 1024 or tiles >= 384):
+                continue
+            if tiles * sp < 40 and sp < 16:
+                continue
+            out.append((13, sp))
     return out
 
 
@@ -194,6 +203,8 @@ def _autotune(key, cands, run, w):
     wc = hip._cold_copies(w)
     for x in wc:
         weight_planes(x)
+        if any(t == 13 for t, _ in cands):
+            hip.x3_upsample_phase_planes(x, W_SCALE)
     best = None
     for t, sp in cands:
         try:
@@ -204,6 +215,7 @@ def _autotune(key, cands, run, w):
             best = (us, t, sp)
     for x in wc[1:]:
         hip._x3_planes.pop((x.data_ptr(), tuple(x.shape), float(W_SCALE)), None)
+        hip._x3_planes.pop((x.data_ptr(), tuple(x.shape), float(W_SCALE), "phase"), None)
     if best is not None:
         _plan_table()[key] = (best[1], best[2])
     return best
@@ -366,7 +378,6 @@ def conv3x3(x, w, bias=None, x2=None, stride=1, upsample=False, rowvec=None, res
     pad_total = 1 if pad_hi_only else 2
     Ho, Wo = (H + pad_total - 3) // stride + 1, (Wd + pad_total - 3) // stride + 1
     M = B * Ho * Wo
-    wp = weight_planes(w)
     p = IefGemmX3pParams()
     p.A, p.planeA = x.t.data_ptr(), x.plane
     if x2 is not None:
@@ -375,7 +386,6 @@ def conv3x3(x, w, bias=None, x2=None, stride=1, upsample=False, rowvec=None, res
         p.E1, p.planeE1 = e1.t.data_ptr(), e1.plane
     if e2 is not None:
         p.E2, p.planeE2 = e2.t.data_ptr(), e2.plane
-    p.W, p.planeW, p.ldw = wp.data_ptr(), wp.stride(0), K
     o32, op = _out_args(p, M, Cout, out, out_planes, x.device, (B, Ho, Wo))
     p.bias = _ptr(_dev32(bias, "bias")) if bias is not None else None
     if rowvec is not None:
@@ -397,17 +407,19 @@ def conv3x3(x, w, bias=None, x2=None, stride=1, upsample=False, rowvec=None, res
     # pixels, or the fused nearest-2x on rows of <= 128 pixels with whole output rows per 256-pixel tile
     halo_ok = HALO and stride == 1 and not pad_hi_only and extra is None and Hp >= 2 and Cout % 80 == 0 and (
         (not upsample and 2 <= Wd <= 64) or (upsample and Wd <= 128 and (H * Wd) % 256 == 0 and 256 % Wd == 0))
+    # the phase form of the fused nearest-2x: tile 11's limits on the SOURCE image
+    phase_ok = HALO and upsample and stride == 1 and not pad_hi_only and extra is None and Hp >= 2 and 2 <= Wp <= 64 and Cout % 80 == 0
     if tile:
         p.tile, p.splits = tile, max(1, splits)
     else:
         variant = ("|u" if upsample else "") + (f"|s{stride}" if stride != 1 else "") + ("|e" if extra is not None else "")
         key = f"conv|{M}|{Cout}|{K}{variant}"
         if AUTOTUNE and key not in _plan_table() and not hip._capturing() and hip._prof is None:
-            _autotune(key, candidate_plans(M, Cout, K, conv=True, halo_ok=halo_ok, ncb=(C1 + C2) // 32),
+            _autotune(key, candidate_plans(M, Cout, K, conv=True, halo_ok=halo_ok, ncb=(C1 + C2) // 32, phase_ok=phase_ok),
                       lambda t, sp, wi: conv3x3(x, wi, bias, x2=x2, stride=stride, upsample=upsample, rowvec=rowvec, residual=residual,
                                                 out=out, out_planes=out_planes, extra=extra, pad_hi_only=pad_hi_only, tile=t, splits=sp), w)
         hit = _plan_table().get(key)
-        if hit is not None and (hit[0] not in (11, 12) or halo_ok):
+        if hit is not None and (hit[0] not in _HALO or (phase_ok if hit[0] == 13 else halo_ok)):
             p.tile, p.splits = hit[0], hit[1]
         elif halo_ok:
             tiles, ncb = -(-M // 256) * (Cout // 80), (C1 + C2) // 32
@@ -419,19 +431,35 @@ def conv3x3(x, w, bias=None, x2=None, stride=1, upsample=False, rowvec=None, res
             p.tile, p.splits = heuristic_plan(M, Cout, K, conv=True)        # (the table is keyed WITH the variant: no plain-key fallback)
             if TILE_FORCE and TILE_FORCE < 10:
                 p.tile = TILE_FORCE
-    if p.tile in (11, 12):
-        if not halo_ok:
-            raise ValueError("planes.conv3x3: this geometry has no halo form (tile 11 / 12)")
-        p.tile = 12 if upsample else 11
+    if p.tile == 13:
+        if not phase_ok:
+            raise ValueError("planes.conv3x3: this geometry has no phase form (tile 13)")
         p.splits = min(p.splits, (C1 + C2) // 32)
+        wp = hip.x3_upsample_phase_planes(w, W_SCALE)       # [2, 4, Cout, 4 C]: the 9-tap planes of this weight are never made
+        if wp is None:
+            raise RuntimeError("phase weight planes missing while capturing: run one eager forward first")
+        K = 4 * (C1 + C2)
+        p.K = K
+    else:
+        if p.tile in (11, 12):
+            if not halo_ok:
+                raise ValueError("planes.conv3x3: this geometry has no halo form (tile 11 / 12)")
+            p.tile = 12 if upsample else 11
+            p.splits = min(p.splits, (C1 + C2) // 32)
+        wp = weight_planes(w)
+    p.W, p.planeW, p.ldw = wp.data_ptr(), wp.stride(0), K
     ws = None
     if p.splits > 1:
         ws = torch.empty(p.splits * M * Cout, dtype=torch.float32, device=x.device)     # noqa: F841
         p.ws = ws.data_ptr()
     nbytes = 4.0 * (B * Hp * Wp * (C1 + C2) + M * (CE1 + CE2) + Cout * K + M * Cout * ((1 if o32 is not None else 0) + (1 if op is not None else 0) + (1 if residual is not None else 0)))
-    kn = f"conv3x3_halo_x3p_kernel<{'true' if upsample else 'false'}>" if p.tile in (11, 12) else f"igemm_x3p_kernel<true> t{p.tile}"
+    # (tile 13: K is 4 (C1 + C2) here, so the FLOPs, weight bytes and staged bytes below are the four taps the launch executes)
+    kn = "conv3x3_halo_x3p_kernel_phase" if p.tile == 13 else \
+        f"conv3x3_halo_x3p_kernel<{'true' if upsample else 'false'}>" if p.tile in (11, 12) else f"igemm_x3p_kernel<true> t{p.tile}"
     kn += f" {M}x{Cout}x{K} s{p.splits}" if hip.PROF_SHAPES else ""
-    if p.tile in (11, 12):      # halo form: per (256-pixel, 80-column) workgroup the weights of nine taps + ONE input super-tile per channel block
+    if p.tile == 13:            # per (256 source pixels, 80 columns, phase) workgroup the weights of four taps + one source super-tile per channel block
+        hip.note_staged(kn, 4.0 * (C1 + C2) * (4 * 80 + 256 + 2 * (Wp + 1)) * -(-(M // 4) // 256) * -(-Cout // 80) * 4)
+    elif p.tile in (11, 12):    # halo form: per (256-pixel, 80-column) workgroup the weights of nine taps + ONE input super-tile per channel block
         hip.note_staged(kn, 4.0 * (C1 + C2) * (9 * 80 + 256 + 2 * (Wd + 1)) * -(-M // 256) * -(-Cout // 80))
     else:
         bm, bn = _TILES[p.tile]

@@ -486,7 +486,9 @@ typedef struct IefGemmX3pParams {
     float inv_scale;                          /* 1 / (activation scale * weight scale) */
     int tile;                                 /* 1: 128x160 (8 waves), 2: the same + 4 loader waves, 3: 128x80 (4 waves), 4: 256x160 (8 waves),
                                                  5: 64x160 (4 waves), 6: 128x64 (4 waves; widths that are multiples of 64 only), 7: 128x160 on 4 waves (two workgroups per CU), 8: 256x320 (8 waves of 64 x 160; the fewest staged bytes per FLOP: wide N only); 11 / 12: conv3x3_halo_x3p (256x80, 8 waves + 4 loader waves;
-                                                 plain 3x3 stride 1 pad 1, rows of <= 64 pixels; 12: nearest-2x fused) */
+                                                 plain 3x3 stride 1 pad 1, rows of <= 64 pixels; 12: nearest-2x fused); 13: nearest-2x in PHASE form
+                                                 (ups = 1, W = the planes of ief_x3_upsample_phase_weights, K = 4 (C1 + C2), source rows of <= 64 pixels:
+                                                 four 2x2 convolutions of the low-resolution image, the phase in grid.z) */
     int splits;                               /* split-K over grid.y: fp32 slabs ws[splits][M][N] summed in slab order by a second launch */
     float* ws;
     int geglu;                                /* weight rows interleaved [8 hidden | 8 gate]: out [M][N / 2] = hidden * gelu(gate) */
@@ -508,6 +510,12 @@ typedef struct IefGemmX3pParams {
     float ln_eps;
 } IefGemmX3pParams;
 int ief_gemm_x3p(const IefGemmX3pParams* p, void* stream);
+/* Upsample2D's weight in PHASE form for tile 13: w fp32 [Cout][3][3][C] (16-byte aligned, C % 4 == 0) -> fp16 planes
+ * [2][4 phases (py, px)][Cout][4 taps (sy, sx)][C] at `scale`.  Output pixel (2y + py, 2x + px) of nearest-2x + 3x3 / pad 1 is a 2x2
+ * convolution of the low-resolution image over the taps ty = py + sy, tx = px + sx (3x3 indexing: tap t = low-res row y + t - 1);
+ * a phase tap is the fp32 sum, in increasing (ky, kx) order, of the original weights that read that low-res pixel
+ * (p = 0: t 0 <- k {0}, t 1 <- k {1, 2}; p = 1: t 1 <- k {0, 1}, t 2 <- k {2}), split as ief_x3_split_weights does. */
+int ief_x3_upsample_phase_weights(const float* w, void* planes, int Cout, int C, float scale, void* stream);
 int ief_gemm_x3p_tile_bm(int tile);
 int ief_gemm_x3p_tile_bn(int tile);
 /* columns one wave owns in a tile (the width of a row-statistics slice): 80, tile 6: 64 */
