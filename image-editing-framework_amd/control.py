@@ -34,6 +34,12 @@ the same effect is expressed as small device tables, so no map is ever written t
       with c >= 1 earlier slots turns the first c slots into packed class bits (`ief_masa_auto_classes`) and ONE class-masked
       launch over all source keys overwrites the two target rows; the per-step gate switches both off in uncontrolled steps.
       c is a property of the layer's place in the execution order (static); thres, the multiplicities and the gate are data
+  MasaCtrl with united source and target keys (/root/reference/masactrl/model/attention_control.py:71-107), same batch: a
+      target row attends with its own queries over [K_src ; K_tgt] of its half, ONE softmax over 2 N keys, source keys first;
+      the source rows are plain self-attention (what the reference intends; its own call for them raises, see the class).  The
+      planes attention walks two key / value segments from two batch rows (`k2_src / v2_src`): the mutual table
+      [0, 0, 2, 2] as the first segment's rows and a second table [-1, 1, -1, 3] -- ONE launch per controlled layer for all
+      four rows, identity / -1 rows in the uncontrolled steps, so a captured graph needs no gate
   Plug-and-Play injection (/root/reference/pnp/model/register.py:27-90,100-182), batch = 4 blocks of s rows
       [uncond_src, uncond_tgt, cond_src, cond_tgt]: during the first qk_steps timesteps the self-attention of the chosen
       decoder layers computes rows of blocks 1 and 3 with the Q and K of block 2 (:45-52), and during the first
@@ -88,8 +94,8 @@ class StepCounter:
 
 
 class ControlPlan:
-    """kind: 'empty' | 'p2p' | 'masactrl' | 'masactrl_mask' | 'masactrl_mask_auto' | 'pnp'"""
-    MASA_KINDS = ("masactrl", "masactrl_mask", "masactrl_mask_auto")
+    """kind: 'empty' | 'p2p' | 'masactrl' | 'masactrl_mask' | 'masactrl_mask_auto' | 'masactrl_union' | 'pnp'"""
+    MASA_KINDS = ("masactrl", "masactrl_mask", "masactrl_mask_auto", "masactrl_union")
     GATED_KINDS = ("masactrl_mask", "masactrl_mask_auto")
     MAP_TOKENS, CTX_TOKENS = 256, 77
 
@@ -161,6 +167,7 @@ class ControlPlan:
         self.masa_steps = set(int(s) for s in masa_steps)
         self.masa_layers = set(int(l) for l in masa_layers)
         self._masa = {}
+        self._union = {}                           # masactrl_union: B -> (second-segment table int32 [steps, B], its current row)
         self._step_synced = -1
         # masactrl_mask: the two binary masks (host fp32 [h, w]), the token counts of the controlled layers (their lists are
         # built by prepare), per N the four device lists, and the per-step gate of the gathered launches
@@ -182,8 +189,42 @@ class ControlPlan:
         self.pnp_qk_steps, self.pnp_conv_steps = int(pnp_qk_steps), int(pnp_conv_steps)
         self._pnp = {}                             # B -> (qk_table, qk_cur, conv_table, conv_cur)
 
+    @staticmethod
+    def masa_table(masa_steps, B: int):
+        """host int32 [steps, B]: the K / V source rows of mutual self-attention per step -- every row of a half reads that half's
+        first row in the controlled steps, itself otherwise; one identity row past the last controlled step"""
+        n = (max(masa_steps) + 2) if masa_steps else 1
+        ident = torch.arange(B, dtype=torch.int32)
+        src = ident.clone()
+        half = B // 2
+        if half > 0:
+            src[:half] = 0
+            src[half:] = half
+        tab = ident.repeat(n, 1)
+        for st in masa_steps:
+            tab[int(st)] = src
+        return tab.contiguous()
+
+    @classmethod
+    def union_tables(cls, masa_steps):
+        """host int32 tables of 'masactrl_union' for the batch [u_src, u_tgt, c_src, c_tgt], both [steps, 4] with one
+        uncontrolled row past the last controlled step: (first-segment rows = `masa_table`: [0, 0, 2, 2] in the controlled
+        steps, identity otherwise; second-segment rows: [-1, 1, -1, 3] in the controlled steps -- a target row appends its
+        own keys behind its half's source keys -- and -1 everywhere otherwise: no second segment)"""
+        tab = cls.masa_table(masa_steps, 4)
+        k2 = torch.full_like(tab, -1)
+        for st in masa_steps:
+            k2[int(st)] = torch.tensor([-1, 1, -1, 3], dtype=torch.int32)
+        return tab, k2.contiguous()
+
     def prepare(self, B: int):
         """allocate per-batch device tables OUTSIDE any graph capture"""
+        if self.kind == "masactrl_union":
+            if B != 4:
+                raise RuntimeError(f"MasaCtrl Union acts on the UNet batch [u_src, u_tgt, c_src, c_tgt]; got batch {B}")
+            if B not in self._union:
+                k2 = self.union_tables(self.masa_steps)[1]
+                self._union[B] = (k2.to(self.device), torch.full((B,), -1, dtype=torch.int32, device=self.device))
         if self.kind in self.GATED_KINDS:
             if B != 4:
                 raise RuntimeError(f"mask-guided MasaCtrl acts on the UNet batch [u_src, u_tgt, c_src, c_tgt]; got batch {B}")
@@ -209,18 +250,9 @@ class ControlPlan:
                     if c >= 1:
                         self._class_words(ei, N)
         if self.kind in self.MASA_KINDS and B not in self._masa:
-            n = (max(self.masa_steps) + 2) if self.masa_steps else 1
-            self.num_steps = max(self.num_steps, n - 1)
-            ident = torch.arange(B, dtype=torch.int32)
-            src = ident.clone()
-            half = B // 2
-            if half > 0:
-                src[:half] = 0
-                src[half:] = half
-            tab = ident.repeat(n, 1)
-            for st in self.masa_steps:
-                tab[st] = src
-            self._masa[B] = (tab.contiguous().to(self.device), ident.clone().to(self.device))
+            tab = self.masa_table(self.masa_steps, B)
+            self.num_steps = max(self.num_steps, tab.shape[0] - 1)
+            self._masa[B] = (tab.to(self.device), torch.arange(B, dtype=torch.int32, device=self.device))
         if self.kind == "pnp" and B not in self._pnp:
             ident = torch.arange(B, dtype=torch.int32)
             inj = ident.clone()
@@ -405,6 +437,8 @@ class ControlPlan:
             return sig if self.blend_w is None else sig + ("blend", self.blend_modules)
         if self.kind == "masactrl":
             return ("masactrl", tuple(sorted(self.masa_layers)), (max(self.masa_steps) + 2) if self.masa_steps else 1)
+        if self.kind == "masactrl_union":     # one two-segment launch per controlled layer in every step; both tables are data
+            return ("masactrl_union", tuple(sorted(self.masa_layers)), (max(self.masa_steps) + 2) if self.masa_steps else 1)
         if self.kind == "masactrl_mask":      # the list LENGTHS are launch arguments (grid, N, L); their contents are data
             # Computed from the masks, so asking builds nothing.  NOTE: it covers `mask_tokens`, which states the UNet's
             # configured sample size until a forward at another latent size adds its counts (mask_lists) -- denoise keys a
@@ -443,6 +477,12 @@ class ControlPlan:
             other.prepare(B)
             self.masa_steps = set(other.masa_steps)
             self._masa[B][0].copy_(other._masa[B][0])
+        elif self.kind == "masactrl_union":
+            other.prepare(B)
+            self.prepare(B)
+            self.masa_steps = set(other.masa_steps)
+            self._masa[B][0].copy_(other._masa[B][0])
+            self._union[B][0].copy_(other._union[B][0])
         elif self.kind == "masactrl_mask":
             other.prepare(B)
             self.prepare(B)
@@ -509,6 +549,8 @@ class ControlPlan:
             hip.select_step(tab, cur, self.step)
             if self.kind in self.GATED_KINDS:       # the gate table has the same rows: 0 in the identity row past the end
                 hip.select_step(self._gate[0], self._gate[1], self.step)
+            if self.kind == "masactrl_union":       # the second-segment table has the same rows: -1 in the row past the end
+                hip.select_step(self._union[B][0], self._union[B][1], self.step)
         elif self.kind == "pnp":
             if B not in self._pnp:
                 if self.captured:
@@ -553,6 +595,13 @@ class ControlPlan:
             cur = self._pnp[B][1]
             return cur, cur, None
         return None, None, None
+
+    def second_sources(self, B: int, attn):
+        """'masactrl_union', a controlled self-attention layer: the current second-segment rows (`k2_src = v2_src` of the planes
+        attention, beside the `self_sources` rows of the first segment); None everywhere else"""
+        if self.kind == "masactrl_union" and not self.muted and (attn._exec_index // 2) in self.masa_layers:
+            return self._union[B][1]
+        return None
 
     def feature_source(self, B: int):
         """source rows of the Plug-and-Play feature injection for the CURRENT step (identity outside its schedule)"""

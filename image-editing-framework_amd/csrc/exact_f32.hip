@@ -471,6 +471,12 @@ extern "C" int ief_attn_flash_f32(const IefAttnF32Params* pp, void* stream) {
     if (!p.x3 && (!p.Out || (p.ldo & 3) || (p.sOb & 3))) return IEF_EINVAL;
     if (!p.x3 && p.lse) return IEF_EINVAL;                // only the split-operand kernels write the row log-sum-exp
     if (p.key_splits > 1 && (!p.x3 || !p.Qp)) return IEF_EINVAL;     // only the operand-planes kernel splits its keys over workgroups
+    if (p.k2_src || p.v2_src) {                           // two key / value segments: the operand-planes kernel only, both tables, combined with no other form
+        if (!p.x3 || !p.Qp || !p.k2_src || !p.v2_src || p.lse || p.key_splits > 1 || p.q_idx || p.k_idx || p.q_cls || p.k_cls)
+            return IEF_EINVAL;
+        if (((uintptr_t)p.k2_src | (uintptr_t)p.v2_src) & 3) return IEF_EALIGN;
+        if (p.d != 40 && p.d != 64 && p.d != 80) return IEF_ESHAPE;
+    }
     if (p.q_cls || p.k_cls) {                             // class-masked: the operand-planes kernel only, both class words, no lse, no key split, no lists
         if (!p.x3 || !p.Qp || !p.q_cls || !p.k_cls || p.lse || p.key_splits > 1 || p.q_idx || p.k_idx || (p.N & 31) || (p.L & 31))
             return IEF_EINVAL;

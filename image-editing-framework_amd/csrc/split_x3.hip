@@ -938,10 +938,22 @@ __global__ __launch_bounds__(256, (D > 80) ? 1 : 2) void attn_flash_x3_kernel(co
 // rescale factor and in the exponent's bias would be NaN); exp2(-1e30 - m) is still exactly 0 once a real score arrives.  The gate
 // as for IDX.  What the form is for: masks that are DATA (made on the device per step and layer), where the gathered lists'
 // lengths cannot be launch arguments -- one launch for both classes.
-template <int D, int KS, int NWV, bool LSE = false, bool SPLIT = false, bool IDX = false, bool CLS = false>
+// UNI (the last instantiation of its own; with none of the four above): ONE softmax over TWO key / value segments taken from two
+// batch rows.  Output row b with k2 = k2_src[b] >= 0 walks the nt1 = ceil(L / KT) tiles of batch row k_src[b] and then the nt1
+// tiles of batch row k2 (V rows v_src[b], v2_src[b] alike) through the same online softmax, lazy maximum and normalisation; a row
+// with k2 < 0 walks the first segment only -- the plain launch's tiles in the plain launch's order, so its bits.  Everything the
+// switch needs is wave-uniform and scalar: the second segment's plane bases are the first's plus (k2 - bk) sKb, (v2 - bv) sVb, and
+// the segment of a tile is (t >= nt1), derived from the tile index both where the tile is ISSUED (one tile ahead of the loop,
+// so it crosses the boundary first) and where it is MASKED; no state is carried that the two places could disagree on.  The
+// key tail (key >= L) and the zero-page rows (row >= L) are in terms of the segment-LOCAL index: with L % KT != 0 the first
+// segment's last tile has masked keys in the middle of the walk, which the running maximum (finite by then) turns into exact
+// zeros.  What the form is for: MasaCtrl's Union editor (control.py, kind 'masactrl_union') -- source rows plain, target rows
+// over [K_src ; K_tgt], all four rows of a controlled layer in one launch.
+template <int D, int KS, int NWV, bool LSE = false, bool SPLIT = false, bool IDX = false, bool CLS = false, bool UNI = false>
 __global__ __launch_bounds__(64 * NWV, D <= 40 ? 4 : 2) void attn_flash_x3p_kernel(const IefAttnF32Params p) {
     static_assert(!IDX || (!LSE && !SPLIT), "the gathered launch writes no lse and does not split its keys");
     static_assert(!CLS || (!LSE && !SPLIT && !IDX), "the class-masked launch writes no lse, does not split its keys and gathers nothing");
+    static_assert(!UNI || (!LSE && !SPLIT && !IDX && !CLS), "the two-segment launch is combined with none of the other forms");
     if constexpr (IDX || CLS) {
         if (p.gate && *p.gate == 0) return;      // uniform over the grid: nobody reaches a barrier
     }
@@ -970,6 +982,17 @@ __global__ __launch_bounds__(64 * NWV, D <= 40 ? 4 : 2) void attn_flash_x3p_kern
         srcs[pl] = (const char*)(pl < 2 ? p.Kp + (long long)bk * p.sKb + (pl & 1) * p.planeK
                                         : p.Vp + (long long)bv * p.sVb + (pl & 1) * p.planeV) + (long long)h * D * 2;
     const char* zp = (const char*)p.zeros;
+    // UNI: tiles of one segment, and what the second segment's K / V planes lie further than the first's (bytes; wave-uniform)
+    const int nt1 = (p.L + KT - 1) / KT;
+    int k2 = -1;
+    long long seg2K = 0, seg2V = 0;
+    if constexpr (UNI) {
+        k2 = p.k2_src[b];
+        if (k2 >= 0) {
+            seg2K = (long long)(k2 - bk) * p.sKb * 2;
+            seg2V = (long long)(p.v2_src[b] - bv) * p.sVb * 2;
+        }
+    }
     float* O = p.Out ? p.Out + (long long)b * p.sOb + (long long)h * D : nullptr;
     half_t* OP = p.OutP ? p.OutP + (long long)b * p.sOPb + (long long)h * D : nullptr;
     const int q0 = qb * (32 * NWV) + wid * 32;
@@ -1014,14 +1037,18 @@ __global__ __launch_bounds__(64 * NWV, D <= 40 ? 4 : 2) void attn_flash_x3p_kern
         }
     };
     auto issue = [&](int t, int buf) {
+        const bool seg2 = UNI && t >= nt1;                   // wave-uniform; from the tile index alone
+        const int tl = seg2 ? t - nt1 : t;                   // the tile inside its segment
 #pragma unroll
         for (int i = 0; i < NPW; ++i) {
             const int q = wid + NWV * i;                     // wave-uniform
             if (q < 4 * NP) {
                 const int pl = q / NP, j = q - pl * NP;
-                const int row = t * KT + s_row[i];
+                const int row = tl * KT + s_row[i];
                 const int ldr = pl < 2 ? p.ldk : p.ldv;
-                const char* g = row < p.L ? srcs[pl] + (long long)(AHEAD ? k_row[i] : IDX ? *(const int*)((const char*)p.k_idx + (unsigned)row * 4u) : row) * ldr * 2 + s_off[i] : zp;
+                const char* base = srcs[pl];
+                if constexpr (UNI) base += seg2 ? (pl < 2 ? seg2K : seg2V) : 0ll;
+                const char* g = row < p.L ? base + (long long)(AHEAD ? k_row[i] : IDX ? *(const int*)((const char*)p.k_idx + (unsigned)row * 4u) : row) * ldr * 2 + s_off[i] : zp;
                 x3_glds16(g, smem_p + buf * (4 * PL) + pl * PL + j * 512);
             }
         }
@@ -1052,7 +1079,8 @@ __global__ __launch_bounds__(64 * NWV, D <= 40 ? 4 : 2) void attn_flash_x3p_kern
     // CLS: the class word of this wave's 32 queries (q0 is a multiple of 32; a wave past N reads nothing and stores nothing)
     unsigned qw = 0;
     if constexpr (CLS) qw = q0 < p.N ? p.q_cls[q0 >> 5] : 0u;
-    int nt = (p.L + KT - 1) / KT, t_beg = 0;
+    int nt = nt1, t_beg = 0;
+    if constexpr (UNI) nt = k2 >= 0 ? 2 * nt1 : nt1;
     if constexpr (SPLIT) {
         const int T = (nt + (int)gridDim.z - 1) / (int)gridDim.z;
         t_beg = (int)blockIdx.z * T;
@@ -1097,12 +1125,13 @@ __global__ __launch_bounds__(64 * NWV, D <= 40 ? 4 : 2) void attn_flash_x3p_kern
         }
         __builtin_amdgcn_s_setprio(0);
         // online softmax (register r <-> key (r & 3) + 8 (r >> 2) + 4 lh of its sub-tile)
+        const int tl = (UNI && t >= nt1) ? t - nt1 : t;    // UNI: the tile inside its segment, from the tile index as in issue
 #pragma unroll
         for (int u = 0; u < KS; ++u) {
-            if (t * KT + (u + 1) * 32 > p.L) {    // wave-uniform: only the tile that crosses L is masked
+            if (tl * KT + (u + 1) * 32 > p.L) {   // wave-uniform: only the tile that crosses L is masked
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int key = t * KT + u * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                    const int key = tl * KT + u * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
                     if (key >= p.L) sacc[u][r] = -INFINITY;
                 }
             }
@@ -1302,6 +1331,17 @@ int ief_attn_flash_x3_dispatch(const IefAttnF32Params& p, hipStream_t st) {
         if (!p.Kp || !p.Vp || !p.zeros) return IEF_EINVAL;
         if ((p.ldq & 7) || (p.ldk & 7) || (p.ldv & 7) || (p.sQb & 7) || (p.sKb & 7) || (p.sVb & 7) || (p.planeQ & 7) || (p.planeK & 7) ||
             (p.planeV & 7) || (((uintptr_t)p.Qp | (uintptr_t)p.Kp | (uintptr_t)p.Vp) & 15)) return IEF_EALIGN;
+        if (p.k2_src || p.v2_src) {              // two key / value segments (ief_attn_flash_f32 has refused a missing half of the pair, lse, key_splits > 1, lists, classes)
+#define FLASHP_UNI_GO(D_, KS_, NWV_, G_) hipLaunchKernelGGL((attn_flash_x3p_kernel<D_, KS_, NWV_, false, false, false, false, true>), G_, dim3(64 * NWV_), 0, st, p)
+            switch (p.d) {
+                case 40: FLASHP_UNI_GO(40, 2, 8, grid8); break;
+                case 64: FLASHP_UNI_GO(64, 1, 4, grid); break;
+                case 80: FLASHP_UNI_GO(80, 1, 4, grid); break;
+                default: return IEF_ESHAPE;
+            }
+            IEF_LAUNCH_CHECK();
+            return IEF_OK;
+        }
         if (p.q_cls || p.k_cls) {                // class-masked (ief_attn_flash_f32 has refused lse, key_splits > 1, lists, a missing pointer, N or L % 32)
 #define FLASHP_CLS_GO(D_, KS_, NWV_, G_) hipLaunchKernelGGL((attn_flash_x3p_kernel<D_, KS_, NWV_, false, false, false, true>), G_, dim3(64 * NWV_), 0, st, p)
             switch (p.d) {

@@ -12,7 +12,8 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 from _bootstrap import load_pipe, seed_everything  # noqa: E402
 
 from ief_amd.masactrl.model.attention_control import (MutualSelfAttentionControl, MutualSelfAttentionControlMask,  # noqa: E402
-                                                      MutualSelfAttentionControlMaskAuto, load_mask_png)
+                                                      MutualSelfAttentionControlMaskAuto, MutualSelfAttentionControlUnion,
+                                                      load_mask_png)
 from ief_amd.masactrl.model.register import regiter_attention_editor_diffusers, unregister_attention_control  # noqa: E402
 from ief_amd.masactrl.model.sd_utils import MasaCtrl, MasaCtrl_NTI, MasaCtrl_XL, MasaCtrl_XL_NTI  # noqa: E402
 from ief_amd.p2p.inversion.ddim import ddim_inversion, ddim_inversion_xl  # noqa: E402
@@ -37,16 +38,20 @@ parser.add_argument("--thres", type=float, default=0.1)
 parser.add_argument("--ref_token_idx", type=int, nargs="+", default=[1])
 parser.add_argument("--cur_token_idx", type=int, nargs="+", default=[1])
 parser.add_argument("--mask_save_dir", type=str, default=None)
+# --union: the target image attends over the source keys AND its own under one softmax (MutualSelfAttentionControlUnion); start
+# step and layer as the plain editor's; not together with --mask_s / --mask_t or --mask_auto
+parser.add_argument("--union", action="store_true")
 
 STEP, LAYPER = 4, 10
 NUM_INNER_STEPS, EARLY_STOP_EPSILON = 10, 1e-5
 
 
 def edit_one(pipe, editor, invertor, image, source_prompt, target_prompt, inversion_type, device, size,
-             num_inference_steps=50, guidance_scale=7.5, masks=None, auto=None):
+             num_inference_steps=50, guidance_scale=7.5, masks=None, auto=None, union=False):
     """invert + MasaCtrl-edit one PIL image -> uint8 images [2,H,W,3] (reconstruction, edit); :128-153 of the reference.
     masks: optional (mask_s, mask_t) fp32 [h, w] in {0, 1} -> the mask-guided editor; auto: optional dict(thres=, ref_token_idx=,
-    cur_token_idx=, mask_save_dir=) -> the editor that makes its masks from cross-attention"""
+    cur_token_idx=, mask_save_dir=) -> the editor that makes its masks from cross-attention; union: the editor with united
+    source and target keys"""
     latent = invertor.image2latent(model=pipe, image=image, device=device, dtype=torch.float32)
     latents, context = invertor.ddim_inversion_loop(pipe, latent, source_prompt)
     extra = {}
@@ -63,6 +68,8 @@ def edit_one(pipe, editor, invertor, image, source_prompt, target_prompt, invers
     elif masks is not None:
         controller = MutualSelfAttentionControlMask(STEP, 54 if xl else LAYPER, mask_s=masks[0], mask_t=masks[1],
                                                     model_type="SDXL" if xl else "SD")
+    elif union:
+        controller = MutualSelfAttentionControlUnion(STEP, 54 if xl else LAYPER, model_type="SDXL" if xl else "SD")
     else:
         controller = MutualSelfAttentionControl(STEP, 54 if xl else LAYPER, model_type="SDXL" if xl else "SD")
     regiter_attention_editor_diffusers(editor.model, controller)
@@ -90,6 +97,8 @@ def main(argv=None):
         parser.error("--mask_s and --mask_t go together")
     if args.mask_auto and args.mask_s is not None:
         parser.error("--mask_auto makes its own masks: not together with --mask_s / --mask_t")
+    if args.union and (args.mask_auto or args.mask_s is not None):
+        parser.error("--union takes no masks: not together with --mask_s / --mask_t or --mask_auto")
     device = torch.device("cuda:{}".format(args.device))
     seed_everything(args.seed)
     num_inference_steps = 50
@@ -104,7 +113,7 @@ def main(argv=None):
     images = edit_one(pipe, editor, invertor, original_image, [args.source_prompt], [args.target_prompt],
                       args.inversion_type, device, size, num_inference_steps, masks=masks,
                       auto=dict(thres=args.thres, ref_token_idx=args.ref_token_idx, cur_token_idx=args.cur_token_idx,
-                                mask_save_dir=args.mask_save_dir) if args.mask_auto else None)
+                                mask_save_dir=args.mask_save_dir) if args.mask_auto else None, union=args.union)
     save_img(images[0], os.path.join(out_path, "inversion.png"))
     save_img(images[1], os.path.join(out_path, "edit.png"))
 

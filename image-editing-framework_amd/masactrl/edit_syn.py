@@ -11,7 +11,8 @@ from _bootstrap import load_pipe, seed_everything  # noqa: E402
 
 from ief_amd.masactrl.model.attention_base import AttentionBase  # noqa: E402
 from ief_amd.masactrl.model.attention_control import (MutualSelfAttentionControl, MutualSelfAttentionControlMask,  # noqa: E402
-                                                      MutualSelfAttentionControlMaskAuto, load_mask_png)
+                                                      MutualSelfAttentionControlMaskAuto, MutualSelfAttentionControlUnion,
+                                                      load_mask_png)
 from ief_amd.masactrl.model.register import regiter_attention_editor_diffusers  # noqa: E402
 from ief_amd.masactrl.model.sd_utils import MasaCtrl  # noqa: E402
 from ief_amd.p2p.utils.save_image import save_img  # noqa: E402
@@ -32,6 +33,9 @@ parser.add_argument("--thres", type=float, default=0.1)
 parser.add_argument("--ref_token_idx", type=int, nargs="+", default=[1])
 parser.add_argument("--cur_token_idx", type=int, nargs="+", default=[1])
 parser.add_argument("--mask_save_dir", type=str, default=None)
+# --union: the target image attends over the source keys AND its own under one softmax (MutualSelfAttentionControlUnion); start
+# step and layer as the plain editor's; not together with --mask_s / --mask_t or --mask_auto
+parser.add_argument("--union", action="store_true")
 
 
 def main(argv=None):
@@ -40,6 +44,8 @@ def main(argv=None):
         parser.error("--mask_s and --mask_t go together")
     if args.mask_auto and args.mask_s is not None:
         parser.error("--mask_auto makes its own masks: not together with --mask_s / --mask_t")
+    if args.union and (args.mask_auto or args.mask_s is not None):
+        parser.error("--union takes no masks: not together with --mask_s / --mask_t or --mask_auto")
     device = torch.device("cuda:{}".format(args.device))
     seed_everything(args.seed)
     num_inference_steps, GUIDANCE_SCALE, STEP, LAYPER = 50, 7.5, 4, 10
@@ -65,6 +71,8 @@ def main(argv=None):
     elif args.mask_s is not None:
         controller = MutualSelfAttentionControlMask(STEP, LAYPER, mask_s=load_mask_png(args.mask_s, device),
                                                     mask_t=load_mask_png(args.mask_t, device), model_type=model_type)
+    elif args.union:
+        controller = MutualSelfAttentionControlUnion(STEP, LAYPER, model_type=model_type)
     else:
         controller = MutualSelfAttentionControl(STEP, LAYPER, model_type=model_type)
     regiter_attention_editor_diffusers(editor.model, controller)

@@ -13,8 +13,12 @@ gathered flash-attention launches; everywhere else the bodies below run on the g
 
 `MutualSelfAttentionControlMaskAuto` (:192-330) needs no masks from the user: per controlled layer it makes them from the
 16 x 16 cross-attention maps the step has computed so far (`--mask_auto`).  In the f16x3 mode `register.py` lowers it to one
-class-masked flash-attention launch per controlled layer (`control.py`, kind 'masactrl_mask_auto').  The Union variant is
-not ported.
+class-masked flash-attention launch per controlled layer (`control.py`, kind 'masactrl_mask_auto').
+
+`MutualSelfAttentionControlUnion` (:71-107) is the variant with united keys for the same batch: a target row attends with its
+own queries over its half's source keys FOLLOWED by its own (one softmax over 2 N keys), the source rows attend to themselves
+(`--union`).  In the f16x3 mode `register.py` lowers it to one two-segment flash-attention launch per controlled layer
+(`control.py`, kind 'masactrl_union').
 """
 import os
 
@@ -39,10 +43,16 @@ class MutualSelfAttentionControl(AttentionBase):
         print("MasaCtrl at U-Net layers: ", self.layer_idx)
 
     def attn_batch(self, q, k, v, sim, attn, is_cross, place_in_unet, num_heads, **kwargs):
-        """all samples of q attend to ONE sample's k, v: [(b h), n, d] x [h, n, d] -> [b, n, h*d]"""
+        """all samples of q attend to the keys of k's samples, concatenated per head in sample order:
+        [(b h), n, d] x [(bk h), n, d] -> [b, n, h*d]; bk == 1 (ONE sample's k, v, all the mutual editor passes) leaves k and v
+        as they are"""
         bh, n, d = q.shape
         b = bh // num_heads
         qh = q.reshape(b, num_heads, n, d).permute(1, 0, 2, 3).reshape(num_heads, b * n, d)
+        bk = k.shape[0] // num_heads
+        if bk > 1:
+            k = k.reshape(bk, num_heads, -1, d).permute(1, 0, 2, 3).reshape(num_heads, -1, d)
+            v = v.reshape(bk, num_heads, -1, d).permute(1, 0, 2, 3).reshape(num_heads, -1, d)
         s = torch.bmm(qh, k.transpose(1, 2)) * kwargs.get("scale")
         out = torch.bmm(s.softmax(-1), v)                           # h (b n) d
         return out.reshape(num_heads, b, n, d).permute(1, 2, 0, 3).reshape(b, n, num_heads * d)
@@ -56,6 +66,36 @@ class MutualSelfAttentionControl(AttentionBase):
         out_u = self.attn_batch(qu, ku[:num_heads], vu[:num_heads], None, None, is_cross, place_in_unet, num_heads, **kwargs)
         out_c = self.attn_batch(qc, kc[:num_heads], vc[:num_heads], None, None, is_cross, place_in_unet, num_heads, **kwargs)
         return torch.cat([out_u, out_c], dim=0)
+
+
+class MutualSelfAttentionControlUnion(MutualSelfAttentionControl):
+    def __init__(self, start_step=4, start_layer=10, layer_idx=None, step_idx=None, total_steps=50, model_type="SD"):
+        """mutual self-attention with UNITED source and target keys, for the UNet batch [u_src, u_tgt, c_src, c_tgt].  At a
+        controlled (step, layer) row u_tgt attends with its own queries over [K_u_src ; K_u_tgt] with values
+        [V_u_src ; V_u_tgt] -- one softmax over 2 N keys, source keys first -- and row c_tgt likewise over its half; rows u_src
+        and c_src are plain self-attention on their own K, V.
+
+        The source rows are where this class leaves the reference's text: there the source branch calls the parent's
+        `forward` on ONE batch row, which at a controlled step halves the HEADS with `q.chunk(2)` and then asks einops for a
+        batch of (h / 2) // h = 0, so the reference raises at its first controlled layer and no run of it exists to compare
+        with.  Its comment ("source image branch") and the Mask / MaskAuto variants, whose source rows attend to themselves,
+        state the intent, and that is what is built here.  Any UNet batch other than 4 raises, where `chunk(4)` would split
+        it silently into something else."""
+        super().__init__(start_step, start_layer, layer_idx, step_idx, total_steps, model_type)
+        print("Using MutualSelfAttentionControlUnion")
+
+    def forward(self, q, k, v, sim, attn, is_cross, place_in_unet, num_heads, **kwargs):
+        if is_cross or self.cur_step not in self.step_idx or self.cur_att_layer // 2 not in self.layer_idx:
+            return AttentionBase.forward(self, q, k, v, sim, attn, is_cross, place_in_unet, num_heads, **kwargs)
+        h = num_heads
+        if q.shape[0] != 4 * h:
+            raise RuntimeError(f"Union acts on the UNet batch [u_src, u_tgt, c_src, c_tgt]; got batch {q.shape[0] // h}")
+        outs = []
+        for half in (0, 2):        # rows (src, tgt) of the uncond, then of the cond half
+            src, tgt, both = slice(half * h, (half + 1) * h), slice((half + 1) * h, (half + 2) * h), slice(half * h, (half + 2) * h)
+            outs.append(AttentionBase.forward(self, q[src], k[src], v[src], None, attn[src], is_cross, place_in_unet, h, **kwargs))
+            outs.append(self.attn_batch(q[tgt], k[both], v[both], None, None, is_cross, place_in_unet, h, **kwargs))
+        return torch.cat(outs, dim=0)
 
 
 def _save_mask_png(mask, path):

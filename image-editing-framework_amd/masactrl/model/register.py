@@ -9,8 +9,10 @@ device plan: the fused flash-attention kernel takes per-batch K/V source rows, w
 the planes attention runs (f16x3): the mutual launch plus two launches over gathered row lists (`control.py`,
 kind 'masactrl_mask'), and so is `MutualSelfAttentionControlMaskAuto`, whose masks come from the step's own 16 x 16
 cross-attention maps: two small kernels make packed class bits on the device and ONE class-masked launch per controlled layer
-reads them (kind 'masactrl_mask_auto').  `lower_editor` prints why when it cannot.  Any OTHER editor (a user subclass of
-`AttentionBase` or of the classes above, the Union variant) takes the GENERIC path: a closure with the reference's dataflow
+reads them (kind 'masactrl_mask_auto'), and `MutualSelfAttentionControlUnion`, whose target rows attend over their half's
+source keys followed by their own: ONE launch of the planes attention's two-segment form per controlled layer (kind
+'masactrl_union').  `lower_editor` prints why when it cannot.  Any OTHER editor (a user subclass of
+`AttentionBase` or of the classes above) takes the GENERIC path: a closure with the reference's dataflow
 (:10-48) on our kernels materialises `sim` and `attn` ([B*heads, N, L]) and calls the editor's Python, exactly as
 `p2p/model/register.py` does for controllers.
 """
@@ -144,6 +146,22 @@ def _lower_mask_editor(editor, device, unet):
                        mask_s=ms, mask_t=mt, mask_tokens=tokens)
 
 
+def _lower_union_editor(editor, device, unet):
+    """the fused plan of `MutualSelfAttentionControlUnion`, or None with one printed line saying why not.  The head dims of the
+    controlled layers are counted at the UNet's configured sample size"""
+    def no(why):
+        print(f"MasaCtrl Union takes the generic path: {why}")
+        return None
+
+    if unet is None or getattr(unet, "precision", None) != "f16x3" or not getattr(unet, "x3p", False) or not planes.FLASH_PLANES:
+        return no("the fused rule runs on the planes attention of the f16x3 mode only")
+    layers = set(int(l) for l in editor.layer_idx)
+    for d, _ in _controlled_self_layers(unet, layers):
+        if d not in planes.FLASH_PLANES_DIMS:
+            return no(f"a controlled layer has head dim {d}, outside the planes attention's {planes.FLASH_PLANES_DIMS}")
+    return ControlPlan(editor, "masactrl_union", device, masa_steps=editor.step_idx, masa_layers=layers)
+
+
 def lower_editor(editor, device, unet=None):
     name = type(editor).__name__
     if name == "AttentionBase":
@@ -154,6 +172,8 @@ def lower_editor(editor, device, unet=None):
         return _lower_mask_editor(editor, device, unet)
     if name == "MutualSelfAttentionControlMaskAuto":
         return _lower_auto_editor(editor, device, unet)
+    if name == "MutualSelfAttentionControlUnion":
+        return _lower_union_editor(editor, device, unet)
     return None
 
 

@@ -597,7 +597,7 @@ def attn_key_splits(B, heads, N, L, d, cus=None, setting="auto") -> int:
 
 
 def attn_flash(q, k, v, heads, scale, q_src=None, k_src=None, v_src=None, out=None, out_planes=True, lse=None, key_splits=1,
-               q_idx=None, k_idx=None, gate=None, q_cls=None, k_cls=None):
+               q_idx=None, k_idx=None, gate=None, q_cls=None, k_cls=None, k2_src=None, v2_src=None):
     """fused attention on operand planes: q [B,N,h*d], k / v [B,L,h*d] as Planes (column slices of the q|k|v GEMM's output are
     fine); K / V tiles are staged by LDS-DMA, nothing is split in the kernel (`attn_flash_x3p_kernel`).  Returns Planes (for
     to_out's GEMM) or, with out_planes=False, fp32.
@@ -614,10 +614,20 @@ def attn_flash(q, k, v, heads, scale, q_src=None, k_src=None, v_src=None, out=No
     class of token 32 w + i (N / 32 and L / 32 words, N and L multiples of 32, shared by all batch rows), and every query attends
     to the keys of its own class only, in ONE launch over all keys.  The destination must exist as for the lists (`out=` /
     `out_planes=` a Planes, [Bo, N, heads*d]); all its rows are written, q_src / k_src / v_src pick the operands' batch rows, gate
-    as above.  Not with lists, lse or a key split (ValueError)."""
+    as above.  Not with lists, lse or a key split (ValueError).
+    k2_src / v2_src (int32 device tables [B], both or neither): TWO key / value segments under one softmax -- output row b with
+    k2_src[b] >= 0 attends over the keys of batch row k_src[b] followed by those of batch row k2_src[b] (values v_src[b], v2_src[b]
+    alike), a row with k2_src[b] < 0 over the first segment only, bit-identical to the launch without the pair.  Not with lists,
+    class words, lse or a key split (ValueError)."""
     lib = hip.load()
     idx = q_idx is not None or k_idx is not None
     cls = q_cls is not None or k_cls is not None
+    uni = k2_src is not None or v2_src is not None
+    if uni and (k2_src is None or v2_src is None):
+        raise ValueError("planes.attn_flash: k2_src and v2_src go together")
+    if uni and (idx or cls or lse is not None or key_splits != 1):
+        raise ValueError("planes.attn_flash: a two-segment launch (k2_src / v2_src) takes no lists and no class words, writes no "
+                         "lse and does not split its keys")
     if idx and (q_idx is None or k_idx is None):
         raise ValueError("planes.attn_flash: q_idx and k_idx go together")
     if cls and (q_cls is None or k_cls is None):
@@ -688,6 +698,11 @@ def attn_flash(q, k, v, heads, scale, q_src=None, k_src=None, v_src=None, out=No
         p.B = B
         p.q_cls, p.k_cls, p.gate = q_cls.data_ptr(), k_cls.data_ptr(), _ptr(gate)
     p.q_src, p.k_src, p.v_src = _ptr(hip._devi32(q_src, "q_src")), _ptr(hip._devi32(k_src, "k_src")), _ptr(hip._devi32(v_src, "v_src"))
+    if uni:
+        hip._devi32(k2_src, "k2_src"), hip._devi32(v2_src, "v2_src")
+        if k2_src.numel() != B or v2_src.numel() != B:
+            raise ValueError(f"planes.attn_flash: k2_src / v2_src must have one entry per batch row ({B})")
+        p.k2_src, p.v2_src = k2_src.data_ptr(), v2_src.data_ptr()
     p.x3, p.zeros = 1, _zeros(q.device)
     if lse is not None:
         if tuple(hip._dev32(lse, "lse").shape) != (B, heads, N):
@@ -715,6 +730,8 @@ def attn_flash(q, k, v, heads, scale, q_src=None, k_src=None, v_src=None, out=No
         name = f"attn_flash_x3p_kernel<{d}, idx>"
     elif cls:
         name = f"attn_flash_x3p_kernel<{d}, cls>"
+    elif uni:
+        name = f"attn_flash_x3p_kernel<{d}, uni>"
     elif S > 1:
         nws = lib.ief_attn_flash_ws_floats(B, heads, N, L, d, S)
         ws = torch.empty(nws, dtype=torch.float32, device=q.device)

@@ -252,6 +252,9 @@ class Attention(nn.Module):
             qs = ks = vs = None
             if plan is not None:
                 qs, ks, vs = plan.self_sources(B, N, self)
+                if plan.second_sources(B, self) is not None:
+                    raise RuntimeError(f"{self.layer_name}: the Union plan's two key segments exist on the planes attention of the "
+                                       "f16x3 mode only")
             o = hip.attn_flash(q, k, v, self.heads, self.scale, q_src=qs, k_src=ks, v_src=vs)
         else:
             q = hip.gemm(x, self.to_q.weight) if ln is None else hip.gemm(x, self.ln_w, bias=self.ln_b, ln=ln)
@@ -305,8 +308,15 @@ class Attention(nn.Module):
             if planes.FLASH_PLANES and self.dim_head in planes.FLASH_PLANES_DIMS:
                 # the q|k|v GEMM writes planes only; the attention kernel stages K / V tiles by LDS-DMA and splits nothing
                 qkv = planes.gemm(xp, w_in, bias=b_in, ln=ln, out=False, out_planes=True)
-                o = planes.attn_flash(qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:], self.heads, self.scale, q_src=qs,
-                                      k_src=ks, v_src=vs, key_splits=self.attn_key_splits)
+                k2 = plan.second_sources(B, self) if plan is not None else None
+                if k2 is not None:
+                    # MasaCtrl Union: ONE launch for all four rows -- a target row walks its half's source keys (ks) and then its
+                    # own (k2) under one softmax, a source row (k2 = -1) its own keys only; the two-segment form never splits keys
+                    o = planes.attn_flash(qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:], self.heads, self.scale, q_src=qs,
+                                          k_src=ks, v_src=vs, k2_src=k2, v2_src=k2, key_splits=1)
+                else:
+                    o = planes.attn_flash(qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:], self.heads, self.scale, q_src=qs,
+                                          k_src=ks, v_src=vs, key_splits=self.attn_key_splits)
                 ml = plan.mask_launches(B, N, self) if plan is not None else None
                 if ml is not None:
                     # mask-guided MasaCtrl: the launch above did mutual attention for every row; the target rows are now
@@ -329,6 +339,9 @@ class Attention(nn.Module):
                 if plan is not None and (plan.mask_launches(B, N, self) is not None or plan.auto_launch(B, N, self) is not None):
                     raise RuntimeError(f"mask-guided MasaCtrl was lowered onto a layer of head dim {self.dim_head} that has no "
                                        "planes attention")
+                if plan is not None and plan.second_sources(B, self) is not None:
+                    raise RuntimeError(f"MasaCtrl Union was lowered onto a layer of head dim {self.dim_head} that has no planes "
+                                       "attention")
                 o = hip.attn_flash(qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:], self.heads, self.scale, q_src=qs, k_src=ks,
                                    v_src=vs, out_planes=True)
         else:

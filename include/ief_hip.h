@@ -326,6 +326,17 @@ typedef struct IefAttnF32Params {
      * until the stream passes; ws_floats: its size.  Without Qp or with x3 == 0, key_splits > 1 is IEF_EINVAL; so are a null or
      * short ws; a misaligned one is IEF_EALIGN. */
     int key_splits; float* ws; long long ws_floats;
+    /* operand planes in (Qp set) only, ABI 4; both null = the launches above (this pair sits in FRONT of the class words, which
+     * sit in front of the gathered-rows fields: those stay the last three of the block; callers set fields by name and the
+     * library checks ief_struct_size(6)).  TWO KEY / VALUE SEGMENTS under one softmax: k2_src / v2_src, device int32 [B].  Output
+     * row b with k2_src[b] >= 0 attends over the L keys of batch row k_src[b] (identity if k_src is null) FOLLOWED by the L
+     * keys of batch row k2_src[b], with the values of rows v_src[b] and v2_src[b] alike: one online softmax over 2 L keys, one
+     * normalisation.  A row with k2_src[b] < 0 takes the first segment only and is bit-identical to the launch without the
+     * pair; v2_src[b] is then not looked at.  Every entry >= 0 must be a batch row of K / V (the library cannot check device
+     * lists).  Both pointers or neither, no lse, no key_splits > 1, no q_idx / k_idx, no q_cls / k_cls, Qp set and x3 != 0:
+     * IEF_EINVAL otherwise; a pointer that is not 4-byte aligned: IEF_EALIGN.  Nothing is launched by a refused call.
+     * d in {40, 64, 80}. */
+    const int* k2_src; const int* v2_src;
     /* operand planes in (Qp set) only, ABI 4; both null = the launches above (the pair sits in FRONT of the gathered-rows
      * fields, which stay the last three of the block; callers set fields by name and the library checks ief_struct_size(6)).  CLASS-MASKED attention: every query
      * and every key carries one class bit, packed one uint32 per 32 consecutive tokens (bit i of word w = token 32 w + i): q_cls
