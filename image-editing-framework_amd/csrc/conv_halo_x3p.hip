@@ -1,7 +1,8 @@
 // 3x3 / stride 1 / pad 1 convolution on operand planes with the input tile RESIDENT in LDS across the nine taps (the split-operand
 // form of conv3x3_halo_kernel, gemm_conv.hip).
 //
-// Measured on igemm_x3p_kernel (ablation builds, tests/abl_x3p.sh): the 128 x 160 x 32 K tile needs 36 KiB of LDS-DMA for 960
+// Measured on igemm_x3p_kernel (timing-only builds that dropped one stage of the loop at a time; that switch has since been
+// removed from the sources): the 128 x 160 x 32 K tile needs 36 KiB of LDS-DMA for 960
 // matrix-pipe cycles per SIMD -- at the ~32 B/clk a CU fills its LDS from L2 the two are equal, and the loop runs at about half the
 // matrix rate.  The lever is fewer staged bytes per MFMA.  A workgroup here owns 256 CONSECUTIVE output pixels of the flattened
 // [B H W] axis x 80 output channels and, per 32-channel block, stages the pixel range m0 - (W + 1) .. m0 + 255 + W + 1 (the
@@ -87,7 +88,6 @@ __global__ __launch_bounds__(768) void conv3x3_halo_x3p_kernel(const IefGemmX3pP
     if (wave >= NW) {
         // ------------------------------------------------------------------------------------------------ loader waves
         const int l = wave - NW;
-        bool abl_prologue = true;                 // (ablation builds only: XP_ABL & 1 keeps the prologue's LDS-DMA, drops the loop's)
         const unsigned st_chunk = (unsigned)(XP_LANE_CHUNK(lane) * 16);
         const int ms_lane = st_row0 + (lane >> 2);
         const char* an_src = zp; long long an_pl = 0; unsigned an_cs = 0, an_c0 = 0; bool an_on = false;
@@ -105,7 +105,7 @@ __global__ __launch_bounds__(768) void conv3x3_halo_x3p_kernel(const IefGemmX3pP
             const int ms = ms_lane + 16 * q;
             const bool ok = exists && an_on && (unsigned)ms < (unsigned)src_pixels;
             const char* g = ok ? an_src + ((long long)pl * an_pl + (long long)((unsigned)ms * an_cs + an_c0) * 2 + st_chunk) : zp;
-            if (!(XP_ABL & 1) || abl_prologue) glds16(g, (half_t*)(smem + (exists ? pl * AD + buf_off + q * 1024 : DUMP)));
+            glds16(g, (half_t*)(smem + (exists ? pl * AD + buf_off + q * 1024 : DUMP)));
         };
         const long long w_lane = (long long)(n0 + (lane >> 2)) * p.K * 2 + st_chunk;
         auto issue_b = [&](int cb, int tap, bool on, int slot_off) {
@@ -117,7 +117,7 @@ __global__ __launch_bounds__(768) void conv3x3_halo_x3p_kernel(const IefGemmX3pP
                 const int pl = v >= NPB ? 1 : 0, q = v - pl * NPB;
                 const bool ok = exists && on && n0 + 16 * q + (lane >> 2) < p.N;
                 const char* g = ok ? (const char*)p.W + ((long long)pl * p.planeW * 2 + w_lane + (long long)(16 * q) * p.K * 2 + k0) : zp;
-                if (!(XP_ABL & 1) || abl_prologue) glds16(g, (half_t*)(smem + (exists ? BOFF + slot_off + pl * BPL + q * 1024 : DUMP)));
+                glds16(g, (half_t*)(smem + (exists ? BOFF + slot_off + pl * BPL + q * 1024 : DUMP)));
             }
         };
         auto n_issued = [](int tap) constexpr -> int { return 3 + (tap < ATAPS ? APT : 0); };
@@ -131,7 +131,6 @@ __global__ __launch_bounds__(768) void conv3x3_halo_x3p_kernel(const IefGemmX3pP
             asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
             XP_BARRIER();
         }
-        abl_prologue = false;
         int bs_prev = 4 * BBUF, bs = 0, bs_next = BBUF;
         for (int cbi = 0; cbi < nblk; ++cbi) {
             const int cb = cb_lo + cbi;
@@ -140,7 +139,7 @@ __global__ __launch_bounds__(768) void conv3x3_halo_x3p_kernel(const IefGemmX3pP
             const int steps_left = nsteps - cbi * 9;
             auto one_step = [&](auto tap_tag) {
                 constexpr int tap = decltype(tap_tag)::value;
-                if (!(XP_ABL & 1)) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n_issued((tap + 8) % 9) + n_issued((tap + 7) % 9)) : "memory");
+                asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n_issued((tap + 8) % 9) + n_issued((tap + 7) % 9)) : "memory");
                 XP_BARRIER();
                 if constexpr (tap < ATAPS) {
 #pragma unroll
@@ -189,9 +188,7 @@ __global__ __launch_bounds__(768) void conv3x3_halo_x3p_kernel(const IefGemmX3pP
         return (a_edge[i] & tmask) ? ZA : ad;
     };
     half8 ah[2][TM], al[2][TM], bh[TN], bl[TN];
-    bool abl_read_done = false;                   // (ablation builds only: XP_ABL & 2 keeps the first fragment reads, drops the loop's)
     auto read_a = [&](half8 (&h)[TM], half8 (&l)[TM], int abuf, int ky, int kx) {
-        if ((XP_ABL & 2) && abl_read_done) return;
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
             const int ad = a_addr(i, abuf, ky, kx);
@@ -218,19 +215,14 @@ __global__ __launch_bounds__(768) void conv3x3_halo_x3p_kernel(const IefGemmX3pP
         for (int j = 0; j < TN; ++j) {
 #pragma unroll
             for (int i = 0; i < TM; ++i) {
-                if (!(XP_ABL & 4)) {
-                    acc[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bl[j], ah[PAR][i], acc[j][i], 0, 0, 0);
-                    acc[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bh[j], al[PAR][i], acc[j][i], 0, 0, 0);
-                }
+                acc[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bl[j], ah[PAR][i], acc[j][i], 0, 0, 0);
+                acc[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bh[j], al[PAR][i], acc[j][i], 0, 0, 0);
                 acc[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bh[j], ah[PAR][i], acc[j][i], 0, 0, 0);
             }
             // this block's weight fragments of step t + 1 take the registers just consumed
-            if (!(XP_ABL & 2)) {
-                bh[j] = *(const half8*)(smem + bs_next + b_off[j]);
-                bl[j] = *(const half8*)(smem + bs_next + b_off[j] + BPL);
-            }
+            bh[j] = *(const half8*)(smem + bs_next + b_off[j]);
+            bl[j] = *(const half8*)(smem + bs_next + b_off[j] + BPL);
         }
-        abl_read_done = true;
         bs_next = bs_next == (NSB - 1) * BBUF ? 0 : bs_next + BBUF;
     };
     for (int cbi = 0; cbi < nblk; cbi += 2) {

@@ -165,14 +165,13 @@ __global__ __launch_bounds__(64 * (WAVES_M * WAVES_N + NL)) void igemm_x3p_kerne
         }
     };
 
-    bool abl_prologue = true;
     auto stage_tile = [&](int buf) {
         if (!stages_) return;
         half_t* base = smem + buf * SLOT + swave * (16 * BK);
 #pragma unroll
         for (int j = 0; j < G; ++j) {
             half_t* dst = (swave + NSW * j < P) ? base + NSW * j * (16 * BK) : smem + DUMP;        // wave-uniform
-            if (!(XP_ABL & 1) || abl_prologue) glds16(ptr[j], dst);
+            glds16(ptr[j], dst);
             if constexpr (TN > 5 && !CONV) ptr[j] += ((stepmask >> j) & 1u) ? BK * 2 : 0;      // the wide tile has no register for step[]
             else ptr[j] += step[j];
         }
@@ -213,10 +212,7 @@ __global__ __launch_bounds__(64 * (WAVES_M * WAVES_N + NL)) void igemm_x3p_kerne
         boff[j] = 2 * BM * BK + row * BK + ((fq ^ xp_swz(row)) << 3);
     }
     half8 ah[TM], al[TM], bh[TN], bl[TN];
-    bool abl_first = true;
     auto read_frags = [&](const half_t* S) {
-        if ((XP_ABL & 2) && !abl_first) return;
-        abl_first = false;
 #pragma unroll
         for (int i = 0; i < TM; ++i) { ah[i] = *(const half8*)(S + aoff[i]); al[i] = *(const half8*)(S + aoff[i] + BM * BK); }
 #pragma unroll
@@ -227,10 +223,8 @@ __global__ __launch_bounds__(64 * (WAVES_M * WAVES_N + NL)) void igemm_x3p_kerne
         for (int j = 0; j < TN; ++j)
 #pragma unroll
             for (int i = 0; i < TM; ++i) {
-                if (!(XP_ABL & 4)) {
-                    acc[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bl[j], ah[i], acc[j][i], 0, 0, 0);
-                    acc[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bh[j], al[i], acc[j][i], 0, 0, 0);
-                }
+                acc[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bl[j], ah[i], acc[j][i], 0, 0, 0);
+                acc[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bh[j], al[i], acc[j][i], 0, 0, 0);
                 acc[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bh[j], ah[i], acc[j][i], 0, 0, 0);
             }
     };
@@ -260,7 +254,6 @@ __global__ __launch_bounds__(64 * (WAVES_M * WAVES_N + NL)) void igemm_x3p_kerne
 #pragma unroll
     for (int s = 0; s < NS - 1; ++s)
         if (kt_lo + s < nk) stage_tile(s);
-    abl_prologue = false;
     if (NL > 0 && !computes) {
         for (int kt = kt_lo; kt < nk; kt += NS) {
 #pragma unroll

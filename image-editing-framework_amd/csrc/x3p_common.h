@@ -11,15 +11,8 @@ __device__ __forceinline__ void glds16(const char* g, half_t* lds_wave_base) {
 }
 
 #define XP_BK 32
-#ifndef XP_ABL
-#define XP_ABL 0        // timing-only ablation builds (outputs wrong): 1 no LDS-DMA in the loop, 2 no fragment reads, 4 one MFMA per block, 8 no barrier
-#endif
 #define XP_GROUP_M 8
-#if XP_ABL & 8
-#define XP_BARRIER() do {} while (0)
-#else
 #define XP_BARRIER() asm volatile("s_barrier" ::: "memory")
-#endif
 // LDS rows are 64 B (one 32-deep K tile of one plane); the slot (16-byte unit) of chunk c of row r is c ^ xp_swz(r).  With
 // xp_swz(r) = 2 * bit 2 of r the ds_read_b128 fragments of 16 CONSECUTIVE rows starting at ANY row are free of bank conflicts
 // (brute-forced over the instruction's four 16-lane groups {0-3,12-15,20-27}, {4-11,16-19,28-31}, ...; the tap shift of the

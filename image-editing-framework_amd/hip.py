@@ -8,6 +8,7 @@ is missing, or a tensor is not an fp16/fp32 device tensor of the documented layo
 Nothing of the ABI is declared here by hand: the parameter structs, every entry point's `restype` /
 `argtypes` and the header's constants are derived from `include/ief_hip.h` by `cabi.py`.
 """
+import collections
 import ctypes
 import os
 from ctypes import byref
@@ -319,21 +320,30 @@ _plans = None
 AUTOTUNE = os.environ.get("IEF_AUTOTUNE", "0") == "1"   # tune unseen shapes on first use (outside graph capture)
 
 
+def read_plans(path):
+    """{key: tuple} of a plan file (this module's and planes.py's); empty without the file or under IEF_NO_PLAN_TABLE=1"""
+    if not os.path.exists(path) or os.environ.get("IEF_NO_PLAN_TABLE", "0") == "1":
+        return {}
+    import json
+    with open(path) as f:
+        return {k: tuple(v) for k, v in json.load(f).items()}
+
+
+def write_plans(path, table):
+    import json
+    with open(path, "w") as f:
+        json.dump({k: list(v) for k, v in sorted(table.items())}, f, indent=0)
+
+
 def _plan_table():
     global _plans
     if _plans is None:
-        _plans = {}
-        if os.path.exists(_PLAN_FILE) and os.environ.get("IEF_NO_PLAN_TABLE", "0") != "1":
-            import json
-            with open(_PLAN_FILE) as f:
-                _plans = {k: tuple(v) for k, v in json.load(f).items()}
+        _plans = read_plans(_PLAN_FILE)
     return _plans
 
 
 def save_plans(path=None):
-    import json
-    with open(path or _PLAN_FILE, "w") as f:
-        json.dump({k: list(v) for k, v in sorted(_plan_table().items())}, f, indent=0)
+    write_plans(path or _PLAN_FILE, _plan_table())
 
 
 def heuristic_plan(M: int, N: int, K: int):
@@ -567,8 +577,9 @@ def _act32(t, name):
     return t
 
 
-def _rows_ld32(t, name):
-    _act32(t, name)
+def _rows_ld_of(t, name, dev):
+    """(rows, cols, ld) of a 2-D/3-D tensor whose leading dims collapse to rows with one stride; dev: the mode's tensor check"""
+    dev(t, name)
     cols = t.shape[-1]
     ld = t.stride(-2) if t.dim() >= 2 else cols
     rows = 1
@@ -577,6 +588,10 @@ def _rows_ld32(t, name):
     if t.dim() == 3 and t.shape[0] > 1 and t.stride(0) != t.shape[1] * ld:
         raise ValueError(f"{name}: batch stride must equal rows * ld")
     return rows, cols, ld
+
+
+def _rows_ld32(t, name):
+    return _rows_ld_of(t, name, _act32)
 
 
 def _dev32(t, name):
@@ -594,19 +609,110 @@ def _devi32(t, name):
 
 
 def _rows_ld(t, name):
-    """(rows, cols, ld) of a 2-D/3-D tensor whose leading dims collapse to rows with one stride."""
-    _dev16(t, name)
-    cols = t.shape[-1]
-    ld = t.stride(-2) if t.dim() >= 2 else cols
-    rows = 1
-    for s in t.shape[:-1]:
-        rows *= s
-    if t.dim() == 3 and t.shape[0] > 1 and t.stride(0) != t.shape[1] * ld:
-        raise ValueError(f"{name}: batch stride must equal rows * ld")
-    return rows, cols, ld
+    return _rows_ld_of(t, name, _dev16)
 
 
-# ------------------------------------------------------------------------------- GEMM / conv
+# ------------------------------------------------------------------------------- GEMM / conv: the launch front-end
+# What the six wrappers (`gemm` / `conv3x3` on fp16 and on fp32 storage here, `planes.gemm` / `planes.conv3x3`) have in common:
+# the geometry of a convolution (`conv_geometry`, shapes only) and the epilogue operands + split-K slabs of a launch
+# (`_fill_epilogue`).  A wrapper keeps the check of its own tensors, its parameter struct, its plan policy and its profile record.
+ConvGeometry = collections.namedtuple(
+    "ConvGeometry", "B Hp Wp C1 C2 CE1 CE2 Cout H Wd Ho Wo M K rows_per_batch halo_geom phase_geom")
+
+
+def _shape(t):
+    return None if t is None else tuple(t.shape)
+
+
+def conv_geometry(x, w, x2=None, extra=None, rowvec=None, residual=None, stride=1, upsample=False, pad_hi_only=False,
+                  who="conv3x3"):
+    """the geometry of one 3x3 convolution launch from SHAPES alone (tuples; `extra` = (e1, e2 | None)): x [B, Hp, Wp, C1],
+    x2 [B, Hp, Wp, C2], w [Cout, 3, 3, C1 + C2] or, with extra sources [B, Ho, Wo, CE] for the fused 1x1, [Cout, K];
+    rowvec [B | 1, Cout], residual [B, Ho, Wo, Cout].  (H, Wd) is the image the taps gather from (the nearest-2x of the source
+    under `upsample`), M x K the implicit GEMM.  halo_geom / phase_geom: whether the geometry fits the halo form (the input
+    super-tile resident in LDS across the taps) and the phase form of the fused nearest-2x (four 2x2 convolutions of the source:
+    the halo form's limits on the SOURCE image) -- each mode adds its own terms.  ValueError (prefixed `who`) on a mismatch."""
+    if len(x) != 4 or len(w) not in (2, 4):
+        raise ValueError(f"{who}: x must be NHWC [B, H, W, C] and w [Cout, 3, 3, C] or fused [Cout, K]")
+    B, Hp, Wp, C1 = x
+    C2 = 0
+    if x2 is not None:
+        if tuple(x2[:-1]) != (B, Hp, Wp):
+            raise ValueError(f"{who}: x2 spatial shape mismatch")
+        C2 = x2[-1]
+    H, Wd = (Hp * 2, Wp * 2) if upsample else (Hp, Wp)
+    pad_total = 1 if pad_hi_only else 2
+    Ho, Wo = (H + pad_total - 3) // stride + 1, (Wd + pad_total - 3) // stride + 1
+    Cout = w[0]
+    CE1 = CE2 = 0
+    if extra is not None:
+        e1, e2 = extra
+        for e in (e1, e2):
+            if e is not None and tuple(e[:-1]) != (B, Ho, Wo):
+                raise ValueError(f"{who}: extra sources must be contiguous NHWC at the output resolution")
+        CE1 = e1[-1]
+        CE2 = 0 if e2 is None else e2[-1]
+    M, K = B * Ho * Wo, 9 * (C1 + C2) + CE1 + CE2
+    if extra is not None:
+        if tuple(w) != (Cout, K):
+            raise ValueError(f"{who}: fused weight must be [Cout, 9*(C1+C2)+CE1+CE2]")
+    elif tuple(w[1:]) != (3, 3, C1 + C2):
+        raise ValueError(f"{who}: weight shape {tuple(w)} does not match C1+C2={C1 + C2}")
+    rows_per_batch = 0
+    if rowvec is not None:
+        if len(rowvec) != 2 or rowvec[1] != Cout or rowvec[0] not in (1, B):
+            raise ValueError(f"{who}: rowvec must be [B, Cout] or [1, Cout]")
+        rows_per_batch = Ho * Wo if rowvec[0] == B and B > 1 else B * Ho * Wo
+    if residual is not None and tuple(residual) != (B, Ho, Wo, Cout):
+        raise ValueError(f"{who}: residual must be contiguous [B, Ho, Wo, Cout]")
+    plain = stride == 1 and not pad_hi_only and extra is None and Hp >= 2
+    halo_geom = plain and ((not upsample and 2 <= Wd <= 64) or (upsample and Wd <= 128 and (H * Wd) % 256 == 0 and 256 % Wd == 0))
+    phase_geom = plain and upsample and 2 <= Wp <= 64
+    return ConvGeometry(B, Hp, Wp, C1, C2, CE1, CE2, Cout, H, Wd, Ho, Wo, M, K, rows_per_batch, bool(halo_geom), bool(phase_geom))
+
+
+def _fill_epilogue(p, rows_ld, who, M, N, device, bias=None, rowvec=None, rows_per_batch=0, residual=None, splits=1):
+    """the fields IefGemmParams, IefGemmF32Params and IefGemmX3pParams name alike: bias, rowvec / rows_per_batch, residual / ldr
+    (rows of one stride under the mode's `_rows_ld` / `_rows_ld32`, M x N) and, for splits > 1, splits / ws.  Returns the
+    split-K slabs (or None): the caller holds them until the launch is queued."""
+    p.bias = _ptr(_dev32(bias, "bias")) if bias is not None else None
+    if rowvec is not None:
+        p.rowvec, p.rows_per_batch = _dev32(rowvec, "rowvec").data_ptr(), rows_per_batch
+    if residual is not None:
+        Mr, Nr, ldr = rows_ld(residual, "residual")
+        if (Mr, Nr) != (M, N):
+            raise ValueError(f"{who}: residual shape mismatch")
+        p.residual, p.ldr = residual.data_ptr(), ldr
+    if splits <= 1:
+        return None
+    ws = torch.empty(splits * M * N, dtype=torch.float32, device=device)
+    p.splits, p.ws = splits, ws.data_ptr()
+    return ws
+
+
+def _conv_geometry_of(dev, x, w, x2, extra, rowvec, residual, stride, upsample, pad_hi_only):
+    """`conv_geometry` of the fp16 / fp32-storage convolution after the mode's tensor check `dev` of its operands"""
+    e1, e2 = (None, None) if extra is None else extra
+    for t, name in ((x, "x"), (w, "w"), (x2, "x2")):
+        if t is not None and not dev(t, name).is_contiguous():
+            raise ValueError("conv3x3: x, x2, w must be contiguous")
+    for e in (e1, e2):
+        if e is not None and not dev(e, "extra").is_contiguous():
+            raise ValueError("conv3x3: extra sources must be contiguous NHWC at the output resolution")
+    if residual is not None and not dev(residual, "residual").is_contiguous():
+        raise ValueError("conv3x3: residual must be contiguous [B, Ho, Wo, Cout]")
+    return conv_geometry(x.shape, w.shape, _shape(x2), None if extra is None else (e1.shape, _shape(e2)), _shape(rowvec),
+                         _shape(residual), stride, upsample, pad_hi_only)
+
+
+def _conv_out(dev, out, g, dtype, device):
+    if out is None:
+        return torch.empty(g.B, g.Ho, g.Wo, g.Cout, dtype=dtype, device=device)
+    if not dev(out, "out").is_contiguous() or out.numel() != g.M * g.Cout:
+        raise ValueError("conv3x3: out must be contiguous [B, Ho, Wo, Cout]")
+    return out
+
+
 def gemm(a, w, bias=None, residual=None, rowvec=None, rows_per_batch=0, out=None, out_scale=1.0, tile_hint=0, splits=1,
          stages=2, geglu=False, ln=None, row_stats=False, col_stats=False):
     """out[..., n] = (a[..., :] . w[n, :] + bias[n] + rowvec[row // rows_per_batch, n] + residual[..., n]) * out_scale
@@ -643,16 +749,8 @@ def gemm(a, w, bias=None, residual=None, rowvec=None, rows_per_batch=0, out=None
         raise ValueError("gemm: out shape mismatch")
     p = IefGemmParams()
     p.A, p.W, p.Out = a.data_ptr(), w.data_ptr(), out.data_ptr()
-    p.bias = _ptr(_dev32(bias, "bias")) if bias is not None else None
-    p.rowvec = _ptr(_dev32(rowvec, "rowvec")) if rowvec is not None else None
-    if residual is not None:
-        Mr, Nr, ldr = _rows_ld(residual, "residual")
-        if (Mr, Nr) != (M, N):
-            raise ValueError("gemm: residual shape mismatch")
-        p.residual, p.ldr = residual.data_ptr(), ldr
     p.M, p.N, p.K = M, N, K
     p.lda, p.ldw, p.ldo = lda, w.stride(0), ldo
-    p.rows_per_batch = rows_per_batch
     p.out_scale = out_scale
     if tile_hint == 0:
         if AUTOTUNE and f"gemm|{M}|{N}|{K}" not in _plan_table() and not _capturing() and _prof is None:
@@ -667,9 +765,8 @@ def gemm(a, w, bias=None, residual=None, rowvec=None, rows_per_batch=0, out=None
             p.tile_hint, p.splits, p.stages = heuristic_plan(M, N, K)[0], 1, 2
     else:
         p.tile_hint, p.splits, p.stages = tile_hint, max(1, splits), stages
-    if p.splits > 1:
-        ws = torch.empty(p.splits * M * N, dtype=torch.float32, device=a.device)
-        p.ws = ws.data_ptr()
+    ws = _fill_epilogue(p, _rows_ld, "gemm", M, N, a.device, bias, rowvec, rows_per_batch, residual, p.splits)
+    if ws is not None:
         nt, kb = _tile_count(lib, p.tile_hint, M, N, p.splits)
         p.cnt = _splitk_counters(a.device, nt, kb) if nt else None
     stats = None
@@ -706,53 +803,17 @@ def conv3x3(x, w, bias=None, x2=None, stride=1, upsample=False, rowvec=None, res
         o = _conv3x3_f32(x, w, bias, x2, stride, upsample, rowvec, residual, out, extra, pad_hi_only)
         return (o, None) if col_stats else o
     lib = load()
-    _dev16(x, "x")
-    _dev16(w, "w")
-    if not x.is_contiguous() or (x2 is not None and not x2.is_contiguous()) or not w.is_contiguous():
-        raise ValueError("conv3x3: x, x2, w must be contiguous")
-    B, Hp, Wp, C1 = x.shape
-    C2 = 0 if x2 is None else x2.shape[-1]
-    if x2 is not None and tuple(x2.shape[:3]) != (B, Hp, Wp):
-        raise ValueError("conv3x3: x2 spatial shape mismatch")
-    Cout = w.shape[0]
-    e1 = e2 = None
-    CE1 = CE2 = 0
-    if extra is not None:
-        e1, e2 = extra
-        CE1 = e1.shape[-1]
-        CE2 = 0 if e2 is None else e2.shape[-1]
-        for e in (e1, e2):
-            if e is not None and (not _dev16(e, "extra").is_contiguous() or tuple(e.shape[:3]) != (B, Hp, Wp)):
-                raise ValueError("conv3x3: extra sources must be contiguous NHWC at the output resolution")
-        if tuple(w.shape) != (Cout, 9 * (C1 + C2) + CE1 + CE2):
-            raise ValueError("conv3x3: fused weight must be [Cout, 9*(C1+C2)+CE1+CE2]")
-    elif tuple(w.shape[1:]) != (3, 3, C1 + C2):
-        raise ValueError(f"conv3x3: weight shape {tuple(w.shape)} does not match C1+C2={C1 + C2}")
-    H, Wd = (Hp * 2, Wp * 2) if upsample else (Hp, Wp)
-    pad_total = 1 if pad_hi_only else 2
-    Ho, Wo = (H + pad_total - 3) // stride + 1, (Wd + pad_total - 3) // stride + 1
-    if out is None:
-        out = torch.empty(B, Ho, Wo, Cout, dtype=torch.float16, device=x.device)
+    g = _conv_geometry_of(_dev16, x, w, x2, extra, rowvec, residual, stride, upsample, pad_hi_only)
+    B, Hp, Wp, C1, C2, CE1, CE2, Cout, H, Wd, Ho, Wo, M, K = g[:14]
+    e1, e2 = (None, None) if extra is None else extra
+    out = _conv_out(_dev16, out, g, torch.float16, x.device)
     p = IefGemmParams()
     p.A, p.A2, p.W, p.Out = x.data_ptr(), _ptr(x2), w.data_ptr(), out.data_ptr()
-    p.bias = _ptr(_dev32(bias, "bias")) if bias is not None else None
-    if rowvec is not None:
-        _dev32(rowvec, "rowvec")
-        if rowvec.dim() != 2 or rowvec.shape[1] != Cout or rowvec.shape[0] not in (1, B):
-            raise ValueError("conv3x3: rowvec must be [B, Cout] or [1, Cout]")
-        p.rowvec = rowvec.data_ptr()
-        p.rows_per_batch = Ho * Wo if rowvec.shape[0] == B and B > 1 else B * Ho * Wo
-    if residual is not None:
-        _dev16(residual, "residual")
-        if tuple(residual.shape) != tuple(out.shape) or not residual.is_contiguous():
-            raise ValueError("conv3x3: residual must match the output and be contiguous")
-        p.residual, p.ldr = residual.data_ptr(), Cout
     p.N, p.ldo = Cout, Cout
     p.H, p.Wd, p.C1, p.C2 = H, Wd, C1, C2
     p.stride, p.ups, p.batch_images = stride, 1 if upsample else 0, B
     p.pad_hi_only = 1 if pad_hi_only else 0
     p.out_scale = 1.0
-    M, K = B * Ho * Wo, 9 * (C1 + C2) + CE1 + CE2
     if tile_hint == 0:
         variant = "|u" if upsample else ""
         if AUTOTUNE and f"conv|{M}|{Cout}|{K}{variant}" not in _plan_table() and not _capturing() and _prof is None:
@@ -764,8 +825,7 @@ def conv3x3(x, w, bias=None, x2=None, stride=1, upsample=False, rowvec=None, res
                                                                             pad_hi_only=pad_hi_only), variant=variant)
             del wc
         p.tile_hint, p.splits, p.stages = pick_plan(M, Cout, K, conv=True, variant=variant)
-        halo_ok = stride == 1 and not pad_hi_only and extra is None and Hp >= 2 and (
-            (not upsample and 2 <= Wd <= 64) or (upsample and Wd <= 128 and (H * Wd) % 256 == 0 and 256 % Wd == 0))
+        halo_ok = g.halo_geom
         if halo_ok and HALO_HEURISTIC and f"conv|{M}|{Cout}|{K}{variant}" not in _plan_table() and (
                 not upsample or f"conv|{M}|{Cout}|{K}" not in _plan_table()):
             # no measured plan for this shape: the halo kernel (256 x 80 tiles) beat the implicit GEMM on every plain 3x3
@@ -782,44 +842,39 @@ def conv3x3(x, w, bias=None, x2=None, stride=1, upsample=False, rowvec=None, res
             p.tile_hint, p.splits, p.stages = heuristic_plan(M, Cout, K) + (2,)
     else:
         p.tile_hint, p.splits, p.stages = tile_hint, max(1, splits), stages
-    if p.splits > 1:
-        ws = torch.empty(p.splits * M * Cout, dtype=torch.float32, device=x.device)
-        p.ws = ws.data_ptr()
+    ws = _fill_epilogue(p, _rows_ld, "conv3x3", M, Cout, x.device, bias, rowvec, g.rows_per_batch, residual, p.splits)
+    if ws is not None:
         nt, kb = _tile_count(lib, p.tile_hint, M, Cout, p.splits)
         p.cnt = _splitk_counters(x.device, nt, kb) if nt and p.tile_hint not in _HALO_TILES else None
     p.E1, p.E2, p.CE1, p.CE2 = _ptr(e1), _ptr(e2), CE1, CE2
     p.flags, p.zeros = 1, _zeros(x.device)
-    cst = _attach_cstat(lib, p, out, M, Cout, Ho * Wo) if col_stats and out.is_contiguous() else None
+    cst = _attach_cstat(lib, p, out, M, Cout, Ho * Wo) if col_stats else None
     nbytes = 2.0 * (B * Hp * Wp * (C1 + C2) + M * (CE1 + CE2) + Cout * K + M * Cout * (2 if residual is not None else 1))
     with _Timed(_kname(p.tile_hint, True, p.stages) + (f" {M}x{Cout}x{K} s{p.splits}" if PROF_SHAPES else ""), 2.0 * M * Cout * K, nbytes):
         _check(lib.ief_conv3x3_f16(byref(p), _stream()), "ief_conv3x3_f16")
     return (out, cst) if col_stats else out
 
 
-def _splits_f32(lib, p, M, N, K, device):
-    """split-K for the fp32 GEMM when M x N alone gives too few 128-row tiles for the 256 CUs (the 16x16 / 8x8 levels):
+def _splits_f32(lib, conv, M, N, K):
+    """split-K count (1: none) for the fp32 GEMM when M x N alone gives too few 128-row tiles for the 256 CUs (the 16x16 / 8x8 levels):
     aim at ~512 workgroups, every slice keeping >= 4 K tiles of 32"""
     x3 = _F32_CONTRACT == "x3"
     nk = -(-K // 32)
     if x3:      # 128 x 80 tiles, two workgroups per CU: split below 1.5 per CU, towards 2 per CU (measured: without the split the
         # 32x32 / 16x16 levels run 1.5-2x slower than the reducer launches cost); 128 x 160 tiles, one 8-wave workgroup per CU:
         # split below one per two CUs, towards one per CU
-        bn = lib.ief_gemm_x3_bn_k(1 if p.conv else 0, N, K)
+        bn = lib.ief_gemm_x3_bn_k(1 if conv else 0, N, K)
         tiles = -(-M // lib.ief_gemm_x3_bm(M, N)) * -(-N // bn)
         below, target = (X3_SPLIT_BELOW_WIDE, X3_SPLIT_TARGET_WIDE) if bn == 160 else (X3_SPLIT_BELOW, X3_SPLIT_TARGET)
         if tiles >= below or nk < 8:
-            return None
+            return 1
         splits = max(1, min(-(-target // tiles), nk // 4, 16))
     else:
         tiles = -(-M // 128) * -(-N // lib.ief_gemm_f32_bn(N))
         if tiles >= 256 or nk < 8:
-            return None
+            return 1
         splits = max(1, min(-(-512 // tiles), nk // 4, 16))
-    if splits <= 1:
-        return None
-    ws = torch.empty(splits * M * N, dtype=torch.float32, device=device)
-    p.splits, p.ws = splits, ws.data_ptr()
-    return ws
+    return splits
 
 
 def _gemm_f32(a, w, bias=None, residual=None, rowvec=None, rows_per_batch=0, out=None, out_scale=1.0, transb=False, geglu=False):
@@ -842,17 +897,10 @@ def _gemm_f32(a, w, bias=None, residual=None, rowvec=None, rows_per_batch=0, out
     p = IefGemmF32Params()
     p.geglu = 1 if geglu else 0
     p.A, p.W, p.Out = a.data_ptr(), w.data_ptr(), out.data_ptr()
-    p.bias = _ptr(_dev32(bias, "bias")) if bias is not None else None
-    if rowvec is not None:
-        p.rowvec, p.rows_per_batch = _dev32(rowvec, "rowvec").data_ptr(), rows_per_batch
-    if residual is not None:
-        Mr, Nr, ldr = _rows_ld32(residual, "residual")
-        if (Mr, Nr) != (M, N):
-            raise ValueError("gemm: residual shape mismatch")
-        p.residual, p.ldr = residual.data_ptr(), ldr
     p.M, p.N, p.K, p.lda, p.ldw, p.ldo = M, N, K, lda, w.stride(0), ldo
     p.out_scale, p.transb = out_scale, 1 if transb else 0
-    ws = None if geglu else _splits_f32(lib, p, M, N, K, a.device)     # noqa: F841  (keeps the slabs alive until the launch is queued)
+    splits = 1 if geglu else _splits_f32(lib, False, M, N, K)
+    ws = _fill_epilogue(p, _rows_ld32, "gemm", M, N, a.device, bias, rowvec, rows_per_batch, residual, splits)     # noqa: F841  (keeps the slabs alive until the launch is queued)
     kn = _set_x3(p, X3_SCALE_ACT, X3_SCALE_ACT if transb else X3_SCALE_W,        # transb: activation x activation
                  w if (not transb and w.is_contiguous()) else None)
     nbytes = 4.0 * (M * K + N * K + M * N * (2 if residual is not None else 1))
@@ -870,50 +918,19 @@ def gemm_nt(a, b, out=None):
 
 def _conv3x3_f32(x, w, bias, x2, stride, upsample, rowvec, residual, out, extra, pad_hi_only):
     lib = load()
-    _act32(x, "x"), _act32(w, "w")
-    if not x.is_contiguous() or (x2 is not None and not _act32(x2, "x2").is_contiguous()) or not w.is_contiguous():
-        raise ValueError("conv3x3: x, x2, w must be contiguous")
-    B, Hp, Wp, C1 = x.shape
-    C2 = 0 if x2 is None else x2.shape[-1]
-    Cout = w.shape[0]
-    e1 = e2 = None
-    CE1 = CE2 = 0
-    if extra is not None:
-        e1, e2 = extra
-        CE1 = _act32(e1, "extra").shape[-1]
-        CE2 = 0 if e2 is None else _act32(e2, "extra").shape[-1]
-        for e in (e1, e2):
-            if e is not None and (not e.is_contiguous() or tuple(e.shape[:3]) != (B, Hp, Wp)):
-                raise ValueError("conv3x3: extra sources must be contiguous NHWC at the output resolution")
-        if tuple(w.shape) != (Cout, 9 * (C1 + C2) + CE1 + CE2):
-            raise ValueError("conv3x3: fused weight must be [Cout, 9*(C1+C2)+CE1+CE2]")
-    elif tuple(w.shape[1:]) != (3, 3, C1 + C2):
-        raise ValueError(f"conv3x3: weight shape {tuple(w.shape)} does not match C1+C2={C1 + C2}")
-    H, Wd = (Hp * 2, Wp * 2) if upsample else (Hp, Wp)
-    pad_total = 1 if pad_hi_only else 2
-    Ho, Wo = (H + pad_total - 3) // stride + 1, (Wd + pad_total - 3) // stride + 1
-    if out is None:
-        out = torch.empty(B, Ho, Wo, Cout, dtype=torch.float32, device=x.device)
+    g = _conv_geometry_of(_act32, x, w, x2, extra, rowvec, residual, stride, upsample, pad_hi_only)
+    B, Hp, Wp, C1, C2, CE1, CE2, Cout, H, Wd, Ho, Wo, M, K = g[:14]
+    e1, e2 = (None, None) if extra is None else extra
+    out = _conv_out(_act32, out, g, torch.float32, x.device)
     p = IefGemmF32Params()
     p.A, p.A2, p.W, p.Out = x.data_ptr(), _ptr(x2), w.data_ptr(), out.data_ptr()
-    p.bias = _ptr(_dev32(bias, "bias")) if bias is not None else None
-    if rowvec is not None:
-        _dev32(rowvec, "rowvec")
-        if rowvec.dim() != 2 or rowvec.shape[1] != Cout or rowvec.shape[0] not in (1, B):
-            raise ValueError("conv3x3: rowvec must be [B, Cout] or [1, Cout]")
-        p.rowvec = rowvec.data_ptr()
-        p.rows_per_batch = Ho * Wo if rowvec.shape[0] == B and B > 1 else B * Ho * Wo
-    if residual is not None:
-        if tuple(_act32(residual, "residual").shape) != tuple(out.shape) or not residual.is_contiguous():
-            raise ValueError("conv3x3: residual must match the output and be contiguous")
-        p.residual, p.ldr = residual.data_ptr(), Cout
-    M, K = B * Ho * Wo, 9 * (C1 + C2) + CE1 + CE2
     p.M, p.N, p.K, p.ldo, p.ldw = M, Cout, K, Cout, K
     p.conv, p.H, p.Wd, p.C1, p.C2, p.Ho, p.Wo = 1, H, Wd, C1, C2, Ho, Wo
     p.stride, p.ups, p.batch_images, p.pad_hi_only = stride, 1 if upsample else 0, B, 1 if pad_hi_only else 0
     p.E1, p.E2, p.CE1, p.CE2 = _ptr(e1), _ptr(e2), CE1, CE2
     p.out_scale = 1.0
-    ws = _splits_f32(lib, p, M, Cout, K, x.device)  # noqa: F841
+    splits = _splits_f32(lib, True, M, Cout, K)
+    ws = _fill_epilogue(p, _rows_ld32, "conv3x3", M, Cout, x.device, bias, rowvec, g.rows_per_batch, residual, splits)     # noqa: F841
     kn = _set_x3(p, X3_SCALE_ACT, X3_SCALE_W, w)
     nbytes = 4.0 * (B * Hp * Wp * (C1 + C2) + M * (CE1 + CE2) + Cout * K + M * Cout * (2 if residual is not None else 1))
     with _Timed(f"{kn}<true, false>" + (f" {M}x{Cout}x{K} s{p.splits}" if PROF_SHAPES else ""), 2.0 * M * Cout * K, nbytes):

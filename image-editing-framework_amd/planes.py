@@ -113,18 +113,12 @@ TILE_FORCE = int(os.environ.get("IEF_X3P_TILE", "0"))        # A/B runs: force o
 def _plan_table():
     global _plans
     if _plans is None:
-        _plans = {}
-        if os.path.exists(_PLAN_FILE) and os.environ.get("IEF_NO_PLAN_TABLE", "0") != "1":
-            import json
-            with open(_PLAN_FILE) as f:
-                _plans = {k: tuple(v) for k, v in json.load(f).items()}
+        _plans = hip.read_plans(_PLAN_FILE)
     return _plans
 
 
 def save_plans(path=None):
-    import json
-    with open(path or _PLAN_FILE, "w") as f:
-        json.dump({k: list(v) for k, v in sorted(_plan_table().items())}, f, indent=0)
+    hip.write_plans(path or _PLAN_FILE, _plan_table())
 
 
 _TILES = {1: (128, 160), 2: (128, 160), 3: (128, 80), 4: (256, 160), 5: (64, 160), 6: (128, 64), 7: (128, 160), 8: (256, 320),
@@ -300,14 +294,6 @@ def gemm(a, w, bias=None, residual=None, rowvec=None, rows_per_batch=0, out=None
     p.W, p.planeW, p.ldw = wp.data_ptr(), wp.stride(0), K
     No = N // 2 if geglu else N
     o32, op = _out_args(p, M, No, out, out_planes, a.device, a.shape[:-1])
-    p.bias = _ptr(_dev32(bias, "bias")) if bias is not None else None
-    if rowvec is not None:
-        p.rowvec, p.rows_per_batch = _dev32(rowvec, "rowvec").data_ptr(), rows_per_batch
-    if residual is not None:
-        Mr, Nr, ldr = hip._rows_ld32(residual, "residual")
-        if (Mr, Nr) != (M, N):
-            raise ValueError("planes.gemm: residual shape mismatch")
-        p.residual, p.ldr = residual.data_ptr(), ldr
     p.M, p.N, p.K = M, N, K
     p.out_scale, p.inv_scale = out_scale, 1.0 / (ACT_SCALE * W_SCALE)
     p.geglu, p.zeros = 1 if geglu else 0, _zeros(a.device)
@@ -334,10 +320,7 @@ def gemm(a, w, bias=None, residual=None, rowvec=None, rows_per_batch=0, out=None
         if st.buf.shape[0] != M or st.slots * st.cnt != K or _dev32(colsum, "colsum").numel() != N:
             raise ValueError("planes.gemm: ln statistics / colsum do not match this launch")
         p.rstat_in, p.rstat_slots, p.rstat_cnt, p.colsum, p.ln_eps = st.buf.data_ptr(), st.slots, st.cnt, colsum.data_ptr(), eps
-    ws = None
-    if p.splits > 1:
-        ws = torch.empty(p.splits * M * N, dtype=torch.float32, device=a.device)       # noqa: F841 (alive until queued)
-        p.ws = ws.data_ptr()
+    ws = hip._fill_epilogue(p, hip._rows_ld32, "planes.gemm", M, N, a.device, bias, rowvec, rows_per_batch, residual, p.splits)       # noqa: F841 (alive until queued)
     nbytes = 4.0 * (M * K + N * K + M * No * ((1 if o32 is not None else 0) + (1 if op is not None else 0)) + (M * N if residual is not None else 0))
     kn = f"igemm_x3p_kernel<false> t{p.tile}" + (f" {M}x{N}x{K} s{p.splits}" if hip.PROF_SHAPES else "")
     bm, bn = _TILES[p.tile]
@@ -359,25 +342,15 @@ def conv3x3(x, w, bias=None, x2=None, stride=1, upsample=False, rowvec=None, res
         raise TypeError("planes.conv3x3: x / x2 must be Planes")
     if not x.is_contiguous() or (x2 is not None and not x2.is_contiguous()) or not w.is_contiguous():
         raise ValueError("planes.conv3x3: x, x2, w must be contiguous")
-    B, Hp, Wp, C1 = x.shape
-    C2 = 0 if x2 is None else x2.shape[-1]
-    Cout = w.shape[0]
-    e1 = e2 = None
-    CE1 = CE2 = 0
-    if extra is not None:
-        e1, e2 = extra
-        CE1 = e1.shape[-1]
-        CE2 = 0 if e2 is None else e2.shape[-1]
-        for e in (e1, e2):
-            if e is not None and (not isinstance(e, Planes) or not e.is_contiguous() or tuple(e.shape[:3]) != (B, Hp, Wp)):
-                raise ValueError("planes.conv3x3: extra sources must be contiguous NHWC Planes at the output resolution")
-    K = 9 * (C1 + C2) + CE1 + CE2
-    if w.numel() != Cout * K:
-        raise ValueError(f"planes.conv3x3: weight {tuple(w.shape)} does not match K = {K}")
-    H, Wd = (Hp * 2, Wp * 2) if upsample else (Hp, Wp)
-    pad_total = 1 if pad_hi_only else 2
-    Ho, Wo = (H + pad_total - 3) // stride + 1, (Wd + pad_total - 3) // stride + 1
-    M = B * Ho * Wo
+    e1, e2 = (None, None) if extra is None else extra
+    for e in (e1, e2):
+        if e is not None and (not isinstance(e, Planes) or not e.is_contiguous()):
+            raise ValueError("planes.conv3x3: extra sources must be contiguous NHWC Planes at the output resolution")
+    if residual is not None and not hip._act32(residual, "residual").is_contiguous():
+        raise ValueError("planes.conv3x3: residual must be contiguous fp32 [B, Ho, Wo, Cout]")
+    g = hip.conv_geometry(x.shape, w.shape, hip._shape(x2), None if extra is None else (e1.shape, hip._shape(e2)), hip._shape(rowvec),
+                          hip._shape(residual), stride, upsample, pad_hi_only, "planes.conv3x3")
+    B, Hp, Wp, C1, C2, CE1, CE2, Cout, H, Wd, Ho, Wo, M, K = g[:14]
     p = IefGemmX3pParams()
     p.A, p.planeA = x.t.data_ptr(), x.plane
     if x2 is not None:
@@ -387,17 +360,6 @@ def conv3x3(x, w, bias=None, x2=None, stride=1, upsample=False, rowvec=None, res
     if e2 is not None:
         p.E2, p.planeE2 = e2.t.data_ptr(), e2.plane
     o32, op = _out_args(p, M, Cout, out, out_planes, x.device, (B, Ho, Wo))
-    p.bias = _ptr(_dev32(bias, "bias")) if bias is not None else None
-    if rowvec is not None:
-        _dev32(rowvec, "rowvec")
-        if rowvec.dim() != 2 or rowvec.shape[1] != Cout or rowvec.shape[0] not in (1, B):
-            raise ValueError("planes.conv3x3: rowvec must be [B, Cout] or [1, Cout]")
-        p.rowvec = rowvec.data_ptr()
-        p.rows_per_batch = Ho * Wo if rowvec.shape[0] == B and B > 1 else B * Ho * Wo
-    if residual is not None:
-        if tuple(hip._act32(residual, "residual").shape) != (B, Ho, Wo, Cout) or not residual.is_contiguous():
-            raise ValueError("planes.conv3x3: residual must be contiguous fp32 [B, Ho, Wo, Cout]")
-        p.residual, p.ldr = residual.data_ptr(), Cout
     p.M, p.N, p.K = M, Cout, K
     p.conv, p.H, p.Wd, p.C1, p.C2, p.Ho, p.Wo = 1, H, Wd, C1, C2, Ho, Wo
     p.stride, p.ups, p.batch_images, p.pad_hi_only = stride, 1 if upsample else 0, B, 1 if pad_hi_only else 0
@@ -405,10 +367,9 @@ def conv3x3(x, w, bias=None, x2=None, stride=1, upsample=False, rowvec=None, res
     p.out_scale, p.inv_scale, p.zeros = 1.0, 1.0 / (ACT_SCALE * W_SCALE), _zeros(x.device)
     # the halo form (input super-tile resident in LDS across the nine taps): plain 3x3 / stride 1 / pad 1 on rows of <= 64
     # pixels, or the fused nearest-2x on rows of <= 128 pixels with whole output rows per 256-pixel tile
-    halo_ok = HALO and stride == 1 and not pad_hi_only and extra is None and Hp >= 2 and Cout % 80 == 0 and (
-        (not upsample and 2 <= Wd <= 64) or (upsample and Wd <= 128 and (H * Wd) % 256 == 0 and 256 % Wd == 0))
+    halo_ok = HALO and g.halo_geom and Cout % 80 == 0
     # the phase form of the fused nearest-2x: tile 11's limits on the SOURCE image
-    phase_ok = HALO and upsample and stride == 1 and not pad_hi_only and extra is None and Hp >= 2 and 2 <= Wp <= 64 and Cout % 80 == 0
+    phase_ok = HALO and g.phase_geom and Cout % 80 == 0
     if tile:
         p.tile, p.splits = tile, max(1, splits)
     else:
@@ -448,10 +409,7 @@ def conv3x3(x, w, bias=None, x2=None, stride=1, upsample=False, rowvec=None, res
             p.splits = min(p.splits, (C1 + C2) // 32)
         wp = weight_planes(w)
     p.W, p.planeW, p.ldw = wp.data_ptr(), wp.stride(0), K
-    ws = None
-    if p.splits > 1:
-        ws = torch.empty(p.splits * M * Cout, dtype=torch.float32, device=x.device)     # noqa: F841
-        p.ws = ws.data_ptr()
+    ws = hip._fill_epilogue(p, hip._rows_ld32, "planes.conv3x3", M, Cout, x.device, bias, rowvec, g.rows_per_batch, residual, p.splits)     # noqa: F841
     nbytes = 4.0 * (B * Hp * Wp * (C1 + C2) + M * (CE1 + CE2) + Cout * K + M * Cout * ((1 if o32 is not None else 0) + (1 if op is not None else 0) + (1 if residual is not None else 0)))
     # (tile 13: K is 4 (C1 + C2) here, so the FLOPs, weight bytes and staged bytes below are the four taps the launch executes)
     kn = "conv3x3_halo_x3p_kernel_phase" if p.tile == 13 else \
