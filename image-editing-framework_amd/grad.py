@@ -35,7 +35,8 @@ class UNetAdjoint:
     """mode "context" (default): d objective / d encoder_hidden_states given d objective / d eps (null-text inversion).
     mode "input": d objective / d sample where the objective is Pix2Pix-zero's cross-attention-map term
     (`/root/reference/pix2pix-zero/model/sd_utils.py:166-173`): the gradient ENTERS at the queries of every cross-attention
-    module (`hip.attn_map_loss_bwd` against the reference maps), nothing enters at eps, and the chain runs all the way
+    module (`hip.attn_map_loss_bwd` against the reference maps; on fp32 storage `hip.cross_map_grad`, which also carries the
+    attention layer's own value path), nothing enters at eps, and the chain runs all the way
     down through the first resnet and conv_in."""
 
     def __init__(self, unet, grad_scale: float = 1.0, mode: str = "context"):
@@ -227,13 +228,17 @@ class UNetAdjoint:
         off = a2._kv_off
         k2 = self.kv_all[..., off:off + C]
         if self.mode == "input":
-            dq2, _, _ = hip.attn_bwd(q2, k2, self.kv_all[..., off + C:off + 2 * C], o2, d_o2, lse2, a2.heads, a2.scale,
-                                     want_dkv=False)
             i = self._cross_index[id(a2)]
             parts = self.loss_parts[self._loss_off[i]:self._loss_off[i + 1]]
-            hip.attn_map_loss_bwd(q2, k2, self.ref_maps[i], dq2, a2.heads, a2.scale,
-                                  gcoef=2.0 * self.grad_scale / (B * a2.heads), accumulate=True, loss=parts,
-                                  loss_coef=1.0 / (B * a2.heads))
+            gcoef, loss_coef = 2.0 * self.grad_scale / (B * a2.heads), 1.0 / (B * a2.heads)
+            if self._cross_fused[i]:       # fp32 storage: value path and objective in one launch, no map in HBM
+                dq2 = hip.cross_map_grad(q2, k2, self.kv_all[..., off + C:off + 2 * C], d_o2, self.ref_maps[i], a2.heads, a2.scale,
+                                         gcoef, loss=parts, loss_coef=loss_coef)
+            else:
+                dq2, _, _ = hip.attn_bwd(q2, k2, self.kv_all[..., off + C:off + 2 * C], o2, d_o2, lse2, a2.heads, a2.scale,
+                                         want_dkv=False)
+                hip.attn_map_loss_bwd(q2, k2, self.ref_maps[i], dq2, a2.heads, a2.scale, gcoef=gcoef, accumulate=True, loss=parts,
+                                      loss_coef=loss_coef)
         else:
             dq2, _, _ = hip.attn_bwd(q2, k2, self.kv_all[..., off + C:off + 2 * C], o2, d_o2, lse2,
                                      a2.heads, a2.scale, dk=self.dkv_all[..., off:off + C],
@@ -268,9 +273,12 @@ class UNetAdjoint:
             raise ValueError(f"UNetAdjoint: {len(self.cross)} cross-attention modules, {len(ref_maps)} reference maps")
         self.ref_maps = list(ref_maps)
         self._cross_index = {id(m): i for i, m in enumerate(self.cross)}
+        # fp32 storage: the modules `hip.cross_map_grad` takes (a shape rule) differentiate both paths into the queries in one launch
+        self._cross_fused = [self.f32 and hip.cross_map_grad_ok(m.dim_head, r.shape[2], r.dtype) for m, r in zip(self.cross, ref_maps)]
         off = [0]
-        for m, r in zip(self.cross, ref_maps):
-            off.append(off[-1] + (hip.map_loss_blocks_f32(r.shape[0] * r.shape[1]) if self.f32 else
+        for m, r, fused in zip(self.cross, ref_maps, self._cross_fused):
+            off.append(off[-1] + (r.shape[0] * hip.cross_map_grad_blocks(r.shape[1], m.dim_head) if fused else
+                                  hip.map_loss_blocks_f32(r.shape[0] * r.shape[1]) if self.f32 else
                                   r.shape[0] * hip.map_loss_blocks(r.shape[1], m.dim_head)))
         self._loss_off = off
         if self.loss_parts is None or self.loss_parts.numel() != off[-1]:

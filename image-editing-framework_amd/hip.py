@@ -1966,6 +1966,56 @@ def _attn_map_loss_bwd_f32(q, k, ref, dq, heads, scale, gcoef, accumulate, loss,
     return dq
 
 
+CROSS_MAP_GRAD_MAX_L = cabi.defines["IEF_CROSS_MAP_GRAD_MAX_L"]
+_CROSS_MAP_GRAD_DIMS = (32, 40, 64, 80, 160)
+
+
+def cross_map_grad_ok(d, L, dtype=torch.float32) -> bool:
+    """`cross_map_grad` takes this cross-attention module: fp32 operands, a head dim of the kernel's set and at most
+    CROSS_MAP_GRAD_MAX_L keys (the LDS image of K, V and the two per-query columns fits a CU).  Everything else keeps
+    `attn_bwd(want_dkv=False)` + `attn_map_loss_bwd`."""
+    return dtype == torch.float32 and int(d) in _CROSS_MAP_GRAD_DIMS and 1 <= int(L) <= CROSS_MAP_GRAD_MAX_L
+
+
+def cross_map_grad_blocks(N, d):
+    """loss partials per (batch, head) that `cross_map_grad` writes"""
+    return load().ief_cross_map_grad_blocks(int(N), int(d))
+
+
+def cross_map_grad(q, k, v, do, ref, heads, scale, gcoef, dq=None, loss=None, loss_coef=1.0):
+    """Pix2Pix-zero guidance of one cross-attention module on the fp32-storage reverse pass, ONE launch (include/ief_hip.h,
+    ief_attn_cross_map_grad_f32): with P = softmax(scale q k^T), dP = do v^T + gcoef (P - ref) and dS = P o (dP - rowsum(dP o P)),
+    dq = scale dS k -- the gradient of the attention layer's value path and of the map objective together; dq is OVERWRITTEN.
+    q / do [B,N,h*d], k / v [B,L,h*d] (strided views ok), ref fp32 [B*heads,N,L] contiguous; dq: None (allocated) or a view of
+    q's shape; loss: optional fp32 [B*heads*cross_map_grad_blocks(N, d)] partials of sum (P - ref)^2, each times loss_coef."""
+    lib = load()
+    for t, nm in ((q, "q"), (k, "k"), (v, "v"), (do, "do")):
+        _act32(t, nm)
+        if t.dim() != 3 or (t.shape[0] > 1 and t.stride(0) != t.shape[1] * t.stride(1)):
+            raise ValueError(f"cross_map_grad: {nm} must be [B, rows, h*d] with batch stride rows * ld")
+    B, N, C = q.shape
+    L = k.shape[1]
+    d = C // heads
+    if heads * d != C or tuple(k.shape) != (B, L, C) or tuple(v.shape) != (B, L, C) or tuple(do.shape) != (B, N, C):
+        raise ValueError("cross_map_grad: shape mismatch")
+    if tuple(_act32(ref, "ref").shape) != (B * heads, N, L) or not ref.is_contiguous():
+        raise ValueError("cross_map_grad: ref must be contiguous fp32 [B*heads, N, L]")
+    if dq is None:
+        dq = torch.empty(B, N, C, dtype=torch.float32, device=q.device)
+    _act32(dq, "dq")
+    if tuple(dq.shape) != (B, N, C) or (B > 1 and dq.stride(0) != N * dq.stride(1)):
+        raise ValueError("cross_map_grad: dq must be [B, N, h*d] with batch stride N * ld")
+    if loss is not None and _dev32(loss, "loss").numel() < B * heads * lib.ief_cross_map_grad_blocks(N, d):
+        raise ValueError("cross_map_grad: loss needs B*heads*cross_map_grad_blocks(N, d) floats")
+    with _Timed(f"cross_map_grad_f32_kernel<{d}>", 6.0 * B * heads * N * L * d,
+                4.0 * (3.0 * B * N * C + 2.0 * B * L * C + B * heads * N * L)):
+        _check(lib.ief_attn_cross_map_grad_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), do.data_ptr(), ref.data_ptr(), dq.data_ptr(),
+                                               _ptr(loss), B, heads, N, L, d, q.stride(1), k.stride(1), v.stride(1), do.stride(1),
+                                               dq.stride(1), float(scale), float(gcoef), float(loss_coef), _stream()),
+               "ief_attn_cross_map_grad_f32")
+    return dq
+
+
 def axpy(y, x, a):
     """y += a * x (fp32, in place)"""
     lib = load()

@@ -623,6 +623,29 @@ typedef struct IefMapLossParams {
 int ief_attn_map_loss_bwd_f16(const IefMapLossParams* p, void* stream);
 /* workgroups per (batch, head) of the kernel above = loss partials per (batch, head) */
 int ief_map_loss_blocks(int N, int d);
+/* The same guidance on the fp32-storage reverse pass, fused with the value path of the attention layer: ONE launch per
+ * cross-attention module gives the whole gradient w.r.t. its queries and the objective's value (csrc/cross_map_grad_f32.hip).
+ * For batch row b, head h, query n, with K / V of (b, h) held in LDS as fp32:
+ *     P    = softmax_j(scale q.K_j)
+ *     dP_j = dO.V_j + gcoef (P_j - ref_j)          value path + objective (gcoef = 2 / (B heads) * gradient scale)
+ *     dS_j = P_j (dP_j - sum_i dP_i P_i)
+ *     dQ   = scale sum_j dS_j K_j                  OVERWRITES dQ: the sum of both paths, there is no accumulate flag
+ *     loss[b][h][w] = loss_coef sum (P - ref)^2 over the queries of workgroup w, summed in a fixed order
+ * Plain fp32 FMAs (no MFMA, no operand splitting); no map and no score is written to global memory.  Q, dO, dQ: fp32 [B][N][heads*d]
+ * with row strides ldq / ldo / lddq; K, V: fp32 [B][L][heads*d] with row strides ldk / ldv (column slices of a wider buffer are
+ * fine); rows of batch b start at b * rows * ld.  ref: contiguous fp32 [B*heads][N][L].  loss (optional): [B][heads]
+ * [ief_cross_map_grad_blocks(N, d)] floats, nothing else is written.  d in {32, 40, 64, 80, 160}; 1 <= L <=
+ * IEF_CROSS_MAP_GRAD_MAX_L, the largest L whose LDS image (L (8 d + 8 * 256 / G) + 16 bytes, G = 2, 2, 4, 4, 8 lanes per query)
+ * fits the 160 KiB of a CU at d = 160; B, heads <= 65535.  A null Q / K / V / dO / ref / dQ: IEF_EINVAL; any other L, d, a
+ * non-positive size or heads * d beyond a row stride: IEF_ESHAPE; Q / K / V / dO / dQ off a 16-byte boundary, a row stride that is
+ * no multiple of 4 floats, ref / loss off a 4-byte boundary: IEF_EALIGN.  Nothing is launched by a refused call.  The arguments
+ * are passed flat, as ief_cross_blend_mass_f32's are: the entry point adds no parameter struct to the ABI. */
+#define IEF_CROSS_MAP_GRAD_MAX_L 106
+int ief_attn_cross_map_grad_f32(const float* Q, const float* K, const float* V, const float* dO, const float* ref, float* dQ,
+                                float* loss, int B, int heads, int N, int L, int d, int ldq, int ldk, int ldv, int ldo, int lddq,
+                                float scale, float gcoef, float loss_coef, void* stream);
+/* workgroups per (batch, head) of the kernel above = loss partials per (batch, head); 0 for a head dim it does not take */
+int ief_cross_map_grad_blocks(int N, int d);
 /* y[i] += a * x[i] (fp32): the plain SGD step on the UNet input (sd_utils.py:160,174) */
 int ief_axpy_f32(float* y, const float* x, float a, long long n, void* stream);
 /* GroupNorm(+SiLU) whose statistics were left by the kernels that produced x (and x2): cstat1 / cstat2 are those launches'
