@@ -16,8 +16,7 @@
 // it wrote itself.
 // LDS: L (8 D + 8 * 256 / G) + 16 bytes -- 1280, 1344, 1024, 1152, 1536 bytes per key for D = 32 .. 160: L <= 106 fits the 160 KiB
 // of a CU at every head dim (IEF_CROSS_MAP_GRAD_MAX_L).
-#include "ief_common.h"
-#include "ief_params.h"
+#include "cross_f32_common.h"                        // cmg_dc, group_sum: shared with csrc/cross_bwd_f32.hip
 
 struct CmgArgs {
     const float* Q; const float* K; const float* V; const float* dO; const float* ref;
@@ -27,27 +26,11 @@ struct CmgArgs {
     float scale, gcoef, loss_coef;
 };
 
-static constexpr int cmg_dc(int d) { return d % 20 == 0 ? 20 : 16; }
 static constexpr size_t cmg_lds(int L, int d) { return (size_t)L * (8 * d + 8 * (256 / (d / cmg_dc(d)))) + 16; }
 static_assert(cmg_lds(IEF_CROSS_MAP_GRAD_MAX_L, 160) <= 160 * 1024 && cmg_lds(IEF_CROSS_MAP_GRAD_MAX_L + 1, 160) > 160 * 1024,
               "IEF_CROSS_MAP_GRAD_MAX_L is the largest L whose LDS image fits a CU at d = 160");
 static_assert(cmg_lds(IEF_CROSS_MAP_GRAD_MAX_L, 32) <= 160 * 1024 && cmg_lds(IEF_CROSS_MAP_GRAD_MAX_L, 40) <= 160 * 1024 &&
               cmg_lds(IEF_CROSS_MAP_GRAD_MAX_L, 64) <= 160 * 1024 && cmg_lds(IEF_CROSS_MAP_GRAD_MAX_L, 80) <= 160 * 1024, "");
-
-// sum over the G adjacent lanes of a query, on the data-parallel primitives (no LDS round trip): lane ^ 1, lane ^ 2 inside a quad,
-// then the mirror image of the 8-lane half row -- the four lanes of a quad hold one value by then, so lane 7 - i stands for lane i ^ 4.
-// Every lane of the group ends with the same bits: each step adds the same two numbers on both sides.
-template <int CTRL>
-__device__ __forceinline__ float dpp_move(float a) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(a), CTRL, 0xF, 0xF, true));
-}
-template <int G>
-__device__ __forceinline__ float group_sum(float a) {
-    if (G >= 2) a += dpp_move<0xB1>(a);               // quad_perm [1, 0, 3, 2]
-    if (G >= 4) a += dpp_move<0x4E>(a);               // quad_perm [2, 3, 0, 1]
-    if (G >= 8) a += dpp_move<0x141>(a);              // row_half_mirror
-    return a;
-}
 
 // JB keys at a time: their LDS reads and group sums are independent and overlap; each dot product still adds its terms in
 // ascending order of the head dim, each accumulation over the keys in ascending order of the key.  A ragged last block of
@@ -197,8 +180,6 @@ __global__ __launch_bounds__(256) void cross_map_grad_f32_kernel(const CmgArgs p
     if (tid == 0 && p.loss)
         p.loss[((long long)b * p.heads + head) * gridDim.x + blockIdx.x] = (red[0] + red[1] + red[2] + red[3]) * p.loss_coef;
 }
-
-static bool cmg_head_dim(int d) { return d == 32 || d == 40 || d == 64 || d == 80 || d == 160; }
 
 extern "C" int ief_cross_map_grad_blocks(int N, int d) {
     if (N <= 0 || !cmg_head_dim(d)) return 0;

@@ -1918,9 +1918,14 @@ def _attn_bwd_f32(q, k, v, do, heads, scale, dq, dk, dv, want_dq, want_dkv, o=No
     """gradients of softmax(scale q k^T) v on MATERIALISED fp32 maps (`/root/reference/p2p/model/register.py:43-51` is the
     forward being differentiated): P recomputed, dP = dO V^T, dS, then dQ = dS K, dK = dS^T Q, dV = P^T dO -- every
     product an `ief_gemm_f32` launch in the model's contraction mode.  With the forward's `lse` (split-operand mode, head dims
-    40 / 64, >= 128 keys: `x3_fused_bwd_ok`) the fused recomputing kernel runs instead and no map is written."""
-    if lse is not None and o is not None and x3_fused_bwd_ok(q.shape[2] // heads, k.shape[1]):
+    40 / 64, >= 128 keys: `x3_fused_bwd_ok`) the fused recomputing kernel runs instead and no map is written.  Where dK / dV are
+    wanted of an attention with few keys (`cross_bwd_ok`: the 77-key cross-attention of the null-text pass, in both contraction
+    modes) `cross_bwd` gives all three gradients in plain fp32, again without a map."""
+    d, L = q.shape[2] // heads, k.shape[1]
+    if lse is not None and o is not None and x3_fused_bwd_ok(d, L):
         return _attn_bwd_x3(q, k, v, o, do, lse, heads, scale, dq, dk, dv, want_dq, want_dkv)
+    if want_dkv and cross_bwd_ok(d, L, q.dtype) and not x3_fused_bwd_ok(d, L):
+        return cross_bwd(q, k, v, do, heads, scale, dq=dq, dk=dk, dv=dv, want_dq=want_dq)
     for t, nm in ((q, "q"), (k, "k"), (v, "v"), (do, "do")):
         _act32(t, nm)
     probs = _attn_scores_f32(q, k, heads, scale)                          # [B*h, N, L]
@@ -2014,6 +2019,60 @@ def cross_map_grad(q, k, v, do, ref, heads, scale, gcoef, dq=None, loss=None, lo
                                                dq.stride(1), float(scale), float(gcoef), float(loss_coef), _stream()),
                "ief_attn_cross_map_grad_f32")
     return dq
+
+
+CROSS_BWD_MAX_L = cabi.defines["IEF_CROSS_BWD_MAX_L"]
+_CROSS_BWD_ROUTED_DIMS = (32, 40, 64, 80)
+
+
+def cross_bwd_ok(d, L, dtype=torch.float32) -> bool:
+    """the reverse pass differentiates this attention with `cross_bwd`: fp32 operands, at most CROSS_BWD_MAX_L keys (the LDS image
+    of K, V, the two per-query columns and a workgroup's q / dO rows fits a CU) and a head dim of 32 / 40 / 64 / 80 -- a shape rule,
+    no switch.  The kernel also takes d = 160, but that head dim belongs to the 16 x 16 and 8 x 8 levels, whose few workgroups sit on
+    the kernel's latency floor: measured 63-76 us per module against 50-72 us materialised, so those levels,
+    like everything else, keep the materialised maps of `_attn_bwd_f32`."""
+    return dtype == torch.float32 and int(d) in _CROSS_BWD_ROUTED_DIMS and 1 <= int(L) <= CROSS_BWD_MAX_L
+
+
+def cross_bwd_blocks(N, d):
+    """dK / dV partials per (batch, head) that `cross_bwd`'s main kernel leaves for its reducer"""
+    return load().ief_cross_bwd_blocks(int(N), int(d))
+
+
+def cross_bwd(q, k, v, do, heads, scale, dq=None, dk=None, dv=None, want_dq=True):
+    """The complete backward of out = softmax(scale q k^T) v for a short-key (cross-) attention on the fp32-storage reverse pass, no
+    map in HBM (include/ief_hip.h, ief_attn_cross_bwd_f32): main kernel + reducer, fixed summation order, results OVERWRITTEN.
+    q / do [B,N,h*d], k / v [B,L,h*d] (strided views ok); dq / dk / dv: None (allocated) or views of their operands' shapes, e.g.
+    column slices of wider buffers; want_dq=False: dq is neither computed nor touched.  -> (dq or None, dk, dv)"""
+    lib = load()
+    for t, nm in ((q, "q"), (k, "k"), (v, "v"), (do, "do")):
+        _act32(t, nm)
+        if t.dim() != 3 or (t.shape[0] > 1 and t.stride(0) != t.shape[1] * t.stride(1)):
+            raise ValueError(f"cross_bwd: {nm} must be [B, rows, h*d] with batch stride rows * ld")
+    B, N, C = q.shape
+    L = k.shape[1]
+    d = C // heads
+    if heads * d != C or tuple(k.shape) != (B, L, C) or tuple(v.shape) != (B, L, C) or tuple(do.shape) != (B, N, C):
+        raise ValueError("cross_bwd: shape mismatch")
+
+    def grad_like(t, g, nm):
+        if g is None:
+            g = torch.empty(t.shape, dtype=torch.float32, device=t.device)
+        _act32(g, nm)
+        if tuple(g.shape) != tuple(t.shape) or (g.shape[0] > 1 and g.stride(0) != g.shape[1] * g.stride(1)):
+            raise ValueError(f"cross_bwd: {nm} must have the shape of its operand and batch stride rows * ld")
+        return g
+    dq = grad_like(q, dq, "dq") if want_dq else None
+    dk, dv = grad_like(k, dk, "dk"), grad_like(v, dv, "dv")
+    # the caller's scratch, as `delta` of ief_attn_bwd_x3: the caching allocator serves it under graph capture too
+    scratch = torch.empty(max(1, lib.ief_cross_bwd_scratch_floats(B, heads, N, L, d)), dtype=torch.float32, device=q.device)
+    with _Timed(f"cross_bwd_f32_kernel<{d}>", (10.0 if want_dq else 8.0) * B * heads * N * L * d,
+                4.0 * ((3.0 if want_dq else 2.0) * B * N * C + 4.0 * B * L * C)):
+        _check(lib.ief_attn_cross_bwd_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), do.data_ptr(), _ptr(dq), dk.data_ptr(),
+                                          dv.data_ptr(), scratch.data_ptr(), B, heads, N, L, d, q.stride(1), k.stride(1), v.stride(1),
+                                          do.stride(1), dq.stride(1) if want_dq else 0, dk.stride(1), dv.stride(1), float(scale),
+                                          _stream()), "ief_attn_cross_bwd_f32")
+    return dq, dk, dv
 
 
 def axpy(y, x, a):

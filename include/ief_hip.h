@@ -646,6 +646,36 @@ int ief_attn_cross_map_grad_f32(const float* Q, const float* K, const float* V, 
                                 float scale, float gcoef, float loss_coef, void* stream);
 /* workgroups per (batch, head) of the kernel above = loss partials per (batch, head); 0 for a head dim it does not take */
 int ief_cross_map_grad_blocks(int N, int d);
+/* The COMPLETE backward of a short-key cross-attention on the fp32-storage reverse pass, no map in global memory
+ * (csrc/cross_bwd_f32.hip): what null-text inversion optimises reaches the context through K and V of these modules
+ * (/root/reference/p2p/inversion/nti.py:15-33).  For batch row b, head h, with K / V of (b, h) held in LDS as fp32:
+ *     P    = softmax_j(scale q.K_j)
+ *     dP_j = dO.V_j
+ *     dS_j = P_j (dP_j - sum_i dP_i P_i)
+ *     dQ_n = scale sum_j dS_nj K_j                 OVERWRITES dQ; dQ == NULL: not computed (the K walk is skipped)
+ *     dK_j = scale sum_n dS_nj Q_n                 OVERWRITES dK
+ *     dV_j =       sum_n P_nj  dO_n                OVERWRITES dV
+ * Plain fp32 FMAs (no MFMA, no operand splitting).  Two launches: the main kernel reduces the queries of each workgroup into one
+ * [L][d] partial per matrix in `scratch` ([B][heads][ief_cross_bwd_blocks(N, d)][2][L][d] floats =
+ * ief_cross_bwd_scratch_floats(...), the caller's, 16-byte aligned, contents irrelevant before and after), a reducer adds the
+ * partials in ascending block order: no atomics, two calls on the same operands give the same bits, and row b of every result
+ * depends on row b of the operands only, whatever B is.  Q, dO, dQ: fp32 [B][N][heads*d] with row strides ldq / ldo / lddq; K, V, dK,
+ * dV: fp32 [B][L][heads*d] with row strides ldk / ldv / lddk / lddv (column slices of wider buffers are fine); rows of batch b
+ * start at b * rows * ld.  d in {32, 40, 64, 80, 160}; 1 <= L <= IEF_CROSS_BWD_MAX_L, the largest L whose LDS image
+ * (8 L d + 8 L QB + 8 QB d bytes: K and V, the two per-query columns, the q and dO rows of the QB = 128, 128, 64, 64, 32 queries of
+ * a workgroup) fits the 160 KiB of a CU at every head dim -- d = 160 sets it, at exactly 160 KiB; B, heads <= 65535.  A null
+ * Q / K / V / dO / dK / dV / scratch: IEF_EINVAL; any other L, d, a non-positive size or heads * d beyond a row stride: IEF_ESHAPE; a
+ * pointer off a 16-byte boundary or a row stride that is no multiple of 4 floats: IEF_EALIGN (lddq counts only with dQ).  Nothing
+ * is launched by a refused call.  Safe under stream capture (no allocation, no synchronisation). */
+#define IEF_CROSS_BWD_MAX_L 80
+int ief_attn_cross_bwd_f32(const float* Q, const float* K, const float* V, const float* dO, float* dQ, float* dK, float* dV,
+                           float* scratch, int B, int heads, int N, int L, int d, int ldq, int ldk, int ldv, int ldo, int lddq,
+                           int lddk, int lddv, float scale, void* stream);
+/* workgroups per (batch, head) of the main kernel above = partials per (batch, head); 0 for a head dim it does not take */
+int ief_cross_bwd_blocks(int N, int d);
+/* floats of `scratch` for ief_attn_cross_bwd_f32: B * heads * blocks * 2 * L * d; 0 for an unsupported shape.  (long long, the
+ * header's one 64-bit return type: every entry point is declared over the types the derived binding knows) */
+long long ief_cross_bwd_scratch_floats(int B, int heads, int N, int L, int d);
 /* y[i] += a * x[i] (fp32): the plain SGD step on the UNet input (sd_utils.py:160,174) */
 int ief_axpy_f32(float* y, const float* x, float a, long long n, void* stream);
 /* GroupNorm(+SiLU) whose statistics were left by the kernels that produced x (and x2): cstat1 / cstat2 are those launches'
