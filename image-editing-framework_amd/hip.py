@@ -713,6 +713,123 @@ def _conv_out(dev, out, g, dtype, device):
     return out
 
 
+# ------------------------------------------------------------------------------- attention: the launch front-end
+# What the attention wrappers of the three modes (here and `planes.attn_flash`) have in common: the geometry of a launch
+# (`attn_geometry`, shapes only), the strided layout of an operand (`_attn_layout`) and the fields of `IefAttnF32Params` that the
+# fused fp32-storage launches fill alike (`_fill_attn`).  The library sees pointers and leading dimensions only: a `v` one row
+# shorter than `k` must end here, as a ValueError, not on the device as a read out of bounds.
+AttnGeometry = collections.namedtuple("AttnGeometry", "B N L C d")
+
+
+def attn_geometry(q, k, v, heads, out=None, do=None, o=None, lse=None, q_src=False, k_src=False, v_src=False, batch=None,
+                  who="attn_flash"):
+    """the geometry of one attention launch from SHAPES alone (tuples): q [Bq, N, C], k / v [Bk | Bv, L, C], C = heads * d.
+    The OPERAND-BATCH rule: the launch has B = `batch` batch rows (default: q's); an operand WITHOUT a batch-row list (`q_src` /
+    `k_src` / `v_src` false) must have exactly B of them, an operand WITH one may have any number -- row b of the launch reads
+    batch row list[b] of it, which only the list's maker can check (`BatchRows` on the host; the lists a control plan switches
+    per step live on the device), so a Bp-row q under a 2 Bp-row launch, or sources of more rows than the destination, are
+    admitted.  The DESTINATION rule: `out` (the result, or the destination a gathered / class-masked launch overwrites) is
+    [B, N, C] and `lse` [B, heads, N], both counted in the launch's rows; `do` / `o` (the backward's upstream gradient and forward
+    output) have q's shape.  Which head dims and key counts have a kernel is not decided here (the `*_ok` predicates and the
+    library's IEF_ESHAPE do that).  ValueError (prefixed `who`) on a mismatch."""
+    for t, nm in ((q, "q"), (k, "k"), (v, "v"), (out, "out"), (do, "do"), (o, "o")):
+        if t is not None and len(t) != 3:
+            raise ValueError(f"{who}: {nm} must be [B, rows, heads*d], got {tuple(t)}")
+    Bq, N, C = q
+    L = k[1]
+    if heads < 1 or C % heads:
+        raise ValueError(f"{who}: {C} channels are not a multiple of heads = {heads}")
+    if k[2] != C or v[2] != C:
+        raise ValueError(f"{who}: k / v must have q's {C} channels, got {k[2]} / {v[2]}")
+    if v[1] != L:
+        raise ValueError(f"{who}: v must have k's {L} rows, got {v[1]}")
+    if N < 1 or L < 1:
+        raise ValueError(f"{who}: no queries or no keys ({N}, {L})")
+    B = Bq if batch is None else int(batch)
+    for t, nm, listed in ((q, "q", q_src), (k, "k", k_src), (v, "v", v_src)):
+        if not listed and t[0] != B:
+            raise ValueError(f"{who}: a launch of {B} batch rows over {nm} of {t[0]} needs {nm}_src")
+    if out is not None and tuple(out) != (B, N, C):
+        raise ValueError(f"{who}: the destination must be [{B}, {N}, {C}], got {tuple(out)}")
+    for t, nm in ((do, "do"), (o, "o")):
+        if t is not None and tuple(t) != (Bq, N, C):
+            raise ValueError(f"{who}: {nm} must have q's shape [{Bq}, {N}, {C}], got {tuple(t)}")
+    if lse is not None and tuple(lse) != (B, heads, N):
+        raise ValueError(f"{who}: lse must be [B, heads, N] = [{B}, {heads}, {N}], got {tuple(lse)}")
+    return AttnGeometry(B, N, L, C, C // heads)
+
+
+def _attn_layout(t, name, dev):
+    """(batch stride, ld) of an attention operand, gradient or destination: 3-D, unit channel stride, batch stride = rows * ld
+    where there is more than one batch row (column slices of a wider projection are fine); dev: the mode's tensor check, as for
+    `_rows_ld_of` (`planes._hi` for operand planes: it returns the hi plane the strides are read from)"""
+    h = dev(t, name)
+    if h.dim() != 3 or h.stride(2) != 1 or (h.shape[0] > 1 and h.stride(0) != h.shape[1] * h.stride(1)):
+        raise ValueError(f"{name}: expected [B, rows, heads*d] with unit channel stride and batch stride rows * ld")
+    return h.stride(0), h.stride(1)
+
+
+def _attn_geometry_of(dev, who, q, k, v, heads, out=None, do=None, o=None, **kw):
+    """`attn_geometry` of a launch after the mode's tensor check `dev` and the layout check of everything it is given"""
+    for t, nm in ((q, "q"), (k, "k"), (v, "v"), (out, "out"), (do, "do"), (o, "o")):
+        if t is not None:
+            _attn_layout(t, nm, dev)
+    return attn_geometry(_shape(q), _shape(k), _shape(v), heads, _shape(out), _shape(do), _shape(o), who=who, **kw)
+
+
+def _grad_like(t, g, name, who):
+    """the gradient buffer of operand t: fresh, or the caller's (a column slice of a wider buffer, say) of t's shape"""
+    if g is None:
+        return torch.empty(t.shape, dtype=t.dtype, device=t.device)
+    _attn_layout(g, name, _act32 if _is32(t) else _dev16)
+    if g.shape != t.shape:
+        raise ValueError(f"{who}: {name} must have the shape of its operand")
+    return g
+
+
+def _fill_attn(p, g, heads, scale, q, k, v, q_src=None, k_src=None, v_src=None, x3=1, out=None, out_planes=False):
+    """the fields of IefAttnF32Params that every fused fp32-storage attention launch fills (`_fill_epilogue`'s counterpart): the
+    operands -- fp32 tensors (Q / K / V) or `planes.Planes` (Qp / Kp / Vp + plane offsets) -- with their strides, B heads N L d
+    scale of the geometry g, the three batch-row lists, x3 and the destination: fresh operand planes for to_out's GEMM
+    (`out_planes` true, `planes.attn_out_args`), the caller's fp32 `out`, a fresh fp32 tensor, or -- `out_planes` a Planes, what
+    a gathered / class-masked launch overwrites -- the caller's planes and, if given, its fp32 `out` beside them.  The launch
+    carries the destination's batch stride, so views such as o[1::2] are fine.  Operands and destination have passed
+    `attn_geometry`.  Returns the result; the caller adds what is its own and launches."""
+    for t, nm in ((q, "Q"), (k, "K"), (v, "V")):
+        h = t
+        if not isinstance(t, torch.Tensor):
+            h, nm = t.hi, nm + "p"
+            setattr(p, "plane" + nm[0], t.plane)
+        setattr(p, nm, h.data_ptr())
+        setattr(p, f"s{nm[0]}b", h.stride(0))
+        setattr(p, "ld" + nm[0].lower(), h.stride(1))
+    p.B, p.heads, p.N, p.L, p.d, p.scale = g.B, heads, g.N, g.L, g.d, scale
+    p.q_src, p.k_src, p.v_src = _ptr(_devi32(q_src, "q_src")), _ptr(_devi32(k_src, "k_src")), _ptr(_devi32(v_src, "v_src"))
+    p.x3 = x3
+    dest_p = out_planes if hasattr(out_planes, "hi") else None
+    if dest_p is not None:
+        hp = dest_p.hi
+        p.OutP, p.planeO, p.sOPb, p.ldp = hp.data_ptr(), dest_p.plane, hp.stride(0), hp.stride(1)
+        if out is None:
+            return dest_p
+    elif out_planes:
+        from . import planes as _pl
+        return _pl.attn_out_args(p, g.B, g.N, g.C, h.device)[0]
+    elif out is None:
+        out = torch.empty(g.B, g.N, g.C, dtype=torch.float32, device=h.device)
+    p.Out, p.sOb, p.ldo = _act32(out, "out").data_ptr(), out.stride(0), out.stride(1)
+    return dest_p or out
+
+
+def _edit_tables(mt, coef, dtype, who="attn_cross_p2p"):
+    """the Prompt-to-Prompt edit tables of a launch: mt [slots, 96, 96] in the mode's dtype, coef [slots, 2, 96] fp32, contiguous"""
+    if not (isinstance(mt, torch.Tensor) and mt.is_cuda and mt.dtype == dtype):
+        raise TypeError(f"{who}: mt must be a {dtype} device tensor")
+    _dev32(coef, "coef")
+    if tuple(mt.shape[-2:]) != (96, 96) or not mt.is_contiguous() or coef.shape[-1] != 96:
+        raise ValueError(f"{who}: mt must be contiguous [slots,96,96] {dtype}, coef [slots,2,96] fp32")
+
+
 def gemm(a, w, bias=None, residual=None, rowvec=None, rows_per_batch=0, out=None, out_scale=1.0, tile_hint=0, splits=1,
          stages=2, geglu=False, ln=None, row_stats=False, col_stats=False):
     """out[..., n] = (a[..., :] . w[n, :] + bias[n] + rowvec[row // rows_per_batch, n] + residual[..., n]) * out_scale
@@ -1211,29 +1328,25 @@ def geglu(x, out=None):
 
 
 # ------------------------------------------------------------------------------- attention
-def _attn_common(p, q, k, v, out, heads):
-    B, N, _ = q.shape
-    L = k.shape[1]
-    d = out.shape[-1] // heads
-    for t, nm in ((q, "q"), (k, "k"), (v, "v"), (out, "out")):
-        _dev16(t, nm)
-        if t.dim() != 3:
-            raise ValueError(f"{nm}: expected [B, rows, heads*d]")
-        if t.shape[0] > 1 and t.stride(0) != t.shape[1] * t.stride(1):
-            raise ValueError(f"{nm}: batch stride must equal rows * ld")
-    p.Q, p.K, p.V, p.Out = q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr()
-    p.B, p.heads, p.N, p.L, p.d = B, heads, N, L, d
-    p.ldq, p.ldk, p.ldv, p.ldo = q.stride(1), k.stride(1), v.stride(1), out.stride(1)
+def _attn_common(p, who, q, k, v, out, heads, **kw):
+    """the operands of an fp16 attention launch (IefAttnParams / IefCrossParams / IefAttnBwdParams name them alike) after
+    `attn_geometry`; kw: its lse / *_src / do / o"""
+    g = _attn_geometry_of(_dev16, who, q, k, v, heads, out, **kw)
+    p.Q, p.K, p.V = q.data_ptr(), k.data_ptr(), v.data_ptr()
+    p.B, p.heads, p.N, p.L, p.d = g.B, heads, g.N, g.L, g.d
+    p.ldq, p.ldk, p.ldv = q.stride(1), k.stride(1), v.stride(1)
+    if out is not None:
+        p.Out, p.ldo = out.data_ptr(), out.stride(1)
+    return g
 
 
 _FLASH_VARIANT_ENV = int(os.environ.get("IEF_FLASH_VARIANT", "0"))      # read once: which flash kernel variant 0 means
 
 
-def _batched32(p, t, heads, d, which):
-    """strides of a [B, rows, heads*d] fp32 operand of a batched product: per batch row and per head"""
-    if t.dim() != 3 or t.stride(2) != 1 or (t.shape[0] > 1 and t.stride(0) != t.shape[1] * t.stride(1)):
-        raise ValueError(f"{which}: expected [B, rows, heads*d] with batch stride rows * ld")
-    return t.stride(0), d, t.stride(1)
+def _batched32(t, d, which):
+    """strides of a [B, rows, heads*d] fp32 operand of a batched product: per batch row, per head and per row"""
+    sb, ld = _attn_layout(t, which, _act32)
+    return sb, d, ld
 
 
 X3_SPLIT_BELOW = int(os.environ.get("IEF_X3_SPLIT_BELOW", "384"))      # split-K policy of the x3 GEMM (A/B runs)
@@ -1242,6 +1355,48 @@ X3_SPLIT_BELOW_WIDE = int(os.environ.get("IEF_X3_SPLIT_BELOW_WIDE", "129"))
 X3_SPLIT_TARGET_WIDE = int(os.environ.get("IEF_X3_SPLIT_TARGET_WIDE", "256"))
 GN3_F32 = os.environ.get("IEF_GN3_F32", "1") == "1"          # 0: the one-launch fp32 GroupNorm (A/B runs)
 FLASH_F32 = os.environ.get("IEF_FLASH_F32", "1") == "1"      # 0: always materialise the fp32 maps (A/B runs)
+X3_FUSE_CROSS = os.environ.get("IEF_X3_FUSE_CROSS", "1") == "1"      # 0: materialised cross maps (scores, softmax, edit, apply: A/B runs)
+X3_FUSED_BWD = os.environ.get("IEF_X3_FUSED_BWD", "1") == "1"      # 0: the reverse pass keeps the materialised maps everywhere (A/B runs)
+
+
+# ------------------------------------------------------------------------------- attention: which kernel takes a layer
+# Pure host predicates of (head dim, key count, mode, switches); every set of head dims is written once, here (the operand-planes
+# kernel's is `planes.FLASH_PLANES_DIMS`).  The library refuses what they do not admit (IEF_ESHAPE).
+_FLASH_F32_DIMS = (32, 40, 64, 80, 160)         # attn_flash_f32_kernel / attn_flash_x3_kernel (`ief_attn_flash_f32` on fp32 operands)
+_CROSS_P2P_X3_DIMS = (40, 64, 80, 160)
+CROSS_MAP_GRAD_MAX_L = cabi.defines["IEF_CROSS_MAP_GRAD_MAX_L"]
+_CROSS_MAP_GRAD_DIMS = (32, 40, 64, 80, 160)
+CROSS_BWD_MAX_L = cabi.defines["IEF_CROSS_BWD_MAX_L"]
+_CROSS_BWD_ROUTED_DIMS = (32, 40, 64, 80)
+
+
+def cross_p2p_x3_ok(d, L) -> bool:
+    """`attn_cross_p2p_x3_kernel` (the edited cross-attention of the f16x3 mode in one launch) has this shape: the edit tables
+    hold 96 tokens.  The mode and the IEF_X3_FUSE_CROSS / IEF_FLASH_F32 switches are the caller's terms."""
+    return int(d) in _CROSS_P2P_X3_DIMS and int(L) <= 96
+
+
+def x3_fused_bwd_ok(d: int, L: int) -> bool:
+    """the fp32-storage reverse pass differentiates this attention layer with `ief_attn_bwd_x3` (P and dS recomputed per tile from
+    the forward's lse, no map in HBM): split-operand mode, head dims 40 / 64 (the levels whose maps are hundreds of MB), at
+    least 128 keys (self-attention; the 77-key cross maps are small and keep the materialised path)"""
+    return X3_FUSED_BWD and _F32_CONTRACT == "x3" and FLASH_F32 and d in (40, 64) and L >= 128
+
+
+def cross_map_grad_ok(d, L, dtype=torch.float32) -> bool:
+    """`cross_map_grad` takes this cross-attention module: fp32 operands, a head dim of the kernel's set and at most
+    CROSS_MAP_GRAD_MAX_L keys (the LDS image of K, V and the two per-query columns fits a CU).  Everything else keeps
+    `attn_bwd(want_dkv=False)` + `attn_map_loss_bwd`."""
+    return dtype == torch.float32 and int(d) in _CROSS_MAP_GRAD_DIMS and 1 <= int(L) <= CROSS_MAP_GRAD_MAX_L
+
+
+def cross_bwd_ok(d, L, dtype=torch.float32) -> bool:
+    """the reverse pass differentiates this attention with `cross_bwd`: fp32 operands, at most CROSS_BWD_MAX_L keys (the LDS image
+    of K, V, the two per-query columns and a workgroup's q / dO rows fits a CU) and a head dim of 32 / 40 / 64 / 80 -- a shape rule,
+    no switch.  The kernel also takes d = 160, but that head dim belongs to the 16 x 16 and 8 x 8 levels, whose few workgroups sit on
+    the kernel's latency floor: measured 63-76 us per module against 50-72 us materialised (DESIGN.md section 7), so those levels,
+    like everything else, keep the materialised maps of `_attn_bwd_f32`."""
+    return dtype == torch.float32 and int(d) in _CROSS_BWD_ROUTED_DIMS and 1 <= int(L) <= CROSS_BWD_MAX_L
 
 
 def _attn_flash_f32(q, k, v, heads, scale, q_src=None, k_src=None, v_src=None, out=None, out_planes=False, lse=None, key_splits=1,
@@ -1251,39 +1406,23 @@ def _attn_flash_f32(q, k, v, heads, scale, q_src=None, k_src=None, v_src=None, o
     out_planes (split-operand mode only): the result leaves as operand planes for to_out's GEMM (`planes.Planes`);
     lse (split-operand mode only): fp32 [B, heads, N] receiving the row log-sum-exp (log2 units) for `ief_attn_bwd_x3`"""
     lib = load()
-    B, N, C = q.shape
-    L, d = k.shape[1], C // heads
-    if batch is not None:
-        B = int(batch)
-    if not FLASH_F32 or d not in (32, 40, 64, 80, 160):
+    g = _attn_geometry_of(_act32, "attn_flash", q, k, v, heads, None if out_planes else out, lse=_shape(lse), batch=batch,
+                          q_src=q_src is not None, k_src=k_src is not None, v_src=v_src is not None)
+    B, N, L, d = g.B, g.N, g.L, g.d
+    if not FLASH_F32 or d not in _FLASH_F32_DIMS:
         return None
+    if out_planes and _F32_CONTRACT != "x3":
+        raise ValueError("attn_flash: operand planes exist in the split-operand mode only")
     p = IefAttnF32Params()
-    p.Q, p.K, p.V = _act32(q, "q").data_ptr(), _act32(k, "k").data_ptr(), _act32(v, "v").data_ptr()
-    op = None
-    if out_planes:
-        if _F32_CONTRACT != "x3":
-            raise ValueError("attn_flash: operand planes exist in the split-operand mode only")
-        from . import planes as _pl
-        op, _ = _pl.attn_out_args(p, B, N, C, q.device)
-    else:
-        if out is None:
-            out = torch.empty(B, N, C, dtype=torch.float32, device=q.device)
-        p.Out = _act32(out, "out").data_ptr()
-        p.sOb, _, p.ldo = _batched32(p, out, heads, d, "out")
-    p.B, p.heads, p.N, p.L, p.d, p.scale = B, heads, N, L, d, scale
-    p.sQb, _, p.ldq = _batched32(p, q, heads, d, "q")
-    p.sKb, _, p.ldk = _batched32(p, k, heads, d, "k")
-    p.sVb, _, p.ldv = _batched32(p, v, heads, d, "v")
-    p.q_src, p.k_src, p.v_src = _ptr(_devi32(q_src, "q_src")), _ptr(_devi32(k_src, "k_src")), _ptr(_devi32(v_src, "v_src"))
-    p.x3 = 1 if _F32_CONTRACT == "x3" else 0
+    res = _fill_attn(p, g, heads, scale, q, k, v, q_src, k_src, v_src, 1 if _F32_CONTRACT == "x3" else 0, out, out_planes)
     if lse is not None:
-        if not p.x3 or tuple(_dev32(lse, "lse").shape) != (B, heads, N) or not lse.is_contiguous():
+        if not p.x3:
             raise ValueError("attn_flash: lse (contiguous fp32 [B, heads, N]) is written by the split-operand kernel only")
-        p.lse = lse.data_ptr()
+        p.lse = _dev32(lse, "lse").data_ptr()
     p.key_splits = int(key_splits)      # > 1: the library refuses (IEF_EINVAL) -- only the operand-planes kernel splits its keys
     with _Timed(f"attn_flash_{'x3' if p.x3 else 'f32'}_kernel<{d}>", 4.0 * B * heads * N * L * d, 4.0 * B * heads * d * (2 * N + 2 * L)):
         _check(lib.ief_attn_flash_f32(byref(p), _stream()), "ief_attn_flash_f32")
-    return op if out_planes else out
+    return res
 
 
 def _attn_scores_f32(q, k, heads, scale, q_src=None, k_src=None, out=None, softmax=True):
@@ -1301,8 +1440,8 @@ def _attn_scores_f32(q, k, heads, scale, q_src=None, k_src=None, out=None, softm
     p = IefGemmF32Params()
     p.A, p.W, p.Out = q.data_ptr(), k.data_ptr(), out.data_ptr()
     p.M, p.N, p.K = N, L, d
-    p.sAb, p.sAh, p.lda = _batched32(p, q, heads, d, "q")
-    p.sWb, p.sWh, p.ldw = _batched32(p, k, heads, d, "k")
+    p.sAb, p.sAh, p.lda = _batched32(q, d, "q")
+    p.sWb, p.sWh, p.ldw = _batched32(k, d, "k")
     p.sOb, p.sOh, p.ldo = heads * N * L, N * L, L
     p.batch, p.heads, p.out_scale = B, heads, scale
     p.a_src, p.w_src = _ptr(_devi32(q_src, "q_src")), _ptr(_devi32(k_src, "k_src"))
@@ -1346,8 +1485,8 @@ def _attn_apply_f32(probs, v, heads, v_src=None, out=None, map_scale=None):
     p.A, p.W, p.Out = probs.data_ptr(), v.data_ptr(), out.data_ptr()
     p.M, p.N, p.K = N, d, L
     p.sAb, p.sAh, p.lda = heads * N * L, N * L, L
-    p.sWb, p.sWh, p.ldw = _batched32(p, v, heads, d, "v")
-    p.sOb, p.sOh, p.ldo = _batched32(p, _act32(out, "out"), heads, d, "out")
+    p.sWb, p.sWh, p.ldw = _batched32(v, d, "v")
+    p.sOb, p.sOh, p.ldo = _batched32(out, d, "out")
     p.batch, p.heads, p.out_scale, p.transb = B, heads, 1.0, 1
     p.w_src = _ptr(_devi32(v_src, "v_src"))
     kn = _set_x3(p, X3_SCALE_PROB if map_scale is None else map_scale, X3_SCALE_ACT)    # maps <= 1: a large scale keeps the lo halves of small entries normal
@@ -1359,9 +1498,9 @@ def _attn_apply_f32(probs, v, heads, v_src=None, out=None, map_scale=None):
 def p2p_cross_edit_(probs, B, heads, edit_src, edit_slot, mt32, coef):
     """in place on fp32 maps [B*heads, N, L]: P'[w] = c1[w] (P_src M)[w] + c2[w] P_tgt[w] for the rows edit_src marks"""
     lib = load()
-    _act32(probs, "probs"), _dev32(mt32, "mt32"), _dev32(coef, "coef")
-    if tuple(mt32.shape[-2:]) != (96, 96) or coef.shape[-1] != 96 or not probs.is_contiguous():
-        raise ValueError("p2p_cross_edit_: mt32 must be [slots,96,96] fp32, coef [slots,2,96] fp32, probs contiguous")
+    _edit_tables(mt32, coef, torch.float32, "p2p_cross_edit_")
+    if not _act32(probs, "probs").is_contiguous():
+        raise ValueError("p2p_cross_edit_: probs must be contiguous")
     _check(lib.ief_p2p_cross_edit_f32(probs.data_ptr(), _devi32(edit_src, "edit_src").data_ptr(),
                                       _devi32(edit_slot, "edit_slot").data_ptr(), mt32.data_ptr(), coef.data_ptr(), B, heads,
                                       probs.shape[1], probs.shape[2], _stream()), "ief_p2p_cross_edit_f32")
@@ -1394,21 +1533,17 @@ def attn_flash(q, k, v, heads, scale, q_src=None, k_src=None, v_src=None, out=No
     if out is None:
         out = torch.empty(q.shape[0], q.shape[1], q.shape[2], dtype=torch.float16, device=q.device)
     p = IefAttnParams()
-    _attn_common(p, q, k, v, out, heads)
+    _attn_common(p, "attn_flash", q, k, v, out, heads, lse=_shape(lse), q_src=q_src is not None, k_src=k_src is not None,
+                 v_src=v_src is not None)
     p.scale = scale
     p.variant = variant if variant else _FLASH_VARIANT_ENV                              # env: A/B runs only
     if lse is not None:
-        if tuple(_dev32(lse, "lse").shape) != (q.shape[0], heads, q.shape[1]):
-            raise ValueError("attn_flash: lse must be fp32 [B, heads, N]")
-        p.lse = lse.data_ptr()
+        p.lse = _dev32(lse, "lse").data_ptr()
     p.q_src, p.k_src, p.v_src = _ptr(_devi32(q_src, "q_src")), _ptr(_devi32(k_src, "k_src")), _ptr(_devi32(v_src, "v_src"))
     kern = {1: "attn_flash_kernel", 2: "attn_flash_pp_kernel"}.get(p.variant, "attn_flash_sp_kernel")
     with _Timed(f"{kern}<{p.d}>", 4.0 * p.B * p.heads * p.N * p.L * p.d, 2.0 * p.B * p.heads * p.d * (2 * p.N + 2 * p.L)):
         _check(lib.ief_attn_flash_f16(byref(p), _stream()), "ief_attn_flash_f16")
     return out
-
-
-X3_FUSE_CROSS = os.environ.get("IEF_X3_FUSE_CROSS", "1") == "1"      # 0: materialised cross maps (scores, softmax, edit, apply: A/B runs)
 
 
 def map_split_scale(coef_bound: float) -> float:
@@ -1452,51 +1587,36 @@ def cfg_q_rows(Bp, device):
     return r
 
 
+def _cfg_rows_of(q_src, q, k):
+    """the device list of a cross-attention launch's q_src: a `BatchRows` built for q's batch rows, one entry per batch row of k"""
+    if not isinstance(q_src, BatchRows) or q_src.rows != q.shape[0] or q_src.n != k.shape[0]:
+        raise ValueError("attn_cross_p2p: q_src must be a hip.BatchRows with one entry per batch row of k / v, checked against "
+                         "the batch rows of q")
+    return q_src.dev
+
+
 def _attn_cross_p2p_x3(q, k, v, heads, scale, edit_src, edit_slot, mt32, coef, out=None, out_planes=False, coef_bound=1.0,
                        q_src=None):
     """`ief_attn_cross_p2p_f32`: the edited cross-attention layer of the f16x3 mode in one launch (maps stay in registers).
     coef_bound: max_w (|c1| + |c2|) over the plan's coefficient tables (sizes the split of the edited maps).
     edit_src None: plain attention by the same kernel.  q_src (`BatchRows`): the launch's batch is k's; row b reads q[q_src[b]]."""
     lib = load()
-    B, N, C = q.shape
-    L, d = k.shape[1], C // heads
-    if q_src is not None:
-        if not isinstance(q_src, BatchRows) or q_src.rows != q.shape[0] or q_src.n != k.shape[0]:
-            raise ValueError("attn_cross_p2p: q_src must be a hip.BatchRows with one entry per batch row of k / v, checked against "
-                             "the batch rows of q")
-        B = k.shape[0]
-    if k.shape[0] != B or v.shape[0] != B:
-        raise ValueError("attn_cross_p2p: q, k, v must have one batch (q may have another one with q_src)")
+    rows = None if q_src is None else _cfg_rows_of(q_src, q, k)
+    g = _attn_geometry_of(_act32, "attn_cross_p2p", q, k, v, heads, None if out_planes else out, q_src=q_src is not None,
+                          batch=None if q_src is None else k.shape[0])
+    B, N, L, d = g.B, g.N, g.L, g.d
     if edit_src is not None:
-        _dev32(mt32, "mt32"), _dev32(coef, "coef")
-        if tuple(mt32.shape[-2:]) != (96, 96) or coef.shape[-1] != 96 or not mt32.is_contiguous() or not coef.is_contiguous():
-            raise ValueError("attn_cross_p2p: mt must be contiguous [slots,96,96] fp32, coef [slots,2,96] fp32")
+        _edit_tables(mt32, coef, torch.float32)
         if _devi32(edit_src, "edit_src").numel() != B or _devi32(edit_slot, "edit_slot").numel() != B:
             raise ValueError("attn_cross_p2p: edit_src / edit_slot need one entry per batch row")
     p = IefAttnF32Params()
-    p.Q, p.K, p.V = _act32(q, "q").data_ptr(), _act32(k, "k").data_ptr(), _act32(v, "v").data_ptr()
-    op = None
-    if out_planes:
-        from . import planes as _pl
-        op, _ = _pl.attn_out_args(p, B, N, C, q.device)
-    else:
-        if out is None:
-            out = torch.empty(B, N, C, dtype=torch.float32, device=q.device)
-        p.Out = _act32(out, "out").data_ptr()
-        p.sOb, _, p.ldo = _batched32(p, out, heads, d, "out")
-    p.B, p.heads, p.N, p.L, p.d, p.scale = B, heads, N, L, d, scale
-    p.sQb, _, p.ldq = _batched32(p, q, heads, d, "q")
-    p.sKb, _, p.ldk = _batched32(p, k, heads, d, "k")
-    p.sVb, _, p.ldv = _batched32(p, v, heads, d, "v")
+    res = _fill_attn(p, g, heads, scale, q, k, v, q_src=rows, out=out, out_planes=out_planes)
     p.p_scale = map_split_scale(coef_bound)
-    p.x3 = 1
-    if q_src is not None:
-        p.q_src = q_src.dev.data_ptr()
     nedit = 2.0 * B * heads * N * 96 * 96 if edit_src is not None else 0.0
     with _Timed(f"attn_cross_p2p_x3_kernel<{d}>", 4.0 * B * heads * N * L * d + nedit, 4.0 * B * heads * d * (2 * N + 2 * L)):
         _check(lib.ief_attn_cross_p2p_f32(byref(p), _ptr(edit_src), _ptr(edit_slot), _ptr(mt32) if edit_src is not None else None,
                                           _ptr(coef) if edit_src is not None else None, _stream()), "ief_attn_cross_p2p_f32")
-    return op if out_planes else out
+    return res
 
 
 def attn_cross_p2p(q, k, v, heads, scale, edit_src=None, edit_slot=None, mt=None, coef=None, out=None, out_planes=False,
@@ -1507,22 +1627,21 @@ def attn_cross_p2p(q, k, v, heads, scale, edit_src=None, edit_slot=None, mt=None
     q_src (`BatchRows`, split-operand mode, L <= 96 only): k / v carry the launch's batch rows, row b reads q[q_src[b]] -- the edited
     layer on `attn_cross_p2p_x3_kernel`, the unedited one on the flash kernel it takes anyway; no other route (ValueError)."""
     if q_src is not None:
-        if not (_is32(q) and _F32_CONTRACT == "x3" and k.shape[1] <= 96 and q.shape[2] // heads in (40, 64, 80, 160)):
+        if not (_is32(q) and _F32_CONTRACT == "x3" and cross_p2p_x3_ok(q.shape[2] // heads, k.shape[1])):
             raise ValueError("attn_cross_p2p: q_src exists on the fused split-operand kernel only (f16x3, <= 96 keys, head dim 40 / "
                              "64 / 80 / 160)")
-        if not isinstance(q_src, BatchRows) or q_src.rows != q.shape[0] or q_src.n != k.shape[0] or v.shape[0] != k.shape[0]:
-            raise ValueError("attn_cross_p2p: q_src must be a hip.BatchRows with one entry per batch row of k / v, checked against "
-                             "the batch rows of q")
         if edit_src is None and FLASH_F32:      # the launch the unedited layer takes without q_src, hence its bits
-            return _attn_flash_f32(q, k, v, heads, scale, q_src=q_src.dev, out=out, out_planes=out_planes, batch=k.shape[0])
+            return _attn_flash_f32(q, k, v, heads, scale, q_src=_cfg_rows_of(q_src, q, k), out=out, out_planes=out_planes,
+                                   batch=k.shape[0])
         return _attn_cross_p2p_x3(q, k, v, heads, scale, edit_src, edit_slot, mt, coef, out, out_planes, coef_bound, q_src=q_src)
     if _is32(q):
         if edit_src is None:
             o = _attn_flash_f32(q, k, v, heads, scale, out=out, out_planes=out_planes)
             if o is not None:
                 return o
-        elif _F32_CONTRACT == "x3" and X3_FUSE_CROSS and k.shape[1] <= 96 and q.shape[2] // heads in (40, 64, 80, 160):
+        elif _F32_CONTRACT == "x3" and X3_FUSE_CROSS and cross_p2p_x3_ok(q.shape[2] // heads, k.shape[1]):
             return _attn_cross_p2p_x3(q, k, v, heads, scale, edit_src, edit_slot, mt, coef, out, out_planes, coef_bound)
+        _attn_geometry_of(_act32, "attn_cross_p2p", q, k, v, heads, out)
         probs = _attn_scores_f32(q, k, heads, scale)
         if edit_src is not None:
             p2p_cross_edit_(probs, q.shape[0], heads, edit_src, edit_slot, mt, coef)
@@ -1535,14 +1654,11 @@ def attn_cross_p2p(q, k, v, heads, scale, edit_src=None, edit_slot=None, mt=None
     if out is None:
         out = torch.empty(q.shape[0], q.shape[1], q.shape[2], dtype=torch.float16, device=q.device)
     p = IefCrossParams()
-    _attn_common(p, q, k, v, out, heads)
+    _attn_common(p, "attn_cross_p2p", q, k, v, out, heads)
     p.scale = scale
     p.edit_src, p.edit_slot = _ptr(_devi32(edit_src, "edit_src")), _ptr(_devi32(edit_slot, "edit_slot"))
     if edit_src is not None:
-        _dev16(mt, "mt")
-        _dev32(coef, "coef")
-        if tuple(mt.shape[-2:]) != (96, 96) or not mt.is_contiguous() or coef.shape[-1] != 96:
-            raise ValueError("attn_cross_p2p: mt must be [slots,96,96] fp16, coef [slots,2,96] fp32")
+        _edit_tables(mt, coef, torch.float16)
         p.MT, p.coef = mt.data_ptr(), coef.data_ptr()
     with _Timed(f"attn_cross_p2p_kernel<{p.d}>", 4.0 * p.B * p.heads * p.N * p.L * p.d,
                 2.0 * p.B * p.heads * p.d * (2 * p.N + 2 * p.L)):
@@ -1564,7 +1680,7 @@ def attn_probs(q, k, heads, scale, out=None):
         if tuple(probs.shape) != (B * heads, N, L) or not probs.is_contiguous():
             raise ValueError("attn_probs: out must be contiguous fp16 [B*heads, N, L]")
     p = IefAttnParams()
-    _attn_common(p, q, k, k, q, heads)
+    _attn_common(p, "attn_probs", q, k, k, q, heads)
     p.scale = scale
     _check(lib.ief_attn_probs_f16(byref(p), probs.data_ptr(), _stream()), "ief_attn_probs_f16")
     return probs
@@ -1585,8 +1701,8 @@ def attn_apply(probs, v, heads, out=None):
     if out is None:
         out = torch.empty(B, N, v.shape[2], dtype=torch.float16, device=v.device)
     p = IefAttnParams()
-    _attn_common(p, out, v, v, out, heads)
-    p.N, p.L = N, L
+    if _attn_common(p, "attn_apply", out, v, v, out, heads).N != N:
+        raise ValueError("attn_apply: out must have the maps' rows")
     _check(lib.ief_attn_apply_f16(byref(p), probs.data_ptr(), _stream()), "ief_attn_apply_f16")
     return out
 
@@ -1865,49 +1981,26 @@ def _softmax_bwd_f32_(probs, dprobs, scale):
     return dprobs
 
 
-X3_FUSED_BWD = os.environ.get("IEF_X3_FUSED_BWD", "1") == "1"      # 0: the reverse pass keeps the materialised maps everywhere (A/B runs)
-
-
-def x3_fused_bwd_ok(d: int, L: int) -> bool:
-    """the fp32-storage reverse pass differentiates this attention layer with `ief_attn_bwd_x3` (P and dS recomputed per tile from
-    the forward's lse, no map in HBM): split-operand mode, head dims 40 / 64 (the levels whose maps are hundreds of MB), at
-    least 128 keys (self-attention; the 77-key cross maps are small and keep the materialised path)"""
-    return X3_FUSED_BWD and _F32_CONTRACT == "x3" and FLASH_F32 and d in (40, 64) and L >= 128
-
-
 def _attn_bwd_x3(q, k, v, o, do, lse, heads, scale, dq, dk, dv, want_dq, want_dkv):
     lib = load()
-    B, N, C = q.shape
-    L, d = k.shape[1], C // heads
-    for t, nm in ((q, "q"), (k, "k"), (v, "v"), (o, "o"), (do, "do")):
-        _act32(t, nm)
-        if t.dim() != 3 or t.stride(2) != 1 or (t.shape[0] > 1 and t.stride(0) != t.shape[1] * t.stride(1)):
-            raise ValueError(f"{nm}: expected [B, rows, heads*d] with unit channel stride and batch stride rows * ld")
-    delta = torch.empty(B, heads, N, dtype=torch.float32, device=q.device)
-    _check(lib.ief_attn_bwd_delta_f32in(o.data_ptr(), do.data_ptr(), delta.data_ptr(), B, heads, N, d, o.stride(1), do.stride(1),
-                                        _stream()), "ief_attn_bwd_delta_f32in")
+    B, N, L, _, d = _attn_geometry_of(_act32, "attn_bwd", q, k, v, heads, do=do, o=o, lse=_shape(_dev32(lse, "lse")))
     p = IefAttnBwdF32Params()
-    p.Q, p.K, p.V, p.dO, p.lse, p.delta = q.data_ptr(), k.data_ptr(), v.data_ptr(), do.data_ptr(), _dev32(lse, "lse").data_ptr(), delta.data_ptr()
-    p.B, p.heads, p.N, p.L, p.d = B, heads, N, L, d
-    p.ldq, p.ldk, p.ldv, p.ldo = q.stride(1), k.stride(1), v.stride(1), do.stride(1)
-    p.scale, p.ds_mul = scale, X3_SCALE_PROB
     what = 0
-
-    def grad_like(t, g, nm):
-        if g is None:
-            g = torch.empty(t.shape, dtype=torch.float32, device=t.device)
-        _act32(g, nm)
-        if tuple(g.shape) != tuple(t.shape) or g.stride(2) != 1 or (g.shape[0] > 1 and g.stride(0) != g.shape[1] * g.stride(1)):
-            raise ValueError(f"{nm}: expected the shape of its operand, unit channel stride, batch stride rows * ld")
-        return g
     if want_dq:
-        dq = grad_like(q, dq, "dq")
+        dq = _grad_like(q, dq, "dq", "attn_bwd")
         p.dQ, p.lddq = dq.data_ptr(), dq.stride(1)
         what |= 1
     if want_dkv:
-        dk, dv = grad_like(k, dk, "dk"), grad_like(v, dv, "dv")
+        dk, dv = _grad_like(k, dk, "dk", "attn_bwd"), _grad_like(v, dv, "dv", "attn_bwd")
         p.dK, p.dV, p.lddk, p.lddv = dk.data_ptr(), dv.data_ptr(), dk.stride(1), dv.stride(1)
         what |= 2
+    delta = torch.empty(B, heads, N, dtype=torch.float32, device=q.device)
+    _check(lib.ief_attn_bwd_delta_f32in(o.data_ptr(), do.data_ptr(), delta.data_ptr(), B, heads, N, d, o.stride(1), do.stride(1),
+                                        _stream()), "ief_attn_bwd_delta_f32in")
+    p.Q, p.K, p.V, p.dO, p.lse, p.delta = q.data_ptr(), k.data_ptr(), v.data_ptr(), do.data_ptr(), lse.data_ptr(), delta.data_ptr()
+    p.B, p.heads, p.N, p.L, p.d = B, heads, N, L, d
+    p.ldq, p.ldk, p.ldv, p.ldo = q.stride(1), k.stride(1), v.stride(1), do.stride(1)
+    p.scale, p.ds_mul = scale, X3_SCALE_PROB
     fl = (6.0 if want_dq else 0.0) + (8.0 if want_dkv else 0.0)
     with _Timed(f"attn_bwd_x3_kernel<{d}>", fl * B * heads * N * L * d):
         _check(lib.ief_attn_bwd_x3(byref(p), what, _stream()), "ief_attn_bwd_x3")
@@ -1926,8 +2019,7 @@ def _attn_bwd_f32(q, k, v, do, heads, scale, dq, dk, dv, want_dq, want_dkv, o=No
         return _attn_bwd_x3(q, k, v, o, do, lse, heads, scale, dq, dk, dv, want_dq, want_dkv)
     if want_dkv and cross_bwd_ok(d, L, q.dtype) and not x3_fused_bwd_ok(d, L):
         return cross_bwd(q, k, v, do, heads, scale, dq=dq, dk=dk, dv=dv, want_dq=want_dq)
-    for t, nm in ((q, "q"), (k, "k"), (v, "v"), (do, "do")):
-        _act32(t, nm)
+    _attn_geometry_of(_act32, "attn_bwd", q, k, v, heads, do=do)
     probs = _attn_scores_f32(q, k, heads, scale)                          # [B*h, N, L]
     ds = _attn_scores_f32(do, v, heads, 1.0, softmax=False)               # dP = dO V^T
     _softmax_bwd_f32_(probs, ds, scale)
@@ -1971,17 +2063,6 @@ def _attn_map_loss_bwd_f32(q, k, ref, dq, heads, scale, gcoef, accumulate, loss,
     return dq
 
 
-CROSS_MAP_GRAD_MAX_L = cabi.defines["IEF_CROSS_MAP_GRAD_MAX_L"]
-_CROSS_MAP_GRAD_DIMS = (32, 40, 64, 80, 160)
-
-
-def cross_map_grad_ok(d, L, dtype=torch.float32) -> bool:
-    """`cross_map_grad` takes this cross-attention module: fp32 operands, a head dim of the kernel's set and at most
-    CROSS_MAP_GRAD_MAX_L keys (the LDS image of K, V and the two per-query columns fits a CU).  Everything else keeps
-    `attn_bwd(want_dkv=False)` + `attn_map_loss_bwd`."""
-    return dtype == torch.float32 and int(d) in _CROSS_MAP_GRAD_DIMS and 1 <= int(L) <= CROSS_MAP_GRAD_MAX_L
-
-
 def cross_map_grad_blocks(N, d):
     """loss partials per (batch, head) that `cross_map_grad` writes"""
     return load().ief_cross_map_grad_blocks(int(N), int(d))
@@ -1994,22 +2075,10 @@ def cross_map_grad(q, k, v, do, ref, heads, scale, gcoef, dq=None, loss=None, lo
     q / do [B,N,h*d], k / v [B,L,h*d] (strided views ok), ref fp32 [B*heads,N,L] contiguous; dq: None (allocated) or a view of
     q's shape; loss: optional fp32 [B*heads*cross_map_grad_blocks(N, d)] partials of sum (P - ref)^2, each times loss_coef."""
     lib = load()
-    for t, nm in ((q, "q"), (k, "k"), (v, "v"), (do, "do")):
-        _act32(t, nm)
-        if t.dim() != 3 or (t.shape[0] > 1 and t.stride(0) != t.shape[1] * t.stride(1)):
-            raise ValueError(f"cross_map_grad: {nm} must be [B, rows, h*d] with batch stride rows * ld")
-    B, N, C = q.shape
-    L = k.shape[1]
-    d = C // heads
-    if heads * d != C or tuple(k.shape) != (B, L, C) or tuple(v.shape) != (B, L, C) or tuple(do.shape) != (B, N, C):
-        raise ValueError("cross_map_grad: shape mismatch")
+    B, N, L, C, d = _attn_geometry_of(_act32, "cross_map_grad", q, k, v, heads, do=do)
     if tuple(_act32(ref, "ref").shape) != (B * heads, N, L) or not ref.is_contiguous():
         raise ValueError("cross_map_grad: ref must be contiguous fp32 [B*heads, N, L]")
-    if dq is None:
-        dq = torch.empty(B, N, C, dtype=torch.float32, device=q.device)
-    _act32(dq, "dq")
-    if tuple(dq.shape) != (B, N, C) or (B > 1 and dq.stride(0) != N * dq.stride(1)):
-        raise ValueError("cross_map_grad: dq must be [B, N, h*d] with batch stride N * ld")
+    dq = _grad_like(q, dq, "dq", "cross_map_grad")
     if loss is not None and _dev32(loss, "loss").numel() < B * heads * lib.ief_cross_map_grad_blocks(N, d):
         raise ValueError("cross_map_grad: loss needs B*heads*cross_map_grad_blocks(N, d) floats")
     with _Timed(f"cross_map_grad_f32_kernel<{d}>", 6.0 * B * heads * N * L * d,
@@ -2019,19 +2088,6 @@ def cross_map_grad(q, k, v, do, ref, heads, scale, gcoef, dq=None, loss=None, lo
                                                dq.stride(1), float(scale), float(gcoef), float(loss_coef), _stream()),
                "ief_attn_cross_map_grad_f32")
     return dq
-
-
-CROSS_BWD_MAX_L = cabi.defines["IEF_CROSS_BWD_MAX_L"]
-_CROSS_BWD_ROUTED_DIMS = (32, 40, 64, 80)
-
-
-def cross_bwd_ok(d, L, dtype=torch.float32) -> bool:
-    """the reverse pass differentiates this attention with `cross_bwd`: fp32 operands, at most CROSS_BWD_MAX_L keys (the LDS image
-    of K, V, the two per-query columns and a workgroup's q / dO rows fits a CU) and a head dim of 32 / 40 / 64 / 80 -- a shape rule,
-    no switch.  The kernel also takes d = 160, but that head dim belongs to the 16 x 16 and 8 x 8 levels, whose few workgroups sit on
-    the kernel's latency floor: measured 63-76 us per module against 50-72 us materialised (DESIGN.md section 7), so those levels,
-    like everything else, keep the materialised maps of `_attn_bwd_f32`."""
-    return dtype == torch.float32 and int(d) in _CROSS_BWD_ROUTED_DIMS and 1 <= int(L) <= CROSS_BWD_MAX_L
 
 
 def cross_bwd_blocks(N, d):
@@ -2045,25 +2101,9 @@ def cross_bwd(q, k, v, do, heads, scale, dq=None, dk=None, dv=None, want_dq=True
     q / do [B,N,h*d], k / v [B,L,h*d] (strided views ok); dq / dk / dv: None (allocated) or views of their operands' shapes, e.g.
     column slices of wider buffers; want_dq=False: dq is neither computed nor touched.  -> (dq or None, dk, dv)"""
     lib = load()
-    for t, nm in ((q, "q"), (k, "k"), (v, "v"), (do, "do")):
-        _act32(t, nm)
-        if t.dim() != 3 or (t.shape[0] > 1 and t.stride(0) != t.shape[1] * t.stride(1)):
-            raise ValueError(f"cross_bwd: {nm} must be [B, rows, h*d] with batch stride rows * ld")
-    B, N, C = q.shape
-    L = k.shape[1]
-    d = C // heads
-    if heads * d != C or tuple(k.shape) != (B, L, C) or tuple(v.shape) != (B, L, C) or tuple(do.shape) != (B, N, C):
-        raise ValueError("cross_bwd: shape mismatch")
-
-    def grad_like(t, g, nm):
-        if g is None:
-            g = torch.empty(t.shape, dtype=torch.float32, device=t.device)
-        _act32(g, nm)
-        if tuple(g.shape) != tuple(t.shape) or (g.shape[0] > 1 and g.stride(0) != g.shape[1] * g.stride(1)):
-            raise ValueError(f"cross_bwd: {nm} must have the shape of its operand and batch stride rows * ld")
-        return g
-    dq = grad_like(q, dq, "dq") if want_dq else None
-    dk, dv = grad_like(k, dk, "dk"), grad_like(v, dv, "dv")
+    B, N, L, C, d = _attn_geometry_of(_act32, "cross_bwd", q, k, v, heads, do=do)
+    dq = _grad_like(q, dq, "dq", "cross_bwd") if want_dq else None
+    dk, dv = _grad_like(k, dk, "dk", "cross_bwd"), _grad_like(v, dv, "dv", "cross_bwd")
     # the caller's scratch, as `delta` of ief_attn_bwd_x3: the caching allocator serves it under graph capture too
     scratch = torch.empty(max(1, lib.ief_cross_bwd_scratch_floats(B, heads, N, L, d)), dtype=torch.float32, device=q.device)
     with _Timed(f"cross_bwd_f32_kernel<{d}>", (10.0 if want_dq else 8.0) * B * heads * N * L * d,
@@ -2091,36 +2131,21 @@ def attn_bwd(q, k, v, o, do, lse, heads, scale, dq=None, dk=None, dv=None, ds_mu
     lib = load()
     if _is32(q):
         return _attn_bwd_f32(q, k, v, do, heads, scale, dq, dk, dv, want_dq, want_dkv, o=o, lse=lse)
-    B, N, _ = q.shape
-    L = k.shape[1]
-    d = o.shape[-1] // heads
-    for t, nm in ((q, "q"), (k, "k"), (v, "v"), (o, "o"), (do, "do")):
-        _dev16(t, nm)
-        if t.dim() != 3 or (t.shape[0] > 1 and t.stride(0) != t.shape[1] * t.stride(1)):
-            raise ValueError(f"{nm}: expected [B, rows, heads*d] with batch stride rows * ld")
-    _dev32(lse, "lse")
+    p = IefAttnBwdParams()
+    B, N, L, _, d = _attn_common(p, "attn_bwd", q, k, v, None, heads, do=do, o=o, lse=_shape(_dev32(lse, "lse")))
     delta = torch.empty(B, heads, N, dtype=torch.float32, device=q.device)
     _check(lib.ief_attn_bwd_delta_f32(o.data_ptr(), do.data_ptr(), delta.data_ptr(), B, heads, N, d, o.stride(1),
                                       do.stride(1), _stream()), "ief_attn_bwd_delta_f32")
-    p = IefAttnBwdParams()
-    p.Q, p.K, p.V, p.dO, p.lse, p.delta = q.data_ptr(), k.data_ptr(), v.data_ptr(), do.data_ptr(), lse.data_ptr(), delta.data_ptr()
-    p.B, p.heads, p.N, p.L, p.d = B, heads, N, L, d
-    p.ldq, p.ldk, p.ldv, p.ldo = q.stride(1), k.stride(1), v.stride(1), do.stride(1)
+    p.dO, p.ldo, p.lse, p.delta = do.data_ptr(), do.stride(1), lse.data_ptr(), delta.data_ptr()
     p.scale = scale
     p.ds_mul = float(ds_mul) if ds_mul is not None else float(min(L, 1024))
     what = 0
     if want_dq:
-        if dq is None:
-            dq = torch.empty(B, N, heads * d, dtype=torch.float16, device=q.device)
-        _dev16(dq, "dq")
+        dq = _grad_like(q, dq, "dq", "attn_bwd")
         p.dQ, p.lddq = dq.data_ptr(), dq.stride(1)
         what |= 1
     if want_dkv:
-        if dk is None:
-            dk = torch.empty(B, L, heads * d, dtype=torch.float16, device=q.device)
-        if dv is None:
-            dv = torch.empty(B, L, heads * d, dtype=torch.float16, device=q.device)
-        _dev16(dk, "dk"), _dev16(dv, "dv")
+        dk, dv = _grad_like(k, dk, "dk", "attn_bwd"), _grad_like(v, dv, "dv", "attn_bwd")
         p.dK, p.dV, p.lddk, p.lddv = dk.data_ptr(), dv.data_ptr(), dk.stride(1), dv.stride(1)
         what |= 2
         # few keys (cross-attention) => few workgroups: cut the query range so ~256 of them run

@@ -12,7 +12,7 @@ from ctypes import byref
 import torch
 
 from . import hip
-from .hip import IefGemmX3pParams, _check, _dev32, _ptr, _stream, _Timed, _zeros
+from .hip import IefGemmX3pParams, _check, _dev32, _ptr, _shape, _stream, _Timed, _zeros
 
 ACT_SCALE = 1.0          # activations: hi = fp16(x) — the fp16 range itself (65504), as on the fp16-storage path
 W_SCALE = hip.X3_SCALE_W
@@ -498,6 +498,13 @@ def attn_out_args(p, B, N, C, device, out32=False):
     return op, o32
 
 
+def _hi(t, name):
+    """the tensor check of a Planes operand, as `hip._dev16` / `hip._act32` are those of the other modes: its hi plane"""
+    if not isinstance(t, Planes) or t.dim() != 3:
+        raise TypeError(f"planes.attn_flash: {name} must be Planes [B, rows, heads*d]")
+    return t.hi
+
+
 FLASH_PLANES = os.environ.get("IEF_X3P_FLASH", "1") == "1"       # 0: the fused attention always takes fp32 q / k / v (A/B runs)
 FLASH_PLANES_DIMS = (40, 64, 80)
 
@@ -608,80 +615,44 @@ def attn_flash(q, k, v, heads, scale, q_src=None, k_src=None, v_src=None, out=No
         raise ValueError("planes.attn_flash: out_planes=<Planes> is the destination of a gathered launch (q_idx / k_idx) or a "
                          "class-masked one (q_cls / k_cls)")
     for t, nm in ((q, "q"), (k, "k"), (v, "v")):
-        if not isinstance(t, Planes) or t.dim() != 3:
-            raise TypeError(f"planes.attn_flash: {nm} must be Planes [B, rows, heads*d]")
-    B, N, C = q.shape
-    L, d = k.shape[1], C // heads
+        hip._attn_layout(t, nm, _hi)
+    # a gathered / class-masked launch overwrites rows of its destination, whose batch rows are the launch's and whose rows are
+    # q's (a gathered launch then counts its lists: p.N / p.L below); every other launch makes its own result
+    dest = (dest_p if dest_p is not None else out) if idx or cls else None
+    if dest_p is not None and out is not None and hip._act32(out, "out").shape != dest_p.shape:
+        raise ValueError("planes.attn_flash: out and out_planes must have one shape")
+    g = hip.attn_geometry(_shape(q), _shape(k), _shape(v), heads, out=_shape(dest), lse=_shape(lse), q_src=q_src is not None,
+                          k_src=k_src is not None, v_src=v_src is not None, batch=None if dest is None else dest.shape[0],
+                          who="planes.attn_flash")
+    B, N, L, C, d = g
     if d not in FLASH_PLANES_DIMS:
         raise ValueError(f"planes.attn_flash: head dim {d} has no planes instantiation")
+    for t, nm in ((q_src, "q_src"), (k_src, "k_src"), (v_src, "v_src")):
+        if dest is not None and t is not None and t.numel() != B:
+            raise ValueError(f"planes.attn_flash: {nm} must have one entry per destination batch row ({B})")
     p = hip.IefAttnF32Params()
-    for t, nm in ((q, "Q"), (k, "K"), (v, "V")):
-        h_ = t.hi
-        if h_.stride(2) != 1 or (h_.shape[0] > 1 and h_.stride(0) != h_.shape[1] * h_.stride(1)):
-            raise ValueError("planes.attn_flash: operands must be [B, rows, heads*d] with batch stride rows * ld")
-        setattr(p, nm + "p", h_.data_ptr())
-        setattr(p, "plane" + nm, t.plane)
-    p.ldq, p.ldk, p.ldv = q.hi.stride(1), k.hi.stride(1), v.hi.stride(1)
-    p.sQb, p.sKb, p.sVb = q.hi.stride(0), k.hi.stride(0), v.hi.stride(0)
-    p.B, p.heads, p.N, p.L, p.d, p.scale = B, heads, N, L, d, scale
+    res = hip._fill_attn(p, g, heads, scale, q, k, v, q_src, k_src, v_src, out=out,
+                         out_planes=out_planes if dest is dest_p else False)
     if idx:
-        hip._devi32(q_idx, "q_idx"), hip._devi32(k_idx, "k_idx"), hip._devi32(gate, "gate")
+        hip._devi32(q_idx, "q_idx"), hip._devi32(k_idx, "k_idx")
         if q_idx.dim() != 1 or k_idx.dim() != 1 or not 1 <= q_idx.numel() <= N or not 1 <= k_idx.numel() <= L:
             raise ValueError("planes.attn_flash: q_idx / k_idx must be non-empty 1-D lists no longer than the operand's rows")
-        rows_q = N
-        dest = dest_p.hi if dest_p is not None else hip._act32(out, "out")
-        if dest.dim() != 3 or dest.shape[1] != rows_q or dest.shape[2] != C:
-            raise ValueError(f"planes.attn_flash: the destination must be [Bo, {rows_q}, {C}]")
-        B, N, L = dest.shape[0], q_idx.numel(), k_idx.numel()
-        for t, nm in ((q_src, "q_src"), (k_src, "k_src"), (v_src, "v_src")):
-            if t is not None and t.numel() != B:
-                raise ValueError(f"planes.attn_flash: {nm} must have one entry per destination batch row ({B})")
-            if t is None and B != q.shape[0]:
-                raise ValueError(f"planes.attn_flash: a destination of {B} batch rows over operands of {q.shape[0]} needs {nm}")
-        p.B, p.N, p.L = B, N, L
-        p.q_idx, p.k_idx, p.gate = q_idx.data_ptr(), k_idx.data_ptr(), _ptr(gate)
+        p.N, p.L = N, L = q_idx.numel(), k_idx.numel()
+        p.q_idx, p.k_idx = q_idx.data_ptr(), k_idx.data_ptr()
     if cls:
-        hip._devi32(q_cls, "q_cls"), hip._devi32(k_cls, "k_cls"), hip._devi32(gate, "gate")
+        hip._devi32(q_cls, "q_cls"), hip._devi32(k_cls, "k_cls")
         if N % 32 or L % 32 or q_cls.numel() != N // 32 or k_cls.numel() != L // 32:
             raise ValueError(f"planes.attn_flash: q_cls / k_cls hold one word per 32 tokens ({N} queries, {L} keys: multiples of 32)")
-        dest = dest_p.hi if dest_p is not None else hip._act32(out, "out")
-        if dest.dim() != 3 or dest.shape[1] != N or dest.shape[2] != C:
-            raise ValueError(f"planes.attn_flash: the destination must be [Bo, {N}, {C}]")
-        B = dest.shape[0]
-        for t, nm in ((q_src, "q_src"), (k_src, "k_src"), (v_src, "v_src")):
-            if t is not None and t.numel() != B:
-                raise ValueError(f"planes.attn_flash: {nm} must have one entry per destination batch row ({B})")
-            if t is None and B != q.shape[0]:
-                raise ValueError(f"planes.attn_flash: a destination of {B} batch rows over operands of {q.shape[0]} needs {nm}")
-        p.B = B
-        p.q_cls, p.k_cls, p.gate = q_cls.data_ptr(), k_cls.data_ptr(), _ptr(gate)
-    p.q_src, p.k_src, p.v_src = _ptr(hip._devi32(q_src, "q_src")), _ptr(hip._devi32(k_src, "k_src")), _ptr(hip._devi32(v_src, "v_src"))
+        p.q_cls, p.k_cls = q_cls.data_ptr(), k_cls.data_ptr()
+    p.gate = _ptr(hip._devi32(gate, "gate"))
     if uni:
         hip._devi32(k2_src, "k2_src"), hip._devi32(v2_src, "v2_src")
         if k2_src.numel() != B or v2_src.numel() != B:
             raise ValueError(f"planes.attn_flash: k2_src / v2_src must have one entry per batch row ({B})")
         p.k2_src, p.v2_src = k2_src.data_ptr(), v2_src.data_ptr()
-    p.x3, p.zeros = 1, _zeros(q.device)
+    p.zeros = _zeros(q.device)
     if lse is not None:
-        if tuple(hip._dev32(lse, "lse").shape) != (B, heads, N):
-            raise ValueError("planes.attn_flash: lse must be contiguous fp32 [B, heads, N]")
-        p.lse = lse.data_ptr()
-    op = None
-    if dest_p is not None:
-        op, h_ = dest_p, dest_p.hi
-        if h_.stride(2) != 1:
-            raise ValueError("planes.attn_flash: out_planes rows must be contiguous")
-        p.OutP, p.planeO, p.sOPb, p.ldp = h_.data_ptr(), dest_p.plane, h_.stride(0), h_.stride(1)
-        if out is not None:
-            if tuple(hip._act32(out, "out").shape) != tuple(h_.shape):
-                raise ValueError("planes.attn_flash: out and out_planes must have one shape")
-            p.Out, p.sOb, p.ldo = out.data_ptr(), out.stride(0), out.stride(1)
-    elif out_planes and not idx and not cls:
-        op, _ = attn_out_args(p, B, N, C, q.device)
-    else:
-        if out is None:
-            out = torch.empty(B, N, C, dtype=torch.float32, device=q.device)
-        p.Out, p.sOb, p.ldo = hip._act32(out, "out").data_ptr(), out.stride(0), out.stride(1)
+        p.lse = hip._dev32(lse, "lse").data_ptr()
     S = 1 if key_splits == 1 else attn_key_splits(B, heads, N, L, d, setting=key_splits)
     name, nbytes = f"attn_flash_x3p_kernel<{d}>", 4.0 * B * heads * d * (2 * N + 2 * L)
     if idx:
@@ -697,4 +668,4 @@ def attn_flash(q, k, v, heads, scale, q_src=None, k_src=None, v_src=None, out=No
         name, nbytes = f"attn_flash_x3p_kernel<{d}, split {S}> + attn_flash_x3p_combine_kernel", nbytes + 8.0 * nws
     with _Timed(name, 4.0 * B * heads * N * L * d, nbytes):
         _check(lib.ief_attn_flash_f32(byref(p), _stream()), "ief_attn_flash_f32 (planes)")
-    return op if op is not None else out
+    return res

@@ -901,7 +901,7 @@ class UNet2DConditionModel(nn.Module):
         plan = self._plan
         return dict(x3p=bool(self.x3p), aug=bool(self.cfg.addition_embed), first_block_cross=cross,
                     native=all(m.is_native() for m in att),
-                    fused_cross=cross and att[1].dim_head in (40, 64, 80, 160) and int(ctx_len) <= 96 and hip.FLASH_F32 and hip.X3_FUSE_CROSS,
+                    fused_cross=cross and hip.cross_p2p_x3_ok(att[1].dim_head, ctx_len) and hip.FLASH_F32 and hip.X3_FUSE_CROSS,
                     ln_folded=bool(planes.LN_FOLD),
                     plan_on_first_self=plan is not None and plan.controls_first_self(self, int(latent_hw[0]) * int(latent_hw[1])))
 
