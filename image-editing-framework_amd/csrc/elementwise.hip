@@ -7,19 +7,28 @@
 // Same operation order as the reference's scheduler.step / ddim_reverse so fp32 results stay
 // within an ulp or two of the eager formula (/root/reference/p2p/model/sd_utils.py:74-76,
 // /root/reference/p2p/inversion/ddim.py:14-17).
+struct DdimCoef { float sb_f, sa_f, sa_t, sb_t, g; };
+__device__ __forceinline__ DdimCoef ddim_coef(const float* __restrict__ coef) {
+    const float a_f = coef[0], a_t = coef[1];
+    return {sqrtf(1.0f - a_f), sqrtf(a_f), sqrtf(a_t), sqrtf(1.0f - a_t), coef[2]};
+}
+// one element of the step, shared by the plain and the rectifying kernel: x' (returned) and the x0 prediction
+__device__ __forceinline__ float cfg_ddim_elem(const DdimCoef& c, const float* __restrict__ eu, const float* __restrict__ ec,
+                                               const float* __restrict__ x, float* __restrict__ x0o, long long i) {
+    float e = ec[i];
+    if (eu) { const float u = eu[i]; e = u + c.g * (e - u); }
+    const float x0 = (x[i] - c.sb_f * e) / c.sa_f;
+    if (x0o) x0o[i] = x0;
+    return c.sa_t * x0 + c.sb_t * e;
+}
+
 __global__ __launch_bounds__(256) void cfg_ddim_kernel(const float* __restrict__ eu, const float* __restrict__ ec,
                                                        const float* __restrict__ x, float* __restrict__ xo,
                                                        float* __restrict__ x0o, const float* __restrict__ coef,
                                                        long long n) {
-    const float a_f = coef[0], a_t = coef[1], g = coef[2];
-    const float sb_f = sqrtf(1.0f - a_f), sa_f = sqrtf(a_f), sa_t = sqrtf(a_t), sb_t = sqrtf(1.0f - a_t);
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-        float e = ec[i];
-        if (eu) { const float u = eu[i]; e = u + g * (e - u); }
-        const float x0 = (x[i] - sb_f * e) / sa_f;
-        if (x0o) x0o[i] = x0;
-        xo[i] = sa_t * x0 + sb_t * e;
-    }
+    const DdimCoef c = ddim_coef(coef);
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256)
+        xo[i] = cfg_ddim_elem(c, eu, ec, x, x0o, i);
 }
 
 extern "C" int ief_cfg_ddim_step_f32(const float* eps_u, const float* eps_c, const float* x, float* x_out,
@@ -30,6 +39,38 @@ extern "C" int ief_cfg_ddim_step_f32(const float* eps_u, const float* eps_c, con
     if (grid > 2048) grid = 2048;
     hipLaunchKernelGGL(cfg_ddim_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, eps_u, eps_c, x, x_out, x0_out,
                        coef, n);
+    IEF_LAUNCH_CHECK();
+    return IEF_OK;
+}
+
+// Direct Inversion (Ju et al.): the same step, and batch row 0 (the source branch, elements i < row_elems) is moved back onto the
+// stored inversion trajectory:  x'' = x' + (z - x'),  z = traj[clamp(step[0], 0, traj_rows - 1)][i], both operations rounded in fp32
+// (this file is built without fma contraction and without reassociation).  Rows >= 1 and x0_out are the plain step's, bit for bit.
+// The row index comes from device memory and is clamped as in select_step_kernel, so one captured graph serves every step.
+__global__ __launch_bounds__(256) void cfg_ddim_rect_kernel(const float* __restrict__ eu, const float* __restrict__ ec,
+                                                            const float* __restrict__ x, float* __restrict__ xo,
+                                                            float* __restrict__ x0o, const float* __restrict__ coef,
+                                                            long long n, long long row_elems, const float* __restrict__ traj,
+                                                            int traj_rows, const int* __restrict__ step) {
+    const DdimCoef c = ddim_coef(coef);
+    int row = step[0];
+    row = row < 0 ? 0 : (row >= traj_rows ? traj_rows - 1 : row);
+    const float* __restrict__ z = traj + (long long)row * row_elems;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+        const float xp = cfg_ddim_elem(c, eu, ec, x, x0o, i);
+        xo[i] = i < row_elems ? xp + (z[i] - xp) : xp;
+    }
+}
+
+extern "C" int ief_cfg_ddim_step_rect_f32(const float* eps_u, const float* eps_c, const float* x, float* x_out,
+                                          float* x0_out, const float* coef, long long n, long long row_elems,
+                                          const float* traj, int traj_rows, const int* step, void* stream) {
+    if (!eps_c || !x || !x_out || !coef || !traj || !step) return IEF_EINVAL;
+    if (n <= 0 || row_elems <= 0 || n % row_elems != 0 || traj_rows <= 0) return IEF_ESHAPE;
+    int grid = (int)((n + 255) / 256);
+    if (grid > 2048) grid = 2048;
+    hipLaunchKernelGGL(cfg_ddim_rect_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, eps_u, eps_c, x, x_out, x0_out,
+                       coef, n, row_elems, traj, traj_rows, step);
     IEF_LAUNCH_CHECK();
     return IEF_OK;
 }

@@ -9,6 +9,7 @@ overhead would exceed the GPU time.  Here the whole step is captured once:
     select_step(time-embedding row)  select_step(DDIM coefficients)     <- read a DEVICE step counter
     [P2P plan: select_step(gate coefficients), select_step(self-replace sources)]
     latents -> CFG batch copy -> UNet (fused attention control) -> fused CFG + DDIM update (in place)
+    [Direct Inversion: the same launch moves the source row (row 0) back onto the stored inversion trajectory]
     [P2P plan with a LocalBlend: the word-masked blend of the updated latents, in place]
     advance_step
 (on the f16x3 planes trunk the UNet takes the latents themselves and runs what both halves of the CFG batch share once: no copy;
@@ -90,17 +91,40 @@ def _check_finite(lat, unet):
         raise FloatingPointError(f"non-finite latents after the denoising loop (precision={mode}): {hint}")
 
 
+def check_source_trajectory(traj, *, mode, cfg, uncond_list, row_shape, num_steps):
+    """the argument checks of a Direct Inversion loop (host-side facts only; raises ValueError): `traj` is fp32 [S, C, h, w] with
+    row i = z*_{S-1-i}, the latent the SOURCE row must hold after edit step i"""
+    if mode != "denoise":
+        raise ValueError(f"source_trajectory: only a denoising loop rectifies its source row (mode={mode!r})")
+    if not cfg:
+        raise ValueError("source_trajectory: Direct Inversion rectifies the source row of a classifier-free-guidance edit; "
+                         "without guidance the cond-only inversion is already reproduced")
+    if uncond_list is not None:
+        raise ValueError("source_trajectory together with uncond_list: choose Direct Inversion or null-text embeddings, not both")
+    if not isinstance(traj, torch.Tensor) or traj.dtype != torch.float32:
+        raise ValueError("source_trajectory: expected one fp32 tensor [steps, C, h, w]")
+    if tuple(traj.shape[1:]) != tuple(row_shape) or traj.dim() != 1 + len(row_shape):
+        raise ValueError(f"source_trajectory: rows of shape {tuple(traj.shape[1:])} for latents of shape {tuple(row_shape)}")
+    if traj.shape[0] != num_steps:
+        raise ValueError(f"source_trajectory: {traj.shape[0]} rows for a schedule of {num_steps} steps")
+
+
 class FusedDenoiser:
     def __init__(self, model, context: torch.Tensor, num_latents: int, latent_hw, guidance_scale: Optional[float],
                  mode: str = "denoise", uncond_list: Optional[List[torch.Tensor]] = None, use_graph: bool = True,
-                 added_cond_kwargs=None):
+                 added_cond_kwargs=None, source_trajectory: Optional[torch.Tensor] = None):
         """context: [2*Bp,77,C] (uncond, cond) for mode 'denoise' with CFG, [Bp,77,C] for 'invert' / no-CFG.
         added_cond_kwargs: SDXL's {"text_embeds" [B, 1280], "time_ids" [B, 6]} (one row per UNet batch row); they are
-        constant over the steps, so they fold into the per-step time-embedding rows (then one row PER BATCH ROW)."""
+        constant over the steps, so they fold into the per-step time-embedding rows (then one row PER BATCH ROW).
+        source_trajectory: Direct Inversion -- fp32 [S, C, h, w], row i = z*_{S-1-i} of the DDIM inversion; after step i batch row 0
+        (the source branch) is x' + (z - x') in the launch of the CFG + DDIM update, every other row is x'."""
         self.model, self.unet, self.sched = model, model.unet, model.scheduler
         dev = self.unet.device
         self.mode = mode
         self.cfg = guidance_scale is not None
+        if source_trajectory is not None:
+            check_source_trajectory(source_trajectory, mode=mode, cfg=self.cfg, uncond_list=uncond_list,
+                                    row_shape=(self.unet.config.in_channels, *latent_hw), num_steps=len(self.sched.timesteps))
         self.Bp = num_latents
         self.B = 2 * num_latents if self.cfg else num_latents
         if context.shape[0] != self.B:
@@ -120,6 +144,8 @@ class FusedDenoiser:
         self.step = torch.zeros(1, dtype=torch.int32, device=dev)
         self.coef_cur = torch.zeros(4, dtype=torch.float32, device=dev)
         self.coef_table = self.temb_table = self.temb_cur = self.ctx = self.ctx_table = None
+        # the graph READS this buffer (row = the device step counter): `rebind` copies the next image's rows into it
+        self.traj = None if source_trajectory is None else source_trajectory.to(dev).contiguous().clone()
         self._fill(context, guidance_scale, uncond_list, added_cond_kwargs)
         self.use_graph = use_graph
         self.graph = None
@@ -178,15 +204,22 @@ class FusedDenoiser:
         return cfg_shared_prefix_reason(mode=self.mode, cfg=self.cfg, enabled=CFG_SHARED_PREFIX and type(self)._step_body is FusedDenoiser._step_body,
                                         **facts(tuple(self.lat.shape[-2:]), ctx_len))
 
-    def _key(self, context, uncond_list):
+    def _key(self, context, uncond_list, source_trajectory=None):
         plan = self.unet._plan
         return (id(self.unet), self.mode, self.Bp, tuple(self.lat.shape[-2:]), self.cfg, tuple(context.shape),
                 None if uncond_list is None else len(uncond_list), len(self.sched.timesteps),
                 None if plan is None else plan.signature(self.unet), self._shared_reason(context.shape[1]) is None,
-                getattr(self.unet, "attn_key_splits", 1))
+                source_trajectory is not None, getattr(self.unet, "attn_key_splits", 1))
 
-    def rebind(self, context, guidance_scale, uncond_list, added_cond_kwargs=None):
-        """point a captured loop at the next image: new tables, new cross-attention K/V, the new controller's plan"""
+    def rebind(self, context, guidance_scale, uncond_list, added_cond_kwargs=None, source_trajectory=None):
+        """point a captured loop at the next image: new tables, new cross-attention K/V, the new controller's plan, the next
+        image's inversion trajectory"""
+        if (source_trajectory is None) != (self.traj is None):
+            raise ValueError("rebind: a loop captured with a source trajectory serves only jobs that bring one, and the reverse")
+        if source_trajectory is not None:
+            check_source_trajectory(source_trajectory, mode=self.mode, cfg=self.cfg, uncond_list=uncond_list,
+                                    row_shape=tuple(self.lat.shape[1:]), num_steps=len(self.sched.timesteps))
+            self.traj.copy_(source_trajectory)
         self._fill(context, guidance_scale, uncond_list, added_cond_kwargs)
         if self.ctx_table is None:          # K/V of the fixed context live in tensors the graph reads: refresh in place, by the
             # same kernels the forward used (the model's contraction mode: "x3" and "f32" differ in the last bits, and an
@@ -216,7 +249,8 @@ class FusedDenoiser:
                 self.lat_in[self.Bp:].copy_(self.lat)
             eps = self.unet(self.lat_in, encoder_hidden_states=self.ctx, temb_row=self.temb_cur)["sample"]
         if self.cfg:
-            hip.cfg_ddim_step(eps[: self.Bp], eps[self.Bp:], self.lat, self.coef_cur, out=self.lat)
+            hip.cfg_ddim_step(eps[: self.Bp], eps[self.Bp:], self.lat, self.coef_cur, out=self.lat,
+                              rect=None if self.traj is None else (self.traj, self.step))
         else:
             hip.cfg_ddim_step(None, eps, self.lat, self.coef_cur, out=self.lat)
         if self.plan is not None and self.cfg:
@@ -368,7 +402,10 @@ class CfgSplitDenoiser(FusedDenoiser):
     (`p2p.model.register.register_attention_control`); its counters advance on both."""
 
     def __init__(self, model, context, num_latents, latent_hw, guidance_scale: float, group=None, uncond_list=None,
-                 use_graph: bool = True):
+                 use_graph: bool = True, source_trajectory=None):
+        if source_trajectory is not None:
+            raise ValueError("CFG split: Direct Inversion (source_trajectory) is not built for the two-GPU split; run the edit "
+                             "on one GPU")
         import torch.distributed as dist
         if dist.get_world_size(group) != 2:
             raise ValueError("a CFG split runs on a group of exactly two ranks")
@@ -468,26 +505,27 @@ class CfgSplitDenoiser(FusedDenoiser):
 
 
 def acquire(model, context, num_latents, latent_hw, guidance_scale, mode="denoise", uncond_list=None,
-            use_graph=True, added_cond_kwargs=None) -> FusedDenoiser:
+            use_graph=True, added_cond_kwargs=None, source_trajectory=None) -> FusedDenoiser:
     """a FusedDenoiser for this job: a pooled one with a captured graph of the same shape / plan signature, re-pointed
-    at the new context, tables and controller — or a new one"""
+    at the new context, tables and controller — or a new one.  source_trajectory: Direct Inversion (`FusedDenoiser`); loops
+    with and without one never share a pool entry"""
     if REUSE_GRAPHS and use_graph:
         probe = FusedDenoiser.__new__(FusedDenoiser)
         probe.unet, probe.sched, probe.mode = model.unet, model.scheduler, mode
         probe.cfg, probe.Bp = guidance_scale is not None, num_latents
         probe.lat = torch.empty(0, 0, *latent_hw)
-        key = probe._key(context, uncond_list)
+        key = probe._key(context, uncond_list, source_trajectory)
         free = _POOL.get(key)
         if free:
             loop = free.pop()
-            loop.rebind(context, guidance_scale, uncond_list, added_cond_kwargs)
+            loop.rebind(context, guidance_scale, uncond_list, added_cond_kwargs, source_trajectory)
             return loop
         loop = FusedDenoiser(model, context, num_latents, latent_hw, guidance_scale, mode, uncond_list, use_graph,
-                             added_cond_kwargs)
+                             added_cond_kwargs, source_trajectory)
         loop._pool_key = key
         return loop
     return FusedDenoiser(model, context, num_latents, latent_hw, guidance_scale, mode, uncond_list, use_graph,
-                         added_cond_kwargs)
+                         added_cond_kwargs, source_trajectory)
 
 
 def drop_pool():

@@ -1708,14 +1708,28 @@ def attn_apply(probs, v, heads, out=None):
 
 
 # ------------------------------------------------------------------------------- sampler
-def cfg_ddim_step(eps_u, eps_c, x, coef, out=None, x0_out=None):
-    """x' from (eps_u, eps_c, x) with coef = device fp32 [a_from, a_to, guidance]; eps_u None => no CFG."""
+def cfg_ddim_step(eps_u, eps_c, x, coef, out=None, x0_out=None, rect=None):
+    """x' from (eps_u, eps_c, x) with coef = device fp32 [a_from, a_to, guidance]; eps_u None => no CFG.
+    rect = (traj, step): Direct Inversion in the same launch -- batch row 0 of x [Bp, ...] becomes x'[0] + (z - x'[0]) with
+    z = traj[clamp(step[0], 0, S - 1)]; traj device fp32 [S, *x.shape[1:]], step device int32 [1] (read by the kernel)."""
     lib = load()
     _dev32(eps_c, "eps_c")
     _dev32(x, "x")
     _dev32(coef, "coef")
     if out is None:
         out = torch.empty_like(x)
+    if rect is not None:
+        traj, step = rect
+        _dev32(traj, "rect trajectory")
+        if x.dim() < 2 or traj.dim() != x.dim() or traj.shape[0] < 1 or traj.shape[1:] != x.shape[1:]:
+            raise ValueError(f"cfg_ddim_step: the trajectory must be [steps, {', '.join(map(str, x.shape[1:]))}] (x without its batch "
+                             f"dimension), got {tuple(traj.shape)}")
+        if _devi32(step, "rect step") is None or step.numel() != 1:
+            raise TypeError("rect step: expected a device int32 tensor of one element")
+        _check(lib.ief_cfg_ddim_step_rect_f32(_ptr(eps_u), eps_c.data_ptr(), x.data_ptr(), out.data_ptr(), _ptr(x0_out),
+                                              coef.data_ptr(), x.numel(), x[0].numel(), traj.data_ptr(), traj.shape[0],
+                                              step.data_ptr(), _stream()), "ief_cfg_ddim_step_rect_f32")
+        return out
     _check(lib.ief_cfg_ddim_step_f32(_ptr(eps_u), eps_c.data_ptr(), x.data_ptr(), out.data_ptr(), _ptr(x0_out),
                                      coef.data_ptr(), x.numel(), _stream()), "ief_cfg_ddim_step_f32")
     return out

@@ -1,6 +1,7 @@
 """Invert a real image, then edit it with MasaCtrl — CLI of `/root/reference/masactrl/edit_real.py` (same flags and
 defaults: `--inversion_type` "null-text" (:27), `STEP = 4`, `LAYPER = 10`; outputs `./exp/source.png`,
-`./exp/inversion.png`, `./exp/edit.png`)."""
+`./exp/inversion.png`, `./exp/edit.png`).  `--inversion_type direct` (not a reference value): Direct Inversion, the DDIM inversion
+whose trajectory the edit's source row is moved back onto after every step (`ief_amd.p2p.inversion.direct`)."""
 import argparse
 import os
 import sys
@@ -17,6 +18,7 @@ from ief_amd.masactrl.model.attention_control import (MutualSelfAttentionControl
 from ief_amd.masactrl.model.register import regiter_attention_editor_diffusers, unregister_attention_control  # noqa: E402
 from ief_amd.masactrl.model.sd_utils import MasaCtrl, MasaCtrl_NTI, MasaCtrl_XL, MasaCtrl_XL_NTI  # noqa: E402
 from ief_amd.p2p.inversion.ddim import ddim_inversion, ddim_inversion_xl  # noqa: E402
+from ief_amd.p2p.inversion.direct import DirectInversion, DirectInversion_XL  # noqa: E402
 from ief_amd.p2p.inversion.nti import NTI, NTI_XL_5e2 as NTI_XL  # noqa: E402  (this folder's copy: lr 5e-2)
 from ief_amd.p2p.utils.save_image import save_img  # noqa: E402
 
@@ -59,6 +61,8 @@ def edit_one(pipe, editor, invertor, image, source_prompt, target_prompt, invers
         # before the editor is registered, as in the reference (:143-147)
         extra["uncond_embeddings_list"] = invertor.null_optimization(pipe, latents, context, NUM_INNER_STEPS,
                                                                      EARLY_STOP_EPSILON, guidance_scale)
+    elif inversion_type == "direct":
+        extra["source_trajectory"] = invertor.trajectory(latents)
     elif inversion_type != "ddim":
         raise ValueError("Please choose right inversion type")
     init_latent = torch.cat([latents[-1], latents[-1]])
@@ -88,6 +92,8 @@ def pick(pipe, inversion_type, num_inference_steps=50):
         return (ddim_inversion_xl() if xl else ddim_inversion()), (MasaCtrl_XL if xl else MasaCtrl)(pipe, num_inference_steps)
     if inversion_type == "null-text":
         return (NTI_XL() if xl else NTI()), (MasaCtrl_XL_NTI if xl else MasaCtrl_NTI)(pipe, num_inference_steps)
+    if inversion_type == "direct":
+        return (DirectInversion_XL() if xl else DirectInversion()), (MasaCtrl_XL if xl else MasaCtrl)(pipe, num_inference_steps)
     raise ValueError("Please choose right inversion type")
 
 

@@ -26,7 +26,10 @@ class MasaCtrl:
     @torch.no_grad()
     def __call__(self, prompt, batch_size=1, height=512, width=512, num_inference_steps=50, guidance_scale=7.5,
                  latents=None, unconditioning=None, neg_prompt=None, ref_intermediate_latents=None,
-                 return_intermediates=False, return_latents=False, uncond_embeddings_list=None, **kwds):
+                 return_intermediates=False, return_latents=False, uncond_embeddings_list=None, source_trajectory=None, **kwds):
+        """source_trajectory (not a reference argument): Direct Inversion -- fp32 [S, C, h, w], row i = z*_{S-1-i} of the source
+        image's DDIM inversion (`p2p.inversion.direct.DirectInversion.trajectory`); after every step the source row (prompt 0) is
+        moved back onto it, in the launch of the CFG + DDIM update (`denoise.FusedDenoiser`)."""
         model = self.model
         dev = model.unet.device
         if isinstance(prompt, list):
@@ -50,6 +53,9 @@ class MasaCtrl:
         # (/root/reference/masactrl/model/sd_utils.py:231-245); the same loop serves both classes here
         uncond_list = uncond_embeddings_list if uncond_embeddings_list is not None else (
             unconditioning if isinstance(unconditioning, list) else None)
+        if source_trajectory is not None and uncond_list is not None:
+            raise ValueError("source_trajectory together with uncond_embeddings_list: choose Direct Inversion or null-text "
+                             "embeddings, not both")
         if guidance_scale > 1.0:
             uc = tok([neg_prompt or ""] * batch_size, padding="max_length", max_length=tok.model_max_length,
                      return_tensors="pt")
@@ -65,7 +71,7 @@ class MasaCtrl:
         # would replay the kernels of the capture pass without calling it)
         native = all(m.is_native() for m in model.unet.attention_modules())
         loop = acquire(model, context, batch_size, (height // 8, width // 8), g, uncond_list=uncond_list,
-                       added_cond_kwargs=added_cond_kwargs, use_graph=native)
+                       added_cond_kwargs=added_cond_kwargs, use_graph=native, source_trajectory=source_trajectory)
         try:
             latents = loop.run(latents)
         finally:

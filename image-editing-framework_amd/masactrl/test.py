@@ -1,6 +1,7 @@
 """PIE-Bench driver for MasaCtrl — `/root/reference/masactrl/test.py` (per image: invert, then the mutual
 self-attention sampler from `cat([x_T, x_T])`), sharded over the GPUs of one node like `p2p/test.py`: rank r of W takes
-items i with i % W == r, no collective on the data path.  `--synthetic N` replaces the (unavailable) PIE download."""
+items i with i % W == r, no collective on the data path.  `--synthetic N` replaces the (unavailable) PIE download.
+`--inversion_type`: `ddim`, `null-text`, or `direct` (not a reference value; Direct Inversion, `ief_amd.p2p.inversion.direct`)."""
 import argparse
 import json
 import os
@@ -26,7 +27,7 @@ from ief_amd.p2p.utils.save_image import PngWriter  # noqa: E402
 CATEGORIES = [0, 1, 2, 3, 4, 6, 7, 8, 9]
 
 
-def main(argv=None):
+def parse_args(argv=None):
     ap = argparse.ArgumentParser("PIE-Bench MasaCtrl")
     ap.add_argument("--sd_version", type=str, default="1.5")
     ap.add_argument("--dataset_path", type=str, default="./PIE")
@@ -34,7 +35,11 @@ def main(argv=None):
     ap.add_argument("--inversion_type", type=str, default="ddim")
     ap.add_argument("--synthetic", type=int, default=0, help="use N generated images instead of ./PIE")
     ap.add_argument("--no_save", action="store_true")
-    args = ap.parse_args(argv)
+    return ap.parse_args(argv)
+
+
+def main(argv=None):
+    args = parse_args(argv)
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     device = torch.device(f"cuda:{local % max(1, torch.cuda.device_count())}")   # ranks beyond the device count share GPUs (gloo rehearsals)

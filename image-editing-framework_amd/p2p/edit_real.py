@@ -2,7 +2,8 @@
 
 Same flags and defaults (`--inversion_type` defaults to "null-text" as in the reference, :26), same outputs:
 `./exp/source.png`, `./exp/inversion.png`, `./exp/edit.png`; plus `--blend_source_words` / `--blend_target_words` /
-`--blend_threshold` for `LocalBlend`.
+`--blend_threshold` for `LocalBlend`, and `--inversion_type direct` (not a reference value): Direct Inversion, the DDIM inversion
+whose trajectory the edit's source row is moved back onto after every step (`ief_amd.p2p.inversion.direct`).
 """
 import argparse
 import os
@@ -13,6 +14,7 @@ from PIL import Image
 from _bootstrap import load_pipe, seed_everything
 
 from ief_amd.p2p.inversion.ddim import ddim_inversion, ddim_inversion_xl
+from ief_amd.p2p.inversion.direct import DirectInversion, DirectInversion_XL
 from ief_amd.p2p.inversion.nti import NTI, NTI_XL
 from ief_amd.p2p.model.attention_control import AttentionRefine, AttentionReplace
 from ief_amd.p2p.model.ptp_utils import local_blend_from_words
@@ -72,6 +74,8 @@ def edit_one(pipe, editor, invertor, image, source_prompt, target_prompt, invers
     if inversion_type == "null-text":
         extra["uncond_embeddings_list"] = invertor.null_optimization(pipe, latents, context, num_inner_steps,
                                                                      early_stop_epsilon, guidance_scale)
+    elif inversion_type == "direct":
+        extra["source_trajectory"] = invertor.trajectory(latents)
     elif inversion_type != "ddim":
         raise ValueError("Please choose right inversion type")
     return edit_latent(pipe, editor, latents[-1], source_prompt, target_prompt, edit_type, device, extra,
@@ -94,6 +98,9 @@ def main(argv=None):
     elif args.inversion_type == "null-text":
         editor = (P2P_XL_NTI if xl else P2P_NTI)(model=pipe, num_inference_steps=50)
         invertor = NTI_XL() if xl else NTI()
+    elif args.inversion_type == "direct":
+        editor = (P2P_XL if xl else P2P)(model=pipe, num_inference_steps=50)
+        invertor = DirectInversion_XL() if xl else DirectInversion()
     else:
         raise ValueError("Please choose right inversion type")
     size = pipe.unet.config.sample_size * pipe.vae_scale_factor

@@ -24,7 +24,7 @@ import torch
 from tqdm import tqdm
 
 from ... import hip
-from ...denoise import acquire, run_interleaved
+from ...denoise import acquire, check_source_trajectory, run_interleaved
 from .register import register_attention_control, unregister_attention_control
 
 
@@ -85,11 +85,19 @@ class P2P:
                               guidance_scale: float = 7.5, generator: Optional[torch.Generator] = None,
                               latent: Optional[torch.FloatTensor] = None, low_resource: bool = False,
                               uncond_embeddings_list=None, height: Optional[int] = None, width: Optional[int] = None,
-                              return_latents: bool = False, cfg_split_group=None):
+                              return_latents: bool = False, cfg_split_group=None, source_trajectory=None):
         """cfg_split_group (not a reference argument): a torch.distributed group of TWO ranks that run this ONE edit
         together — rank 0 the unconditional rows of the CFG batch, rank 1 the conditional rows, one eps exchange per
-        step (`denoise.CfgSplitDenoiser`); both ranks return the same latents / images."""
+        step (`denoise.CfgSplitDenoiser`); both ranks return the same latents / images.
+        source_trajectory (not a reference argument): Direct Inversion -- fp32 [S, C, h, w], row i = z*_{S-1-i} of the source
+        image's DDIM inversion (`inversion.direct.DirectInversion.trajectory`); after every step the source row (prompt 0) is
+        moved back onto it, in the launch of the CFG + DDIM update."""
+        if source_trajectory is not None and uncond_embeddings_list is not None:
+            raise ValueError("source_trajectory together with uncond_embeddings_list: choose Direct Inversion or null-text "
+                             "embeddings, not both")
         if cfg_split_group is not None:
+            if source_trajectory is not None:
+                raise ValueError("CFG split: Direct Inversion (source_trajectory) is not built for the two-GPU split")
             return self._text2image_cfg_split(model, prompt, controller, num_inference_steps, guidance_scale, latent,
                                               uncond_embeddings_list, height, width, return_latents, cfg_split_group)
         if controller is not None:
@@ -103,17 +111,26 @@ class P2P:
         context = torch.cat([uncond_embeddings, text_embeddings])
         if _fusable(model, controller, low_resource):
             loop = acquire(model, context, batch_size, (height // 8, width // 8), guidance_scale,
-                                 uncond_list=uncond_embeddings_list, added_cond_kwargs=added_cond_kwargs)
+                                 uncond_list=uncond_embeddings_list, added_cond_kwargs=added_cond_kwargs,
+                                 source_trajectory=source_trajectory)
             try:
                 latents = loop.run(latents)
             finally:
                 loop.release()
         else:
+            rect = None
+            if source_trajectory is not None:
+                check_source_trajectory(source_trajectory, mode="denoise", cfg=True, uncond_list=None,
+                                        row_shape=tuple(latents.shape[1:]), num_steps=len(model.scheduler.timesteps))
+                step = torch.zeros(1, dtype=torch.int32, device=model.device)
+                rect = (source_trajectory.to(model.device).contiguous(), step)
             for i, t in enumerate(tqdm(model.scheduler.timesteps, desc="Now doing P2P editing")):
                 if uncond_embeddings_list is not None:
                     context = torch.cat([uncond_embeddings_list[i].expand(*text_embeddings.shape), text_embeddings])
+                if rect is not None:
+                    step.fill_(i)           # the host's step index, where the captured loop reads its device counter
                 latents = self.diffusion_step(model, controller, latents, context, t, guidance_scale, low_resource,
-                                              added_cond_kwargs=added_cond_kwargs)
+                                              added_cond_kwargs=added_cond_kwargs, rect=rect)
         if return_latents:
             return latents, latent
         image = self.latent2image(model.vae, latents)
@@ -164,7 +181,8 @@ class P2P:
                   height: Optional[int] = None, width: Optional[int] = None):
         """Several independent edits IN FLIGHT on one GPU (a throughput schedule the reference does not have: its
         drivers call `text2image_ldm_stable` once per image).  jobs: [(prompts, controller, latent x_T [1,4,h,w])] or
-        [(prompts, controller, x_T, uncond_embeddings_list)] (null-text embeddings, as `P2P_NTI`);
+        [(prompts, controller, x_T, uncond_embeddings_list)] (null-text embeddings, as `P2P_NTI`) or
+        [(prompts, controller, x_T, None, source_trajectory)] (Direct Inversion, as `text2image_ldm_stable`);
         every controller must be one of the lowered classes.  Each job's loop is captured while its controller is
         registered, then all loops are stepped in turn on their own streams (`denoise.run_interleaved`).  Returns
         [(images uint8 [len(prompts),H,W,3], x_T)] — the same values as one `text2image_ldm_stable` call per job."""
@@ -176,6 +194,9 @@ class P2P:
             for job in jobs:
                 prompt, controller, latent = job[:3]
                 uncond_list = job[3] if len(job) > 3 else None
+                source_trajectory = job[4] if len(job) > 4 else None
+                if source_trajectory is not None and uncond_list is not None:
+                    raise ValueError("edit_many: a job brings a source trajectory or null-text embeddings, not both")
                 register_attention_control(model, controller)
                 if not _fusable(model, controller, False):
                     raise RuntimeError("edit_many: only controllers lowered to a device plan can run concurrently")
@@ -184,7 +205,7 @@ class P2P:
                 latent, latents = self.init_latent(latent, model, height, width, None, len(prompt))
                 loop = acquire(model, torch.cat([uncond_embeddings, text_embeddings]), len(prompt),
                                      (height // 8, width // 8), guidance_scale, uncond_list=uncond_list,
-                                     added_cond_kwargs=added_cond_kwargs)
+                                     added_cond_kwargs=added_cond_kwargs, source_trajectory=source_trajectory)
                 loop.start(latents)
                 loops.append(loop)
                 firsts.append(latent)
@@ -197,8 +218,10 @@ class P2P:
                 loop.release()
 
     def diffusion_step(self, model, controller, latents, context, t, guidance_scale, low_resource=False,
-                       added_cond_kwargs=None):
-        """one eager step (`sd_utils.py:67-79`, XL: :175-186); CFG + DDIM update fused in one kernel."""
+                       added_cond_kwargs=None, rect=None):
+        """one eager step (`sd_utils.py:67-79`, XL: :175-186); CFG + DDIM update fused in one kernel.  rect = (trajectory, step):
+        Direct Inversion's move of the source row in that kernel (`hip.cfg_ddim_step`), in front of the controller's callback as
+        in the captured step."""
         latents = latents.float().contiguous()
         if low_resource:
             bp = latents.shape[0]
@@ -211,7 +234,7 @@ class P2P:
             eps_u, eps_c = eps.chunk(2)
         a_t, a_p = model.scheduler.step_coeffs(int(t))
         coef = torch.tensor([a_t, a_p, float(guidance_scale)], dtype=torch.float32, device=latents.device)
-        latents = hip.cfg_ddim_step(eps_u.contiguous(), eps_c.contiguous(), latents, coef)
+        latents = hip.cfg_ddim_step(eps_u.contiguous(), eps_c.contiguous(), latents, coef, rect=rect)
         if controller is not None:
             latents = controller.step_callback(latents)
         return latents

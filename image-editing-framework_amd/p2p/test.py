@@ -20,6 +20,8 @@ each other's dispatch gaps.  Both change the schedule, not the results.
 `--nti_batch K` (with `--inversion_type null-text`) runs the null-text optimisations of a shard in groups of K through ONE
 UNet batch (`NTI.null_optimization_batched`: one optimiser and three graphs for the whole run, every image with its own
 early stop) instead of `--in_flight` chains at batch 1; `--in_flight` keeps governing the edits.  Not for SDXL pipelines.
+`--inversion_type direct` (not a reference value): Direct Inversion -- the DDIM inversion, and every edit moves its source row back
+onto the stored trajectory after each step (`ief_amd.p2p.inversion.direct`); `--invert_batch` / `--in_flight` work as for `ddim`.
 """
 import argparse
 import json
@@ -35,6 +37,7 @@ from edit_real import edit_latent, edit_one
 from ief_amd.p2p.model.attention_control import AttentionRefine, AttentionReplace
 from ief_amd.p2p.dataset.pie import PIE, SyntheticPIE
 from ief_amd.p2p.inversion.ddim import ddim_inversion, ddim_inversion_xl
+from ief_amd.p2p.inversion.direct import DirectInversion, DirectInversion_XL
 from ief_amd.p2p.inversion.nti import NTI, NTI_XL
 from ief_amd.p2p.model.sd_utils import P2P, P2P_NTI, P2P_XL, P2P_XL_NTI
 from ief_amd.p2p.utils.save_image import PngWriter
@@ -60,6 +63,7 @@ def run_items(pipe, editor, invertor, items, size, device, inversion_type="ddim"
     Also what `bench.py` times for its images/sec figures."""
     save = save or (lambda *a: None)
     nti = inversion_type == "null-text"
+    direct = inversion_type == "direct"
     bs = max(1, invert_batch)
     E = max(1, in_flight)
     nb = max(1, nti_batch) if nti else 1
@@ -89,6 +93,8 @@ def run_items(pipe, editor, invertor, items, size, device, inversion_type="ddim"
                         unc, cnd = context.chunk(2)
                         ctxs.append(torch.cat([unc[j:j + 1], cnd[j:j + 1]]))
             x_T = [t[-1] for t in traj]
+            # Direct Inversion: per image, the rows its edit's source branch is moved back onto
+            rows = [invertor.trajectory(t) if direct else None for t in traj]
             # null-text optimisation: E images in flight
             uncond = [None] * len(chunk)
             if nti and nb > 1:
@@ -105,7 +111,7 @@ def run_items(pipe, editor, invertor, items, size, device, inversion_type="ddim"
                 if len(part) == 1:
                     j = part[0]
                     _, src, tgt = chunk[j]
-                    extra = {"uncond_embeddings_list": uncond[j]} if nti else None
+                    extra = {"uncond_embeddings_list": uncond[j]} if nti else ({"source_trajectory": rows[j]} if direct else None)
                     results = [edit_latent(pipe, editor, x_T[j], [src], [tgt], edit_type_of(src, tgt), device, extra)]
                 else:
                     jobs, ctrls = [], []
@@ -115,7 +121,7 @@ def run_items(pipe, editor, invertor, items, size, device, inversion_type="ddim"
                         ctrl = cls(prompts=[src, tgt], tokenizer=pipe.tokenizer, num_steps=50, cross_replace_steps=0.8,
                                    self_replace_steps=0.6, device=device)
                         ctrls.append(ctrl)
-                        jobs.append(([src, tgt], ctrl, x_T[j]) + ((uncond[j],) if nti else ()))
+                        jobs.append(([src, tgt], ctrl, x_T[j]) + ((uncond[j],) if nti else ((None, rows[j]) if direct else ())))
                     results = [im for im, _ in editor.edit_many(pipe, jobs, num_inference_steps=50, guidance_scale=7.5)]
                     for ctrl in ctrls:
                         ctrl.reset()
@@ -151,6 +157,8 @@ def parse_args(argv=None):
     args = ap.parse_args(argv)
     if args.nti_batch < 1:
         ap.error("--nti_batch must be >= 1")
+    if args.nti_batch > 1 and args.inversion_type == "direct":
+        ap.error("--nti_batch groups null-text optimisations; --inversion_type direct runs none (use --invert_batch / --in_flight)")
     if args.nti_batch > 1 and args.sd_version in XL_VERSIONS:
         ap.error("--nti_batch: the SDXL null-text optimiser restarts per timestep with per-image added conditions and is not "
                  "batched; use --in_flight")
@@ -176,6 +184,9 @@ def main(argv=None):
     elif args.inversion_type == "null-text":
         editor = (P2P_XL_NTI if xl else P2P_NTI)(model=pipe, num_inference_steps=50)
         invertor = NTI_XL() if xl else NTI()
+    elif args.inversion_type == "direct":
+        editor = (P2P_XL if xl else P2P)(model=pipe, num_inference_steps=50)
+        invertor = DirectInversion_XL() if xl else DirectInversion()
     else:
         raise ValueError("Please choose right inversion type")
     size = pipe.unet.config.sample_size * pipe.vae_scale_factor

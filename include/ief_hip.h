@@ -198,6 +198,15 @@ int ief_attn_apply_f16(const IefAttnParams* p, const ief_half* probs, void* stre
  */
 int ief_cfg_ddim_step_f32(const float* eps_u, const float* eps_c, const float* x, float* x_out,
                           float* x0_out, const float* coef, long long n, void* stream);
+/* Direct Inversion (Ju et al., "Direct Inversion: Boosting Diffusion-based Editing with 3 Lines of Code"): the same step in the
+ * same launch, and batch row 0 (elements i < row_elems, the source branch of a two-branch edit) is moved back onto the stored
+ * inversion trajectory:  x_out = x' + (z - x'),  z = traj[min(max(step[0], 0), traj_rows - 1)][i], both operations rounded in fp32.
+ * Rows >= 1 of x_out and all of x0_out (the un-rectified x0 prediction) equal ief_cfg_ddim_step_f32's bit for bit.
+ * traj: DEVICE fp32 [traj_rows][row_elems]; step: DEVICE int32 [1], read by the kernel and clamped as ief_select_step clamps it.
+ * IEF_EINVAL: a null eps_c / x / x_out / coef / traj / step; IEF_ESHAPE: n <= 0, row_elems <= 0, n % row_elems != 0, traj_rows <= 0. */
+int ief_cfg_ddim_step_rect_f32(const float* eps_u, const float* eps_c, const float* x, float* x_out, float* x0_out,
+                               const float* coef, long long n, long long row_elems,
+                               const float* traj, int traj_rows, const int* step, void* stream);
 /* sinusoidal timestep embedding, flip_sin_to_cos, shift 0: out fp16 [B][dim] = [cos | sin] */
 int ief_timestep_embedding_f16(const float* t, ief_half* out, int B, int dim, void* stream);
 /* out = a + b elementwise on fp16 (residual add when a hook owns Attention.forward) */
