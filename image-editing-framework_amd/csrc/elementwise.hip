@@ -75,6 +75,88 @@ extern "C" int ief_cfg_ddim_step_rect_f32(const float* eps_u, const float* eps_c
     return IEF_OK;
 }
 
+// Edit-friendly DDPM inversion (Huberman-Spiegelglas et al., "An Edit Friendly DDPM Noise Space"): the eta = 1 update
+//   eps = eps_u + g (eps_c - eps_u);  x0 = (x - sqrt(1-a_f) eps) / sqrt(a_f);  mu = sqrt(a_t) x0 + dir eps;  x' = mu + sigma z
+// with sigma and dir = sqrt(1 - a_t - sigma^2) handed in (the host forms them in fp64), and its inverse z = (x_prev - mu) / sigma.
+// Both kernels take mu from ddpm_mu_elem, so the step undoes the extraction on the same eps up to the roundings of z itself.  With
+// sigma = 0 and dir = sqrtf(1 - a_t) mu is cfg_ddim_elem's x', operation for operation.
+struct DdpmCoef { float sb_f, sa_f, sa_t, sigma, dir; };
+__device__ __forceinline__ DdpmCoef ddpm_coef(const float* __restrict__ coef) {
+    const float a_f = coef[0], a_t = coef[1];
+    return {sqrtf(1.0f - a_f), sqrtf(a_f), sqrtf(a_t), coef[2], coef[3]};
+}
+__device__ __forceinline__ float ddpm_mu_elem(const DdpmCoef& c, float g, const float* __restrict__ eu, const float* __restrict__ ec,
+                                              const float* __restrict__ x, float* __restrict__ x0o, long long i) {
+    float e = ec[i];
+    if (eu) { const float u = eu[i]; e = u + g * (e - u); }
+    const float x0 = (x[i] - c.sb_f * e) / c.sa_f;
+    if (x0o) x0o[i] = x0;
+    return c.sa_t * x0 + c.dir * e;
+}
+// row of element i; launches of the sampler stay far below 2^32 elements, where one 32-bit division does
+__device__ __forceinline__ long long ddpm_row_of(long long i, long long row_elems, bool small) {
+    return small ? (long long)((unsigned)i / (unsigned)row_elems) : i / row_elems;
+}
+
+// every batch row reads the SAME noise row (chosen by the device step counter, clamped as in select_step_kernel) and its own scale
+__global__ __launch_bounds__(256) void cfg_ddpm_kernel(const float* __restrict__ eu, const float* __restrict__ ec,
+                                                       const float* __restrict__ x, float* __restrict__ xo,
+                                                       float* __restrict__ x0o, const float* __restrict__ coef,
+                                                       const float* __restrict__ g_rows, long long n, long long row_elems,
+                                                       const float* __restrict__ noise, int noise_rows,
+                                                       const int* __restrict__ step) {
+    const DdpmCoef c = ddpm_coef(coef);
+    int row = step[0];
+    row = row < 0 ? 0 : (row >= noise_rows ? noise_rows - 1 : row);
+    const float* __restrict__ z = noise + (long long)row * row_elems;
+    const bool small = n <= 0xffffffffll;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+        const long long b = ddpm_row_of(i, row_elems, small);
+        const float mu = ddpm_mu_elem(c, eu ? g_rows[b] : 1.0f, eu, ec, x, x0o, i);
+        xo[i] = c.sigma == 0.0f ? mu : mu + c.sigma * z[i - b * row_elems];
+    }
+}
+
+extern "C" int ief_cfg_ddpm_step_f32(const float* eps_u, const float* eps_c, const float* x, float* x_out, float* x0_out,
+                                     const float* coef, const float* g_rows, long long n, long long row_elems,
+                                     const float* noise, int noise_rows, const int* step, void* stream) {
+    if (!eps_c || !x || !x_out || !coef || !noise || !step || (eps_u && !g_rows)) return IEF_EINVAL;
+    if (n <= 0 || row_elems <= 0 || n % row_elems != 0 || noise_rows <= 0) return IEF_ESHAPE;
+    int grid = (int)((n + 255) / 256);
+    if (grid > 2048) grid = 2048;
+    hipLaunchKernelGGL(cfg_ddpm_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, eps_u, eps_c, x, x_out, x0_out, coef,
+                       g_rows, n, row_elems, noise, noise_rows, step);
+    IEF_LAUNCH_CHECK();
+    return IEF_OK;
+}
+
+// the extraction: R rows at R timesteps in one launch, coef_rows[r] = {a_from, a_to, sigma, dir, g}
+__global__ __launch_bounds__(256) void ddpm_noise_maps_kernel(const float* __restrict__ eu, const float* __restrict__ ec,
+                                                              const float* __restrict__ xt, const float* __restrict__ xp,
+                                                              float* __restrict__ zo, const float* __restrict__ coef_rows,
+                                                              long long n, long long row_elems) {
+    const bool small = n <= 0xffffffffll;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+        const float* __restrict__ cr = coef_rows + 5 * ddpm_row_of(i, row_elems, small);
+        const DdpmCoef c = ddpm_coef(cr);
+        const float mu = ddpm_mu_elem(c, cr[4], eu, ec, xt, nullptr, i);
+        zo[i] = c.sigma == 0.0f ? 0.0f : (xp[i] - mu) / c.sigma;
+    }
+}
+
+extern "C" int ief_ddpm_noise_maps_f32(const float* eps_u, const float* eps_c, const float* x_t, const float* x_prev,
+                                       float* z_out, const float* coef_rows, int R, long long row_elems, void* stream) {
+    if (!eps_c || !x_t || !x_prev || !z_out || !coef_rows) return IEF_EINVAL;
+    if (R <= 0 || row_elems <= 0) return IEF_ESHAPE;
+    const long long n = (long long)R * row_elems;
+    int grid = (int)((n + 255) / 256);
+    if (grid > 2048) grid = 2048;
+    hipLaunchKernelGGL(ddpm_noise_maps_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, eps_u, eps_c, x_t, x_prev, z_out,
+                       coef_rows, n, row_elems);
+    IEF_LAUNCH_CHECK();
+    return IEF_OK;
+}
+
 // diffusers Timesteps(dim, flip_sin_to_cos=True, downscale_freq_shift=0) [ext]: [cos | sin]
 __global__ void timestep_embedding_kernel(const float* __restrict__ t, half_t* __restrict__ out, int B, int dim) {
     const int half_dim = dim >> 1;

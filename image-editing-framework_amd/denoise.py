@@ -10,6 +10,7 @@ overhead would exceed the GPU time.  Here the whole step is captured once:
     [P2P plan: select_step(gate coefficients), select_step(self-replace sources)]
     latents -> CFG batch copy -> UNet (fused attention control) -> fused CFG + DDIM update (in place)
     [Direct Inversion: the same launch moves the source row (row 0) back onto the stored inversion trajectory]
+    [edit-friendly DDPM inversion: CFG with a scale per batch row + the eta = 1 update with the stored noise map of this step instead]
     [P2P plan with a LocalBlend: the word-masked blend of the updated latents, in place]
     advance_step
 (on the f16x3 planes trunk the UNet takes the latents themselves and runs what both halves of the CFG batch share once: no copy;
@@ -109,15 +110,59 @@ def check_source_trajectory(traj, *, mode, cfg, uncond_list, row_shape, num_step
         raise ValueError(f"source_trajectory: {traj.shape[0]} rows for a schedule of {num_steps} steps")
 
 
+def guidance_rows(guidance_scale, num_latents):
+    """one guidance scale per batch row: a number serves every row, a sequence brings one each (ValueError otherwise)"""
+    if isinstance(guidance_scale, (int, float)):
+        return [float(guidance_scale)] * num_latents
+    try:
+        rows = [float(g) for g in guidance_scale]
+    except TypeError:
+        raise ValueError("noise_maps: guidance_scale is one number or a sequence of one number per prompt") from None
+    if len(rows) != num_latents:
+        raise ValueError(f"noise_maps: {len(rows)} guidance scales for {num_latents} batch rows")
+    return rows
+
+
+def check_noise_maps(maps, *, mode, cfg, uncond_list, source_trajectory, row_shape, num_steps, skip, guidance_scale=None,
+                     num_latents=None):
+    """the argument checks of an edit-friendly DDPM inversion loop (host-side facts only; raises ValueError): `maps` is fp32
+    [S - skip, C, h, w], row i = the noise map z of edit step i, which runs timestep `timesteps[skip + i]` of the S-step schedule"""
+    if mode != "denoise":
+        raise ValueError(f"noise_maps: only a denoising loop adds stored noise (mode={mode!r})")
+    if not cfg:
+        raise ValueError("noise_maps: the maps were extracted under classifier-free guidance and the edit needs a guidance scale per "
+                         "row; a loop without guidance has none")
+    if uncond_list is not None:
+        raise ValueError("noise_maps together with uncond_list: choose DDPM inversion or null-text embeddings, not both")
+    if source_trajectory is not None:
+        raise ValueError("noise_maps together with source_trajectory: choose DDPM inversion or Direct Inversion, not both")
+    if not isinstance(skip, int) or isinstance(skip, bool) or not 0 <= skip < num_steps:
+        raise ValueError(f"noise_maps: skip must be an integer in [0, {num_steps}), got {skip!r}")
+    if not isinstance(maps, torch.Tensor) or maps.dtype != torch.float32:
+        raise ValueError("noise_maps: expected one fp32 tensor [steps - skip, C, h, w]")
+    if tuple(maps.shape[1:]) != tuple(row_shape) or maps.dim() != 1 + len(row_shape):
+        raise ValueError(f"noise_maps: rows of shape {tuple(maps.shape[1:])} for latents of shape {tuple(row_shape)}")
+    if maps.shape[0] != num_steps - skip:
+        raise ValueError(f"noise_maps: {maps.shape[0]} rows for a schedule of {num_steps} steps with skip {skip} "
+                         f"({num_steps - skip} edit steps)")
+    if num_latents is not None:
+        guidance_rows(guidance_scale, num_latents)
+
+
 class FusedDenoiser:
     def __init__(self, model, context: torch.Tensor, num_latents: int, latent_hw, guidance_scale: Optional[float],
                  mode: str = "denoise", uncond_list: Optional[List[torch.Tensor]] = None, use_graph: bool = True,
-                 added_cond_kwargs=None, source_trajectory: Optional[torch.Tensor] = None):
+                 added_cond_kwargs=None, source_trajectory: Optional[torch.Tensor] = None,
+                 noise_maps: Optional[torch.Tensor] = None, skip: int = 0):
         """context: [2*Bp,77,C] (uncond, cond) for mode 'denoise' with CFG, [Bp,77,C] for 'invert' / no-CFG.
         added_cond_kwargs: SDXL's {"text_embeds" [B, 1280], "time_ids" [B, 6]} (one row per UNet batch row); they are
         constant over the steps, so they fold into the per-step time-embedding rows (then one row PER BATCH ROW).
         source_trajectory: Direct Inversion -- fp32 [S, C, h, w], row i = z*_{S-1-i} of the DDIM inversion; after step i batch row 0
-        (the source branch) is x' + (z - x') in the launch of the CFG + DDIM update, every other row is x'."""
+        (the source branch) is x' + (z - x') in the launch of the CFG + DDIM update, every other row is x'.
+        noise_maps, skip: edit-friendly DDPM inversion -- fp32 [S - skip, C, h, w], the maps of `p2p.inversion.ddpm.DDPMInversion`; the
+        loop runs the S - skip timesteps `timesteps[skip:]` from y_skip, step i is the eta = 1 update with map i (every batch row
+        reads the same map), and `guidance_scale` may be a sequence of one scale per latent (the source row takes the scale its
+        maps were extracted with)."""
         self.model, self.unet, self.sched = model, model.unet, model.scheduler
         dev = self.unet.device
         self.mode = mode
@@ -125,6 +170,15 @@ class FusedDenoiser:
         if source_trajectory is not None:
             check_source_trajectory(source_trajectory, mode=mode, cfg=self.cfg, uncond_list=uncond_list,
                                     row_shape=(self.unet.config.in_channels, *latent_hw), num_steps=len(self.sched.timesteps))
+        if noise_maps is not None:
+            check_noise_maps(noise_maps, mode=mode, cfg=self.cfg, uncond_list=uncond_list, source_trajectory=source_trajectory,
+                             row_shape=(self.unet.config.in_channels, *latent_hw), num_steps=len(self.sched.timesteps), skip=skip,
+                             guidance_scale=guidance_scale, num_latents=num_latents)
+            if added_cond_kwargs is not None:
+                raise ValueError("noise_maps: DDPM inversion is built for the SD1.x / SD2.x pipelines (no added_cond_kwargs)")
+        elif skip:
+            raise ValueError("skip: only a loop with noise maps starts inside the schedule")
+        self.skip = skip if noise_maps is not None else 0
         self.Bp = num_latents
         self.B = 2 * num_latents if self.cfg else num_latents
         if context.shape[0] != self.B:
@@ -146,6 +200,9 @@ class FusedDenoiser:
         self.coef_table = self.temb_table = self.temb_cur = self.ctx = self.ctx_table = None
         # the graph READS this buffer (row = the device step counter): `rebind` copies the next image's rows into it
         self.traj = None if source_trajectory is None else source_trajectory.to(dev).contiguous().clone()
+        # likewise the noise maps and the per-row guidance scales of a DDPM inversion edit
+        self.maps = None if noise_maps is None else noise_maps.to(dev).contiguous().clone()
+        self.g_rows = None
         self._fill(context, guidance_scale, uncond_list, added_cond_kwargs)
         self.use_graph = use_graph
         self.graph = None
@@ -160,9 +217,12 @@ class FusedDenoiser:
         if self.mode == "invert":
             ts = ts[::-1]
             coef = [self.sched.reverse_coeffs(t) for t in ts]
+        elif self.maps is not None:
+            ts = ts[self.skip:]
+            coef = [self.sched.ddpm_coeffs(t) for t in ts]
         else:
             coef = [self.sched.step_coeffs(t) for t in ts]
-        g = float(guidance_scale) if self.cfg else 1.0
+        g = float(guidance_scale) if self.cfg and self.maps is None else 1.0
         self.num_steps = len(ts)
 
         def put(name, value):
@@ -172,7 +232,11 @@ class FusedDenoiser:
             else:
                 cur.copy_(value)
 
-        put("coef_table", torch.tensor([[a, b, g, 0.0] for a, b in coef], dtype=torch.float32, device=dev))
+        if self.maps is not None:         # rows {a, p, sigma, dir}; the guidance scales travel per batch row
+            put("coef_table", torch.tensor(coef, dtype=torch.float32, device=dev))
+            put("g_rows", torch.tensor(guidance_rows(guidance_scale, self.Bp), dtype=torch.float32, device=dev))
+        else:
+            put("coef_table", torch.tensor([[a, b, g, 0.0] for a, b in coef], dtype=torch.float32, device=dev))
         aug = self.unet.aug_embedding(added_cond_kwargs)          # None unless the UNet has SDXL's additional embedding
         if aug is not None and aug.shape[0] != self.B:
             raise ValueError(f"added_cond_kwargs batch {aug.shape[0]} != UNet batch {self.B}")
@@ -204,16 +268,25 @@ class FusedDenoiser:
         return cfg_shared_prefix_reason(mode=self.mode, cfg=self.cfg, enabled=CFG_SHARED_PREFIX and type(self)._step_body is FusedDenoiser._step_body,
                                         **facts(tuple(self.lat.shape[-2:]), ctx_len))
 
-    def _key(self, context, uncond_list, source_trajectory=None):
+    def _key(self, context, uncond_list, source_trajectory=None, noise_maps=None, skip=0):
         plan = self.unet._plan
         return (id(self.unet), self.mode, self.Bp, tuple(self.lat.shape[-2:]), self.cfg, tuple(context.shape),
                 None if uncond_list is None else len(uncond_list), len(self.sched.timesteps),
                 None if plan is None else plan.signature(self.unet), self._shared_reason(context.shape[1]) is None,
-                source_trajectory is not None, getattr(self.unet, "attn_key_splits", 1))
+                source_trajectory is not None, noise_maps is not None, skip if noise_maps is not None else 0,
+                getattr(self.unet, "attn_key_splits", 1))
 
-    def rebind(self, context, guidance_scale, uncond_list, added_cond_kwargs=None, source_trajectory=None):
+    def rebind(self, context, guidance_scale, uncond_list, added_cond_kwargs=None, source_trajectory=None, noise_maps=None,
+               skip=0):
         """point a captured loop at the next image: new tables, new cross-attention K/V, the new controller's plan, the next
-        image's inversion trajectory"""
+        image's inversion trajectory or noise maps and guidance scales"""
+        if (noise_maps is None) != (self.maps is None) or (noise_maps is not None and skip != self.skip):
+            raise ValueError("rebind: a loop captured with noise maps serves only jobs that bring maps of the same skip, and the reverse")
+        if noise_maps is not None:
+            check_noise_maps(noise_maps, mode=self.mode, cfg=self.cfg, uncond_list=uncond_list, source_trajectory=source_trajectory,
+                             row_shape=tuple(self.lat.shape[1:]), num_steps=len(self.sched.timesteps), skip=skip,
+                             guidance_scale=guidance_scale, num_latents=self.Bp)
+            self.maps.copy_(noise_maps)
         if (source_trajectory is None) != (self.traj is None):
             raise ValueError("rebind: a loop captured with a source trajectory serves only jobs that bring one, and the reverse")
         if source_trajectory is not None:
@@ -248,7 +321,9 @@ class FusedDenoiser:
                 self.lat_in[: self.Bp].copy_(self.lat)
                 self.lat_in[self.Bp:].copy_(self.lat)
             eps = self.unet(self.lat_in, encoder_hidden_states=self.ctx, temb_row=self.temb_cur)["sample"]
-        if self.cfg:
+        if self.maps is not None:
+            hip.cfg_ddpm_step(eps[: self.Bp], eps[self.Bp:], self.lat, self.coef_cur, self.g_rows, self.maps, self.step, out=self.lat)
+        elif self.cfg:
             hip.cfg_ddim_step(eps[: self.Bp], eps[self.Bp:], self.lat, self.coef_cur, out=self.lat,
                               rect=None if self.traj is None else (self.traj, self.step))
         else:
@@ -402,7 +477,10 @@ class CfgSplitDenoiser(FusedDenoiser):
     (`p2p.model.register.register_attention_control`); its counters advance on both."""
 
     def __init__(self, model, context, num_latents, latent_hw, guidance_scale: float, group=None, uncond_list=None,
-                 use_graph: bool = True, source_trajectory=None):
+                 use_graph: bool = True, source_trajectory=None, noise_maps=None, skip=0):
+        if noise_maps is not None or skip:
+            raise ValueError("CFG split: edit-friendly DDPM inversion (noise_maps) is not built for the two-GPU split; run the edit "
+                             "on one GPU")
         if source_trajectory is not None:
             raise ValueError("CFG split: Direct Inversion (source_trajectory) is not built for the two-GPU split; run the edit "
                              "on one GPU")
@@ -505,27 +583,28 @@ class CfgSplitDenoiser(FusedDenoiser):
 
 
 def acquire(model, context, num_latents, latent_hw, guidance_scale, mode="denoise", uncond_list=None,
-            use_graph=True, added_cond_kwargs=None, source_trajectory=None) -> FusedDenoiser:
+            use_graph=True, added_cond_kwargs=None, source_trajectory=None, noise_maps=None, skip=0) -> FusedDenoiser:
     """a FusedDenoiser for this job: a pooled one with a captured graph of the same shape / plan signature, re-pointed
     at the new context, tables and controller — or a new one.  source_trajectory: Direct Inversion (`FusedDenoiser`); loops
-    with and without one never share a pool entry"""
+    with and without one never share a pool entry.  noise_maps, skip: edit-friendly DDPM inversion (`FusedDenoiser`;
+    guidance_scale may then be one scale per latent); presence of maps and skip are part of the pool key"""
     if REUSE_GRAPHS and use_graph:
         probe = FusedDenoiser.__new__(FusedDenoiser)
         probe.unet, probe.sched, probe.mode = model.unet, model.scheduler, mode
         probe.cfg, probe.Bp = guidance_scale is not None, num_latents
         probe.lat = torch.empty(0, 0, *latent_hw)
-        key = probe._key(context, uncond_list, source_trajectory)
+        key = probe._key(context, uncond_list, source_trajectory, noise_maps, skip)
         free = _POOL.get(key)
         if free:
             loop = free.pop()
-            loop.rebind(context, guidance_scale, uncond_list, added_cond_kwargs, source_trajectory)
+            loop.rebind(context, guidance_scale, uncond_list, added_cond_kwargs, source_trajectory, noise_maps, skip)
             return loop
         loop = FusedDenoiser(model, context, num_latents, latent_hw, guidance_scale, mode, uncond_list, use_graph,
-                             added_cond_kwargs, source_trajectory)
+                             added_cond_kwargs, source_trajectory, noise_maps, skip)
         loop._pool_key = key
         return loop
     return FusedDenoiser(model, context, num_latents, latent_hw, guidance_scale, mode, uncond_list, use_graph,
-                         added_cond_kwargs, source_trajectory)
+                         added_cond_kwargs, source_trajectory, noise_maps, skip)
 
 
 def drop_pool():

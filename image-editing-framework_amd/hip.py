@@ -1735,6 +1735,62 @@ def cfg_ddim_step(eps_u, eps_c, x, coef, out=None, x0_out=None, rect=None):
     return out
 
 
+def cfg_ddpm_step(eps_u, eps_c, x, coef, g_rows, noise, step, out=None, x0_out=None):
+    """The eta = 1 step of an edit-friendly DDPM inversion edit (`ief_cfg_ddpm_step_f32`): for batch row b of x [Bp, ...]
+        eps = eps_u[b] + g_rows[b] (eps_c[b] - eps_u[b]);  mu = sqrt(a_to) x0 + dir eps;  x'[b] = mu + sigma noise[clamp(step[0])]
+    coef = device fp32 [a_from, a_to, sigma, dir]; g_rows device fp32 [Bp] (None only with eps_u None => eps = eps_c); noise device fp32
+    [rows, *x.shape[1:]] -- every batch row reads the same row; step device int32 [1] (read by the kernel)."""
+    lib = load()
+    _dev32(eps_c, "eps_c")
+    _dev32(x, "x")
+    _dev32(coef, "coef")
+    _dev32(noise, "noise maps")
+    if eps_u is not None:
+        _dev32(eps_u, "eps_u")
+        _dev32(g_rows, "g_rows")
+    if x.dim() < 2 or eps_c.shape != x.shape or (eps_u is not None and eps_u.shape != x.shape):
+        raise ValueError(f"cfg_ddpm_step: eps and x must be [Bp, ...] of one shape, got {tuple(eps_c.shape)} and {tuple(x.shape)}")
+    if coef.numel() != 4:
+        raise ValueError(f"cfg_ddpm_step: coef is [a_from, a_to, sigma, dir], got {coef.numel()} elements")
+    if eps_u is not None and g_rows.numel() != x.shape[0]:
+        raise ValueError(f"cfg_ddpm_step: {g_rows.numel()} guidance scales for {x.shape[0]} batch rows")
+    if noise.dim() != x.dim() or noise.shape[0] < 1 or noise.shape[1:] != x.shape[1:]:
+        raise ValueError(f"cfg_ddpm_step: the noise maps must be [steps, {', '.join(map(str, x.shape[1:]))}] (x without its batch "
+                         f"dimension), got {tuple(noise.shape)}")
+    if _devi32(step, "step") is None or step.numel() != 1:
+        raise TypeError("step: expected a device int32 tensor of one element")
+    if out is None:
+        out = torch.empty_like(x)
+    for t, name in ((out, "out"), (x0_out, "x0_out")):
+        if t is not None and (_dev32(t, name).shape != x.shape):
+            raise ValueError(f"cfg_ddpm_step: {name} must have the shape of x")
+    _check(lib.ief_cfg_ddpm_step_f32(_ptr(eps_u), eps_c.data_ptr(), x.data_ptr(), out.data_ptr(), _ptr(x0_out), coef.data_ptr(),
+                                     _ptr(g_rows) if eps_u is not None else None, x.numel(), x[0].numel(), noise.data_ptr(),
+                                     noise.shape[0], step.data_ptr(), _stream()), "ief_cfg_ddpm_step_f32")
+    return out
+
+
+def ddpm_noise_maps(eps_u, eps_c, x_t, x_prev, coef_rows, out=None):
+    """The noise maps of R rows at R timesteps in one launch (`ief_ddpm_noise_maps_f32`): z[r] = (x_prev[r] - mu_r) / sigma_r with
+    mu_r the mean of `cfg_ddpm_step` at (x_t[r], eps[r]); a row with sigma_r == 0 is zero.  All tensors device fp32 [R, ...];
+    coef_rows device fp32 [R, 5] = [a_from, a_to, sigma, dir, guidance] per row; eps_u None => eps = eps_c."""
+    lib = load()
+    for t, name in ((eps_c, "eps_c"), (x_t, "x_t"), (x_prev, "x_prev"), (coef_rows, "coef_rows")) + (
+            () if eps_u is None else ((eps_u, "eps_u"),)) + (() if out is None else ((out, "out"),)):
+        _dev32(t, name)
+    if x_t.dim() < 2 or any(t.shape != x_t.shape for t in (eps_c, x_prev) + (() if eps_u is None else (eps_u,)) +
+                            (() if out is None else (out,))):
+        raise ValueError(f"ddpm_noise_maps: eps, x_t, x_prev and out must be [R, ...] of one shape ({tuple(x_t.shape)})")
+    if tuple(coef_rows.shape) != (x_t.shape[0], 5):
+        raise ValueError(f"ddpm_noise_maps: coef_rows must be [{x_t.shape[0]}, 5] = [a_from, a_to, sigma, dir, guidance] per row, "
+                         f"got {tuple(coef_rows.shape)}")
+    if out is None:
+        out = torch.empty_like(x_t)
+    _check(lib.ief_ddpm_noise_maps_f32(_ptr(eps_u), eps_c.data_ptr(), x_t.data_ptr(), x_prev.data_ptr(), out.data_ptr(),
+                                       coef_rows.data_ptr(), x_t.shape[0], x_t[0].numel(), _stream()), "ief_ddpm_noise_maps_f32")
+    return out
+
+
 def ddim_step(eps, x, a_from: float, a_to: float):
     """scheduler.step on device tensors: returns (x_prev, x0)."""
     coef = torch.tensor([a_from, a_to, 1.0], dtype=torch.float32, device=x.device)

@@ -3,7 +3,10 @@
 Same flags and defaults (`--inversion_type` defaults to "null-text" as in the reference, :26), same outputs:
 `./exp/source.png`, `./exp/inversion.png`, `./exp/edit.png`; plus `--blend_source_words` / `--blend_target_words` /
 `--blend_threshold` for `LocalBlend`, and `--inversion_type direct` (not a reference value): Direct Inversion, the DDIM inversion
-whose trajectory the edit's source row is moved back onto after every step (`ief_amd.p2p.inversion.direct`).
+whose trajectory the edit's source row is moved back onto after every step (`ief_amd.p2p.inversion.direct`), and
+`--inversion_type ddpm` (not a reference value): edit-friendly DDPM inversion (`ief_amd.p2p.inversion.ddpm`) -- noise maps extracted
+`--invert_batch` rows per UNet launch under `--ddpm_guidance_src`, the edit from step `--skip` on with `--ddpm_guidance_tar` on the
+target row; `--seed` also seeds the maps' noise.  Not for SDXL pipelines.
 """
 import argparse
 import os
@@ -14,6 +17,7 @@ from PIL import Image
 from _bootstrap import load_pipe, seed_everything
 
 from ief_amd.p2p.inversion.ddim import ddim_inversion, ddim_inversion_xl
+from ief_amd.p2p.inversion.ddpm import DDPMInversion
 from ief_amd.p2p.inversion.direct import DirectInversion, DirectInversion_XL
 from ief_amd.p2p.inversion.nti import NTI, NTI_XL
 from ief_amd.p2p.model.attention_control import AttentionRefine, AttentionReplace
@@ -21,6 +25,34 @@ from ief_amd.p2p.model.ptp_utils import local_blend_from_words
 from ief_amd.p2p.model.register import unregister_attention_control
 from ief_amd.p2p.model.sd_utils import P2P, P2P_NTI, P2P_XL, P2P_XL_NTI
 from ief_amd.p2p.utils.save_image import save_img
+
+XL_VERSIONS = ("xl-base", "smallxl")       # the `StableDiffusionXLPipeline` branch of `_bootstrap._build_pipe`
+NUM_STEPS = 50
+
+
+def add_ddpm_arguments(ap):
+    """the flags of `--inversion_type ddpm` (shared with test.py); defaults: the paper's"""
+    ap.add_argument("--ddpm_guidance_src", type=float, default=3.5, help="ddpm: guidance scale of the extraction and of the source row")
+    ap.add_argument("--ddpm_guidance_tar", type=float, default=15.0, help="ddpm: guidance scale of the target row")
+    ap.add_argument("--skip", type=int, default=18,
+                    help="ddpm: the edit starts at this step of the 50 (18 = 36 %% of 50 steps, the paper's setting); 0 = from pure noise")
+
+
+def check_ddpm_arguments(ap, args, nti_batch=1):
+    """argparse errors of `--inversion_type ddpm`; -> the keyword arguments `edit_one` takes as `ddpm=`, or None"""
+    if args.inversion_type != "ddpm":
+        return None
+    if nti_batch > 1:
+        ap.error("--nti_batch groups null-text optimisations; --inversion_type ddpm runs none (use --invert_batch / --in_flight)")
+    if args.sd_version in XL_VERSIONS:
+        ap.error("--inversion_type ddpm is built for the SD1.x / SD2.x pipelines, not for --sd_version " + args.sd_version)
+    if not 0 <= args.skip < NUM_STEPS:
+        ap.error(f"--skip must lie in [0, {NUM_STEPS}): the edit runs the steps from --skip on")
+    if args.invert_batch < 1:
+        ap.error("--invert_batch must be >= 1")
+    return dict(guidance_src=args.ddpm_guidance_src, guidance_tar=args.ddpm_guidance_tar, skip=args.skip,
+                rows_per_launch=args.invert_batch, seed=args.seed)
+
 
 parser = argparse.ArgumentParser("General config")
 parser.add_argument("--sd_version", type=str, default="1.5")
@@ -42,12 +74,15 @@ parser.add_argument("--attn_key_splits", type=str, default=None, choices=["1", "
 parser.add_argument("--blend_source_words", type=str, nargs="+", default=None)
 parser.add_argument("--blend_target_words", type=str, nargs="+", default=None)
 parser.add_argument("--blend_threshold", type=float, default=0.3)
+add_ddpm_arguments(parser)
+parser.add_argument("--invert_batch", type=int, default=4, help="--inversion_type ddpm: rows (timesteps) per UNet launch, at CFG batch 2 K (8 measured fastest on SD1.5)")
 
 
 def edit_latent(pipe, editor, x_T, source_prompt, target_prompt, edit_type, device, extra=None, num_inference_steps=50,
-                guidance_scale=7.5, cross_replace_steps=0.8, self_replace_steps=0.6, local_blend=None):
-    """Prompt-to-Prompt edit from an inverted latent x_T [1,4,h,w] -> uint8 images [2,H,W,3] (reconstruction, edit)"""
-    kw = dict(prompts=source_prompt + target_prompt, tokenizer=pipe.tokenizer, num_steps=num_inference_steps,
+                guidance_scale=7.5, cross_replace_steps=0.8, self_replace_steps=0.6, local_blend=None, controller_steps=None):
+    """Prompt-to-Prompt edit from an inverted latent x_T [1,4,h,w] -> uint8 images [2,H,W,3] (reconstruction, edit).
+    controller_steps: the steps the controller counts when the edit runs only a part of the schedule (ddpm with --skip)"""
+    kw = dict(prompts=source_prompt + target_prompt, tokenizer=pipe.tokenizer, num_steps=controller_steps or num_inference_steps,
               cross_replace_steps=cross_replace_steps, self_replace_steps=self_replace_steps, device=device,
               local_blend=local_blend)
     if edit_type == "replace":
@@ -64,11 +99,26 @@ def edit_latent(pipe, editor, x_T, source_prompt, target_prompt, edit_type, devi
     return images
 
 
+def ddpm_invert(pipe, invertor, latent, source_prompt, num_inference_steps, ddpm):
+    """the noise maps of one encoded image -> (y_skip [1,4,h,w], maps [S - skip,4,h,w])"""
+    pipe.scheduler.set_timesteps(num_inference_steps)
+    y_skip, maps, _ = invertor.noise_maps(pipe, latent, source_prompt, guidance_scale=ddpm["guidance_src"], skip=ddpm["skip"],
+                                          rows_per_launch=ddpm["rows_per_launch"],
+                                          generator=torch.Generator().manual_seed(ddpm["seed"]))
+    return y_skip, maps
+
+
 def edit_one(pipe, editor, invertor, image, source_prompt, target_prompt, inversion_type, edit_type, device,
              num_inference_steps=50, guidance_scale=7.5, cross_replace_steps=0.8, self_replace_steps=0.6,
-             num_inner_steps=10, early_stop_epsilon=1e-5, local_blend=None):
-    """invert + edit one PIL image -> uint8 images [2,H,W,3] (inversion reconstruction, edit)"""
+             num_inner_steps=10, early_stop_epsilon=1e-5, local_blend=None, ddpm=None):
+    """invert + edit one PIL image -> uint8 images [2,H,W,3] (inversion reconstruction, edit).  ddpm: `check_ddpm_arguments`' dict
+    for inversion_type "ddpm" (its `seed` seeds this image's noise)"""
     latent = invertor.image2latent(model=pipe, image=image, device=device, dtype=torch.float32)
+    if inversion_type == "ddpm":
+        y_skip, maps = ddpm_invert(pipe, invertor, latent, source_prompt, num_inference_steps, ddpm)
+        return edit_latent(pipe, editor, y_skip, source_prompt, target_prompt, edit_type, device, dict(noise_maps=maps, skip=ddpm["skip"]),
+                           num_inference_steps, (ddpm["guidance_src"], ddpm["guidance_tar"]), cross_replace_steps, self_replace_steps,
+                           local_blend, controller_steps=num_inference_steps - ddpm["skip"])
     latents, context = invertor.ddim_inversion_loop(pipe, latent, source_prompt)
     extra = {}
     if inversion_type == "null-text":
@@ -84,6 +134,7 @@ def edit_one(pipe, editor, invertor, image, source_prompt, target_prompt, invers
 
 def main(argv=None):
     args = parser.parse_args(argv)
+    ddpm = check_ddpm_arguments(parser, args)
     if (args.blend_source_words is None) != (args.blend_target_words is None):
         parser.error("--blend_source_words and --blend_target_words go together")
     device = torch.device("cuda:{}".format(args.device))
@@ -101,6 +152,9 @@ def main(argv=None):
     elif args.inversion_type == "direct":
         editor = (P2P_XL if xl else P2P)(model=pipe, num_inference_steps=50)
         invertor = DirectInversion_XL() if xl else DirectInversion()
+    elif args.inversion_type == "ddpm":
+        editor = P2P(model=pipe, num_inference_steps=50)
+        invertor = DDPMInversion()
     else:
         raise ValueError("Please choose right inversion type")
     size = pipe.unet.config.sample_size * pipe.vae_scale_factor
@@ -111,7 +165,7 @@ def main(argv=None):
                       edit_type, device,
                       local_blend=local_blend_from_words(pipe.tokenizer, [args.source_prompt, args.target_prompt],
                                                          args.blend_source_words, args.blend_target_words, args.blend_threshold,
-                                                         device))
+                                                         device), ddpm=ddpm)
     save_img(images[0], os.path.join(out_path, "inversion.png"))
     save_img(images[1], os.path.join(out_path, "edit.png"))
 

@@ -1,0 +1,94 @@
+"""Edit-friendly DDPM inversion (Huberman-Spiegelglas, Kulikov, Michaeli, "An Edit Friendly DDPM Noise Space", CVPR 2024): the
+fourth inversion type.
+
+Unlike the DDIM inversion there is NO chain.  With `scheduler.timesteps` in edit order t_0 > ... > t_{S-1}, (a_i, p_i) =
+`step_coeffs(t_i)` and the eta = 1 quantities of `DDIMScheduler.ddpm_coeffs` (sigma_i, dir_i), the stored latents are drawn
+independently from the encoded image x0,
+
+    y_S = x0,      y_i = sqrt(a_i) x0 + sqrt(1 - a_i) n_i     (n_i: seeded CPU generator, fp32)
+
+and the noise maps follow from one UNet evaluation each, independent of each other:
+
+    eps_i = eps_u + g_src (eps_c - eps_u)                     UNet at (y_i, t_i), source prompt
+    mu_i  = sqrt(p_i) (y_i - sqrt(1 - a_i) eps_i) / sqrt(a_i) + dir_i eps_i
+    z_i   = (y_{i+1} - mu_i) / sigma_i                        i = skip ... S - 1
+
+So one image gives S - skip rows that run through the UNet K at a time, at CFG batch 2 K with ONE TIMESTEP PER ROW (`temb_row`
+with one row per batch row), followed by one `ief_ddpm_noise_maps_f32` launch per chunk: no other inversion here fills the chip
+from a single image.  The edit starts from y_skip and runs `timesteps[skip:]`; step i of it is x' = mu_i(x, eps) + sigma_i z_i on
+every batch row (`ief_cfg_ddpm_step_f32`), with a guidance scale per row: the source row takes g_src and so reproduces y_{i+1}, ...,
+y_S = x0 up to rounding, the target rows take a stronger scale.
+
+The published code zeroes the last map (its final step is deterministic).  Here EVERY map is kept: with z_{S-1} the source row ends
+on x0 itself, not on the mean of the last step, which is what "the source row reproduces the image" asks for.
+
+Out of scope: SDXL pipelines, eta != 1, chunks that mix rows of several images.
+"""
+import torch
+
+from ... import hip
+from .ddim import ddim_inversion
+
+
+class DDPMInversion(ddim_inversion):
+    """`ddim_inversion` (for `image2latent` / `get_context`) plus the noise-map extraction; `ddim_inversion_loop` is inherited
+    untouched and not used by it"""
+
+    def sample_xts(self, model, x0, generator=None):
+        """x0 [1, C, h, w] (or [C, h, w]) -> fp32 [S + 1, C, h, w] on x0's device: row i < S = sqrt(a_i) x0 + sqrt(1 - a_i) n_i at
+        `timesteps[i]`, row S = x0.  The n_i are ONE draw of [S, C, h, w] from a CPU generator (default: seed 0), so a run does not
+        depend on the device."""
+        x0 = x0.float().reshape(-1, *x0.shape[-2:])
+        ts = model.scheduler.timesteps.tolist()
+        if generator is None:
+            generator = torch.Generator().manual_seed(0)
+        if generator.device.type != "cpu":
+            raise ValueError("sample_xts: the noise is drawn from a CPU torch.Generator (device-independent runs)")
+        noise = torch.randn((len(ts), *x0.shape), generator=generator, dtype=torch.float32)
+        a = torch.tensor([model.scheduler.step_coeffs(t)[0] for t in ts], dtype=torch.float32).reshape(-1, 1, 1, 1)
+        x0c = x0.cpu()
+        xts = torch.sqrt(a) * x0c[None] + torch.sqrt(1.0 - a) * noise
+        return torch.cat([xts, x0c[None]]).to(x0.device).contiguous()
+
+    @torch.no_grad()
+    def noise_maps(self, model, x0, prompt, guidance_scale=3.5, skip=0, rows_per_launch=4, generator=None):
+        """-> (y_skip [1, C, h, w], maps fp32 [S - skip, C, h, w], xts [S + 1, C, h, w]).  guidance_scale 3.5 and skip 0 are the
+        paper's extraction defaults (its edits then skip 36 % of the steps).  Rows skip ... S - 1 go through the UNet
+        `rows_per_launch` at a time: one forward at batch 2 K = [K unconditional | K conditional] rows with the chunk's K
+        time-embedding rows repeated for both halves, then one extraction launch.  The last chunk is simply shorter (eager
+        launches: nothing is captured, so nothing needs padding)."""
+        unet, sched = model.unet, model.scheduler
+        if not (all(m.is_native() for m in unet.attention_modules()) and getattr(unet, "_plan", None) is None):
+            raise RuntimeError("DDPMInversion: an attention hook is installed; invert before registering controllers")
+        if getattr(getattr(unet, "cfg", None), "addition_embed", False):
+            raise ValueError("DDPMInversion: built for the SD1.x / SD2.x pipelines, not for an SDXL UNet")
+        ts = sched.timesteps.tolist()
+        S = len(ts)
+        if not isinstance(skip, int) or not 0 <= skip < S:
+            raise ValueError(f"noise_maps: skip must be an integer in [0, {S}), got {skip!r}")
+        K = int(rows_per_launch)
+        if K < 1:
+            raise ValueError("noise_maps: rows_per_launch must be >= 1")
+        if isinstance(prompt, str):
+            prompt = [prompt]
+        if len(prompt) != 1:
+            raise ValueError("noise_maps: one image and one source prompt per call")
+        dev = unet.device
+        xts = self.sample_xts(model, x0.to(dev), generator)
+        uncond, cond = self.get_context(model, prompt).chunk(2)
+        g = float(guidance_scale)
+        coef = torch.tensor([[*sched.ddpm_coeffs(t), g] for t in ts], dtype=torch.float32, device=dev)
+        temb = unet.time_rows(torch.tensor(ts, dtype=torch.float32, device=dev))          # [S, width]
+        maps = torch.empty(S - skip, *xts.shape[1:], dtype=torch.float32, device=dev)
+        ctxs = {}         # one context tensor per chunk size: the cross-attention K/V cache is keyed on the tensor, so the full
+        for r0 in range(skip, S, K):      # chunks project their K/V once
+            r1 = min(r0 + K, S)
+            k = r1 - r0
+            y = xts[r0:r1]
+            if k not in ctxs:
+                ctxs[k] = unet._act(torch.cat([uncond.expand(k, -1, -1), cond.expand(k, -1, -1)]).to(dev).contiguous())
+            ctx = ctxs[k]
+            rows = temb[r0:r1]
+            eps = unet(torch.cat([y, y]), encoder_hidden_states=ctx, temb_row=torch.cat([rows, rows]).contiguous())["sample"]
+            hip.ddpm_noise_maps(eps[:k], eps[k:], y, xts[r0 + 1:r1 + 1], coef[r0:r1], out=maps[r0 - skip:r1 - skip])
+        return xts[skip:skip + 1].clone(), maps, xts

@@ -24,7 +24,7 @@ import torch
 from tqdm import tqdm
 
 from ... import hip
-from ...denoise import acquire, check_source_trajectory, run_interleaved
+from ...denoise import acquire, check_noise_maps, check_source_trajectory, guidance_rows, run_interleaved
 from .register import register_attention_control, unregister_attention_control
 
 
@@ -85,16 +85,33 @@ class P2P:
                               guidance_scale: float = 7.5, generator: Optional[torch.Generator] = None,
                               latent: Optional[torch.FloatTensor] = None, low_resource: bool = False,
                               uncond_embeddings_list=None, height: Optional[int] = None, width: Optional[int] = None,
-                              return_latents: bool = False, cfg_split_group=None, source_trajectory=None):
+                              return_latents: bool = False, cfg_split_group=None, source_trajectory=None, noise_maps=None,
+                              skip: int = 0):
         """cfg_split_group (not a reference argument): a torch.distributed group of TWO ranks that run this ONE edit
         together — rank 0 the unconditional rows of the CFG batch, rank 1 the conditional rows, one eps exchange per
         step (`denoise.CfgSplitDenoiser`); both ranks return the same latents / images.
         source_trajectory (not a reference argument): Direct Inversion -- fp32 [S, C, h, w], row i = z*_{S-1-i} of the source
         image's DDIM inversion (`inversion.direct.DirectInversion.trajectory`); after every step the source row (prompt 0) is
-        moved back onto it, in the launch of the CFG + DDIM update."""
+        moved back onto it, in the launch of the CFG + DDIM update.
+        noise_maps, skip (not reference arguments): edit-friendly DDPM inversion -- fp32 [S - skip, C, h, w] from
+        `inversion.ddpm.DDPMInversion.noise_maps`, `latent` = its y_skip; the edit runs `timesteps[skip:]` (the controller counts
+        them from 0), every step is the eta = 1 update with that step's map on every row, and `guidance_scale` may be a sequence
+        of one scale per prompt (the source prompt takes the scale the maps were extracted with)."""
         if source_trajectory is not None and uncond_embeddings_list is not None:
             raise ValueError("source_trajectory together with uncond_embeddings_list: choose Direct Inversion or null-text "
                              "embeddings, not both")
+        if noise_maps is not None:
+            if uncond_embeddings_list is not None or source_trajectory is not None:
+                raise ValueError("noise_maps together with uncond_embeddings_list or source_trajectory: choose ONE of DDPM inversion, "
+                                 "null-text embeddings and Direct Inversion")
+            if low_resource:
+                raise ValueError("noise_maps: the low_resource path (two half-batch forwards) is not built for DDPM inversion")
+            if cfg_split_group is not None:
+                raise ValueError("CFG split: edit-friendly DDPM inversion (noise_maps) is not built for the two-GPU split")
+        elif skip:
+            raise ValueError("skip: only an edit with noise maps starts inside the schedule")
+        elif isinstance(guidance_scale, (list, tuple)):
+            raise ValueError("guidance_scale: one scale per prompt needs noise_maps (the DDPM step takes a scale per batch row)")
         if cfg_split_group is not None:
             if source_trajectory is not None:
                 raise ValueError("CFG split: Direct Inversion (source_trajectory) is not built for the two-GPU split")
@@ -112,11 +129,23 @@ class P2P:
         if _fusable(model, controller, low_resource):
             loop = acquire(model, context, batch_size, (height // 8, width // 8), guidance_scale,
                                  uncond_list=uncond_embeddings_list, added_cond_kwargs=added_cond_kwargs,
-                                 source_trajectory=source_trajectory)
+                                 source_trajectory=source_trajectory, noise_maps=noise_maps, skip=skip)
             try:
                 latents = loop.run(latents)
             finally:
                 loop.release()
+        elif noise_maps is not None:
+            if added_cond_kwargs is not None:
+                raise ValueError("noise_maps: DDPM inversion is built for the SD1.x / SD2.x pipelines")
+            check_noise_maps(noise_maps, mode="denoise", cfg=True, uncond_list=None, source_trajectory=None,
+                             row_shape=tuple(latents.shape[1:]), num_steps=len(model.scheduler.timesteps), skip=skip,
+                             guidance_scale=guidance_scale, num_latents=batch_size)
+            step = torch.zeros(1, dtype=torch.int32, device=model.device)
+            g_rows = torch.tensor(guidance_rows(guidance_scale, batch_size), dtype=torch.float32, device=model.device)
+            ddpm = (noise_maps.to(model.device).contiguous(), g_rows, step)
+            for i, t in enumerate(tqdm(model.scheduler.timesteps[skip:], desc="Now doing P2P editing")):
+                step.fill_(i)               # the host's step index, where the captured loop reads its device counter
+                latents = self.diffusion_step(model, controller, latents, context, t, None, ddpm=ddpm)
         else:
             rect = None
             if source_trajectory is not None:
@@ -182,7 +211,9 @@ class P2P:
         """Several independent edits IN FLIGHT on one GPU (a throughput schedule the reference does not have: its
         drivers call `text2image_ldm_stable` once per image).  jobs: [(prompts, controller, latent x_T [1,4,h,w])] or
         [(prompts, controller, x_T, uncond_embeddings_list)] (null-text embeddings, as `P2P_NTI`) or
-        [(prompts, controller, x_T, None, source_trajectory)] (Direct Inversion, as `text2image_ldm_stable`);
+        [(prompts, controller, x_T, None, source_trajectory)] (Direct Inversion, as `text2image_ldm_stable`) or
+        [(prompts, controller, y_skip, None, None, (noise_maps, skip, guidance scales))] (edit-friendly DDPM inversion: the sixth
+        element; its scales, one per prompt or one number, replace `guidance_scale` for that job);
         every controller must be one of the lowered classes.  Each job's loop is captured while its controller is
         registered, then all loops are stepped in turn on their own streams (`denoise.run_interleaved`).  Returns
         [(images uint8 [len(prompts),H,W,3], x_T)] — the same values as one `text2image_ldm_stable` call per job."""
@@ -197,6 +228,9 @@ class P2P:
                 source_trajectory = job[4] if len(job) > 4 else None
                 if source_trajectory is not None and uncond_list is not None:
                     raise ValueError("edit_many: a job brings a source trajectory or null-text embeddings, not both")
+                noise_maps, skip, g_job = job[5] if len(job) > 5 and job[5] is not None else (None, 0, guidance_scale)
+                if noise_maps is not None and (uncond_list is not None or source_trajectory is not None):
+                    raise ValueError("edit_many: a job brings ONE of noise maps, a source trajectory and null-text embeddings")
                 register_attention_control(model, controller)
                 if not _fusable(model, controller, False):
                     raise RuntimeError("edit_many: only controllers lowered to a device plan can run concurrently")
@@ -204,8 +238,9 @@ class P2P:
                 uncond_embeddings, text_embeddings, added_cond_kwargs = self._encode(model, prompt, height, width)
                 latent, latents = self.init_latent(latent, model, height, width, None, len(prompt))
                 loop = acquire(model, torch.cat([uncond_embeddings, text_embeddings]), len(prompt),
-                                     (height // 8, width // 8), guidance_scale, uncond_list=uncond_list,
-                                     added_cond_kwargs=added_cond_kwargs, source_trajectory=source_trajectory)
+                                     (height // 8, width // 8), g_job, uncond_list=uncond_list,
+                                     added_cond_kwargs=added_cond_kwargs, source_trajectory=source_trajectory,
+                                     noise_maps=noise_maps, skip=skip)
                 loop.start(latents)
                 loops.append(loop)
                 firsts.append(latent)
@@ -218,10 +253,11 @@ class P2P:
                 loop.release()
 
     def diffusion_step(self, model, controller, latents, context, t, guidance_scale, low_resource=False,
-                       added_cond_kwargs=None, rect=None):
+                       added_cond_kwargs=None, rect=None, ddpm=None):
         """one eager step (`sd_utils.py:67-79`, XL: :175-186); CFG + DDIM update fused in one kernel.  rect = (trajectory, step):
         Direct Inversion's move of the source row in that kernel (`hip.cfg_ddim_step`), in front of the controller's callback as
-        in the captured step."""
+        in the captured step.  ddpm = (noise maps, g_rows, step): the eta = 1 update of an edit-friendly DDPM inversion edit instead
+        (`hip.cfg_ddpm_step`; guidance_scale is then unused), likewise in front of the callback."""
         latents = latents.float().contiguous()
         if low_resource:
             bp = latents.shape[0]
@@ -232,6 +268,11 @@ class P2P:
             eps = model.unet(torch.cat([latents] * 2), t, encoder_hidden_states=context,
                              added_cond_kwargs=added_cond_kwargs)["sample"]
             eps_u, eps_c = eps.chunk(2)
+        if ddpm is not None:
+            maps, g_rows, step = ddpm
+            coef = torch.tensor(model.scheduler.ddpm_coeffs(int(t)), dtype=torch.float32, device=latents.device)
+            latents = hip.cfg_ddpm_step(eps_u.contiguous(), eps_c.contiguous(), latents, coef, g_rows, maps, step)
+            return latents if controller is None else controller.step_callback(latents)
         a_t, a_p = model.scheduler.step_coeffs(int(t))
         coef = torch.tensor([a_t, a_p, float(guidance_scale)], dtype=torch.float32, device=latents.device)
         latents = hip.cfg_ddim_step(eps_u.contiguous(), eps_c.contiguous(), latents, coef, rect=rect)

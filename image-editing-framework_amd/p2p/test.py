@@ -22,6 +22,12 @@ UNet batch (`NTI.null_optimization_batched`: one optimiser and three graphs for 
 early stop) instead of `--in_flight` chains at batch 1; `--in_flight` keeps governing the edits.  Not for SDXL pipelines.
 `--inversion_type direct` (not a reference value): Direct Inversion -- the DDIM inversion, and every edit moves its source row back
 onto the stored trajectory after each step (`ief_amd.p2p.inversion.direct`); `--invert_batch` / `--in_flight` work as for `ddim`.
+`--inversion_type ddpm` (not a reference value): edit-friendly DDPM inversion (`ief_amd.p2p.inversion.ddpm`).  The inversion has no
+chain: `--invert_batch K` is the number of ROWS (timesteps of ONE image) per UNet launch, at CFG batch 2 K; `--in_flight` governs the
+edits as for `ddim`.  `--ddpm_guidance_src 3.5` / `--ddpm_guidance_tar 15` / `--skip 18` (36 % of the 50 steps) are the paper's
+settings; image i of a shard draws its noise from a CPU generator seeded `--seed` + i, whatever the schedule.  `--in_flight` does not
+change the pixels; K is part of the numerics in the fp32-storage modes (a batched forward equals batch-1 forwards to 1e-6 of eps, as
+for the batched DDIM inversion).  Not for SDXL pipelines.
 """
 import argparse
 import json
@@ -33,10 +39,11 @@ from PIL import Image
 
 from _bootstrap import load_pipe, seed_everything
 
-from edit_real import edit_latent, edit_one
+from edit_real import XL_VERSIONS, add_ddpm_arguments, check_ddpm_arguments, ddpm_invert, edit_latent, edit_one
 from ief_amd.p2p.model.attention_control import AttentionRefine, AttentionReplace
 from ief_amd.p2p.dataset.pie import PIE, SyntheticPIE
 from ief_amd.p2p.inversion.ddim import ddim_inversion, ddim_inversion_xl
+from ief_amd.p2p.inversion.ddpm import DDPMInversion
 from ief_amd.p2p.inversion.direct import DirectInversion, DirectInversion_XL
 from ief_amd.p2p.inversion.nti import NTI, NTI_XL
 from ief_amd.p2p.model.sd_utils import P2P, P2P_NTI, P2P_XL, P2P_XL_NTI
@@ -55,11 +62,12 @@ def edit_type_of(source_prompt: str, target_prompt: str) -> str:
 
 
 def run_items(pipe, editor, invertor, items, size, device, inversion_type="ddim", invert_batch=1, in_flight=1, save=None,
-              nti_batch=1):
+              nti_batch=1, ddpm=None):
     """the per-image loop of `/root/reference/p2p/test.py:116-181` over `items` = [(image path, source prompt, target
     prompt)]; `save(image_path, original PIL image, uint8 images [2,H,W,3])` is called per image.  invert_batch /
     in_flight = 1 is the reference's order (invert one image, edit it, next); see the module docstring for the others.
     nti_batch > 1: the null-text optimisations run in groups of nti_batch through one batched optimiser.
+    ddpm: `edit_real.check_ddpm_arguments`' dict for inversion_type "ddpm" (`_run_ddpm_chunk`; invert_batch is then its rows per launch).
     Also what `bench.py` times for its images/sec figures."""
     save = save or (lambda *a: None)
     nti = inversion_type == "null-text"
@@ -67,7 +75,7 @@ def run_items(pipe, editor, invertor, items, size, device, inversion_type="ddim"
     bs = max(1, invert_batch)
     E = max(1, in_flight)
     nb = max(1, nti_batch) if nti else 1
-    group = max(bs, E, nb)
+    group = max(bs, E, nb) if ddpm is None else E
     try:
         for c0 in range(0, len(items), group):
             chunk = items[c0:c0 + group]
@@ -75,8 +83,13 @@ def run_items(pipe, editor, invertor, items, size, device, inversion_type="ddim"
             if group == 1:
                 image_path, source_prompt, target_prompt = chunk[0]
                 images = edit_one(pipe, editor, invertor, originals[0], [source_prompt], [target_prompt], inversion_type,
-                                  edit_type_of(source_prompt, target_prompt), device)
+                                  edit_type_of(source_prompt, target_prompt), device,
+                                  ddpm=None if ddpm is None else dict(ddpm, seed=ddpm["seed"] + c0))
                 save(image_path, originals[0], images)
+                continue
+            if ddpm is not None:
+                for j, images in enumerate(_run_ddpm_chunk(pipe, editor, invertor, chunk, originals, device, ddpm, c0)):
+                    save(chunk[j][0], originals[j], images)
                 continue
             # inversion: batched over `bs` images at a time (the DDIM loop is the same for both inversion types)
             traj, ctxs = [], []
@@ -132,7 +145,24 @@ def run_items(pipe, editor, invertor, items, size, device, inversion_type="ddim"
             invertor.release_batched()          # the optimiser that served every group of this run
 
 
-XL_VERSIONS = ("xl-base", "smallxl")       # the `StableDiffusionXLPipeline` branch of `_bootstrap._build_pipe`
+def _run_ddpm_chunk(pipe, editor, invertor, chunk, originals, device, ddpm, first_index):
+    """edit-friendly DDPM inversion of the images of `chunk` (one after the other: every image fills its own UNet batches), then
+    their edits in flight through `P2P.edit_many` -> [uint8 images [2,H,W,3]] per image, those of `edit_one` on each"""
+    S, skip = 50, ddpm["skip"]
+    jobs, ctrls = [], []
+    for j, ((_, src, tgt), im) in enumerate(zip(chunk, originals)):
+        latent = invertor.image2latent(model=pipe, image=im, device=device, dtype=torch.float32)
+        y_skip, maps = ddpm_invert(pipe, invertor, latent, [src], S, dict(ddpm, seed=ddpm["seed"] + first_index + j))
+        cls = AttentionReplace if edit_type_of(src, tgt) == "replace" else AttentionRefine
+        ctrl = cls(prompts=[src, tgt], tokenizer=pipe.tokenizer, num_steps=S - skip, cross_replace_steps=0.8,
+                   self_replace_steps=0.6, device=device)
+        ctrls.append(ctrl)
+        jobs.append(([src, tgt], ctrl, y_skip, None, None, (maps, skip, (ddpm["guidance_src"], ddpm["guidance_tar"]))))
+    results = [im for im, _ in editor.edit_many(pipe, jobs, num_inference_steps=S)]
+    for ctrl in ctrls:
+        ctrl.reset()
+    return results
+
 
 
 def parse_args(argv=None):
@@ -143,7 +173,8 @@ def parse_args(argv=None):
     ap.add_argument("--inversion_type", type=str, default="ddim")
     ap.add_argument("--synthetic", type=int, default=0, help="use N generated images instead of ./PIE")
     ap.add_argument("--no_save", action="store_true")
-    ap.add_argument("--invert_batch", type=int, default=1, help="images inverted per batched DDIM loop")
+    ap.add_argument("--invert_batch", type=int, default=1, help="images inverted per batched DDIM loop; with --inversion_type ddpm: rows (timesteps) of one image per UNet launch, "
+                         "at CFG batch 2 K (8 measured fastest on SD1.5)")
     ap.add_argument("--precision", type=str, default=os.environ.get("IEF_PRECISION", "f16x3"), choices=["f16", "f32", "f16x3"],
                     help="f16x3 (default): fp32 storage, contractions on split fp16 operands -- the reference's fp32 images to 4e-6; "
                          "f32: the same on the fp32-input MFMA; f16: fp16 storage, 2.5x faster, images within 2 grey levels")
@@ -154,7 +185,10 @@ def parse_args(argv=None):
                     help="independent images stepped concurrently on one GPU (null-text optimisations and edits)")
     ap.add_argument("--nti_batch", type=int, default=1,
                     help="null-text optimisations per UNet batch (1: per image, --in_flight of them at a time); not for SDXL")
+    ap.add_argument("--seed", type=int, default=42, help="global seed; with --inversion_type ddpm also the seed of the maps' noise")
+    add_ddpm_arguments(ap)
     args = ap.parse_args(argv)
+    args.ddpm = check_ddpm_arguments(ap, args, args.nti_batch)
     if args.nti_batch < 1:
         ap.error("--nti_batch must be >= 1")
     if args.nti_batch > 1 and args.inversion_type == "direct":
@@ -175,7 +209,7 @@ def main(argv=None):
     if world > 1:
         from _bootstrap import init_distributed
         dist = init_distributed(device)       # rank 0 loads the weights; `load_pipe` broadcasts them (RCCL over xGMI)
-    seed_everything(42)
+    seed_everything(args.seed)
     pipe = load_pipe(args.sd_version, device, precision=args.precision, attn_key_splits=args.attn_key_splits)
     xl = pipe.__class__.__name__ == "StableDiffusionXLPipeline"          # dispatch of test.py:86-104
     if args.inversion_type == "ddim":
@@ -187,6 +221,9 @@ def main(argv=None):
     elif args.inversion_type == "direct":
         editor = (P2P_XL if xl else P2P)(model=pipe, num_inference_steps=50)
         invertor = DirectInversion_XL() if xl else DirectInversion()
+    elif args.inversion_type == "ddpm":
+        editor = P2P(model=pipe, num_inference_steps=50)
+        invertor = DDPMInversion()
     else:
         raise ValueError("Please choose right inversion type")
     size = pipe.unet.config.sample_size * pipe.vae_scale_factor
@@ -216,7 +253,7 @@ def main(argv=None):
             writer.save_img(images[1], os.path.join(out_path, "edit.png"))
 
         run_items(pipe, editor, invertor, [items[i] for i in mine], size, device, args.inversion_type, args.invert_batch,
-                  args.in_flight, save, nti_batch=args.nti_batch)
+                  args.in_flight, save, nti_batch=args.nti_batch, ddpm=args.ddpm)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     n = torch.tensor([float(len(mine)), dt], device=device)

@@ -87,6 +87,17 @@ class DDIMScheduler:
         a_c = float(self.alphas_cumprod[cur]) if cur >= 0 else float(self.final_alpha_cumprod)
         return a_c, float(self.alphas_cumprod[nxt])
 
+    def ddpm_coeffs(self, t: int):
+        """(a_t, a_prev, sigma, dir) of the eta = 1 step at timestep t (edit-friendly DDPM inversion, `p2p.inversion.ddpm`):
+            v = (1 - a_prev) / (1 - a_t) * (1 - a_t / a_prev);  sigma = sqrt(v);  dir = sqrt(1 - a_prev - v)
+        a_t / a_prev are `step_coeffs`' fp32 table values; sigma and dir are formed here in fp64 and rounded to fp32 (returned as
+        python floats that hold fp32 values), so dir^2 + sigma^2 = 1 - a_prev to fp32 rounding.  v is clamped at 0 from below and
+        1 - a_prev - v likewise: a step with sigma == 0 adds no noise."""
+        a_t, a_p = self.step_coeffs(t)
+        v = max(0.0, (1.0 - a_p) / (1.0 - a_t) * (1.0 - a_t / a_p))
+        d = max(0.0, 1.0 - a_p - v)
+        return a_t, a_p, float(np.float32(np.sqrt(v))), float(np.float32(np.sqrt(d)))
+
     @staticmethod
     def linear_form(a_from: float, a_to: float):
         """x' = cx * x + ce * eps  for  x0=(x-sqrt(1-a_from)eps)/sqrt(a_from); x'=sqrt(a_to)x0+sqrt(1-a_to)eps.

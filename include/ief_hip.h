@@ -207,6 +207,27 @@ int ief_cfg_ddim_step_f32(const float* eps_u, const float* eps_c, const float* x
 int ief_cfg_ddim_step_rect_f32(const float* eps_u, const float* eps_c, const float* x, float* x_out, float* x0_out,
                                const float* coef, long long n, long long row_elems,
                                const float* traj, int traj_rows, const int* step, void* stream);
+/* Edit-friendly DDPM inversion (Huberman-Spiegelglas, Kulikov, Michaeli, "An Edit Friendly DDPM Noise Space"): CFG with one
+ * guidance scale PER BATCH ROW and the eta = 1 update with a stored noise row, in one launch.  For element i of row b = i / row_elems:
+ *   eps = eps_u + g_rows[b] (eps_c - eps_u);  x0 = (x - sqrt(1 - a_from) eps) / sqrt(a_from)
+ *   mu  = sqrt(a_to) x0 + dir eps;            x_out = mu + sigma z,   z = noise[min(max(step[0], 0), noise_rows - 1)][i - b row_elems]
+ * every operation rounded in fp32; sigma == 0 gives x_out = mu (the noise is not read into the result), and with dir = the fp32
+ * sqrt(1 - a_to) that is ief_cfg_ddim_step_f32's x_out and x0_out bit for bit.  Every batch row reads the same noise row.
+ * coef: DEVICE fp32 [4] = {a_from, a_to, sigma, dir}; g_rows: DEVICE fp32 [n / row_elems]; noise: DEVICE fp32 [noise_rows][row_elems];
+ * step: DEVICE int32 [1], read by the kernel and clamped as ief_select_step clamps it.  eps_u == NULL: eps = eps_c, g_rows may be
+ * NULL.  x0_out optional (the x0 prediction); x_out == x allowed.
+ * IEF_EINVAL: a null eps_c / x / x_out / coef / noise / step, or eps_u without g_rows; IEF_ESHAPE: n <= 0, row_elems <= 0,
+ * n % row_elems != 0, noise_rows <= 0. */
+int ief_cfg_ddpm_step_f32(const float* eps_u, const float* eps_c, const float* x, float* x_out, float* x0_out, const float* coef,
+                          const float* g_rows, long long n, long long row_elems,
+                          const float* noise, int noise_rows, const int* step, void* stream);
+/* the extraction of the noise maps, R rows at R different timesteps in one launch: with mu as above (the same device function, so
+ * the same bits) from row r of x_t and coef_rows[r],  z_out[r] = (x_prev[r] - mu) / sigma_r;  sigma_r == 0 gives a zero row.
+ * coef_rows: DEVICE fp32 [R][5] = {a_from, a_to, sigma, dir, g}: the guidance scale of a row is its fifth column (one scale per
+ * row, as there is one timestep per row).  eps_u == NULL: eps = eps_c.  All tensors fp32 [R][row_elems].
+ * IEF_EINVAL: a null eps_c / x_t / x_prev / z_out / coef_rows; IEF_ESHAPE: R <= 0, row_elems <= 0. */
+int ief_ddpm_noise_maps_f32(const float* eps_u, const float* eps_c, const float* x_t, const float* x_prev, float* z_out,
+                            const float* coef_rows, int R, long long row_elems, void* stream);
 /* sinusoidal timestep embedding, flip_sin_to_cos, shift 0: out fp16 [B][dim] = [cos | sin] */
 int ief_timestep_embedding_f16(const float* t, ief_half* out, int B, int dim, void* stream);
 /* out = a + b elementwise on fp16 (residual add when a hook owns Attention.forward) */
