@@ -75,6 +75,53 @@ extern "C" int ief_cfg_ddim_step_rect_f32(const float* eps_u, const float* eps_c
     return IEF_OK;
 }
 
+// DiffEdit (Couairon et al.): the same step, and EVERY batch row keeps x' only where its own binary mask is set; elsewhere the element
+// is put back onto the stored inversion trajectory:  x_out = mask[b][p] != 0 ? x' : z[c][p],  z = traj[clamp(step[0], 0, traj_rows - 1)],
+// for element i = (b row_elems + c hw + p).  A select: inside the mask the plain step's bits, outside the trajectory's.  x0_out is the
+// un-masked x0 prediction.  Launches of the sampler stay far below 2^32 elements, where 32-bit divisions do.
+__global__ __launch_bounds__(256) void cfg_ddim_masked_kernel(const float* __restrict__ eu, const float* __restrict__ ec,
+                                                              const float* __restrict__ x, float* __restrict__ xo,
+                                                              float* __restrict__ x0o, const float* __restrict__ coef,
+                                                              long long n, long long row_elems, long long hw,
+                                                              const float* __restrict__ traj, int traj_rows,
+                                                              const int* __restrict__ step, const float* __restrict__ mask) {
+    const DdimCoef c = ddim_coef(coef);
+    int row = step[0];
+    row = row < 0 ? 0 : (row >= traj_rows ? traj_rows - 1 : row);
+    const float* __restrict__ z = traj + (long long)row * row_elems;
+    const bool small = n <= 0xffffffffll;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+        long long b, e, p;                   // batch row, element of the row, pixel
+        if (small) {
+            b = (unsigned)i / (unsigned)row_elems;
+            e = (unsigned)i - (unsigned)b * (unsigned)row_elems;
+            p = (unsigned)e % (unsigned)hw;
+        } else {
+            b = i / row_elems;
+            e = i - b * row_elems;
+            p = e % hw;
+        }
+        const float xp = cfg_ddim_elem(c, eu, ec, x, x0o, i);
+        xo[i] = mask[b * hw + p] != 0.0f ? xp : z[e];
+    }
+}
+
+extern "C" int ief_cfg_ddim_step_masked_f32(const float* eps_u, const float* eps_c, const float* x, float* x_out, float* x0_out,
+                                            const float* coef, long long n, long long row_elems, long long hw, const float* traj,
+                                            int traj_rows, const int* step, const float* mask, void* stream) {
+    if (!eps_c || !x || !x_out || !coef || !traj || !step || !mask) return IEF_EINVAL;
+    if (n <= 0 || row_elems <= 0 || n % row_elems != 0 || hw <= 0 || row_elems % hw != 0 || traj_rows <= 0) return IEF_ESHAPE;
+    if (((uintptr_t)eps_u | (uintptr_t)eps_c | (uintptr_t)x | (uintptr_t)x_out | (uintptr_t)x0_out | (uintptr_t)coef | (uintptr_t)traj |
+         (uintptr_t)step | (uintptr_t)mask) & 3)
+        return IEF_EALIGN;
+    int grid = (int)((n + 255) / 256);
+    if (grid > 2048) grid = 2048;
+    hipLaunchKernelGGL(cfg_ddim_masked_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, eps_u, eps_c, x, x_out, x0_out, coef, n,
+                       row_elems, hw, traj, traj_rows, step, mask);
+    IEF_LAUNCH_CHECK();
+    return IEF_OK;
+}
+
 // Edit-friendly DDPM inversion (Huberman-Spiegelglas et al., "An Edit Friendly DDPM Noise Space"): the eta = 1 update
 //   eps = eps_u + g (eps_c - eps_u);  x0 = (x - sqrt(1-a_f) eps) / sqrt(a_f);  mu = sqrt(a_t) x0 + dir eps;  x' = mu + sigma z
 // with sigma and dir = sqrt(1 - a_t - sigma^2) handed in (the host forms them in fp64), and its inverse z = (x_prev - mu) / sigma.

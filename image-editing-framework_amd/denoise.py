@@ -11,6 +11,7 @@ overhead would exceed the GPU time.  Here the whole step is captured once:
     latents -> CFG batch copy -> UNet (fused attention control) -> fused CFG + DDIM update (in place)
     [Direct Inversion: the same launch moves the source row (row 0) back onto the stored inversion trajectory]
     [edit-friendly DDPM inversion: CFG with a scale per batch row + the eta = 1 update with the stored noise map of this step instead]
+    [DiffEdit: the same launch puts every row back onto the stored inversion trajectory outside that row's edit mask]
     [P2P plan with a LocalBlend: the word-masked blend of the updated latents, in place]
     advance_step
 (on the f16x3 planes trunk the UNet takes the latents themselves and runs what both halves of the CFG batch share once: no copy;
@@ -149,11 +150,48 @@ def check_noise_maps(maps, *, mode, cfg, uncond_list, source_trajectory, row_sha
         guidance_rows(guidance_scale, num_latents)
 
 
+def check_edit_mask(mask, *, mode, cfg, uncond_list, noise_maps, source_trajectory, row_shape, num_steps, skip, num_latents):
+    """the argument checks of a DiffEdit loop (host-side facts only; raises ValueError): `mask` is fp32 or bool [Bp, h, w] (or
+    [h, w], shared by every row), nonzero = edited; `source_trajectory` is fp32 [S - skip, C, h, w] with row i = z*_{S-skip-1-i}, the
+    latent every row must hold OUTSIDE its mask after edit step i, which runs timestep `timesteps[skip + i]`"""
+    if mode != "denoise":
+        raise ValueError(f"edit_mask: only a denoising loop keeps its background on the inversion trajectory (mode={mode!r})")
+    if not cfg:
+        raise ValueError("edit_mask: DiffEdit decodes under classifier-free guidance; a loop without guidance has no masked step")
+    if uncond_list is not None:
+        raise ValueError("edit_mask together with uncond_list: choose DiffEdit or null-text embeddings, not both")
+    if noise_maps is not None:
+        raise ValueError("edit_mask together with noise_maps: choose DiffEdit or DDPM inversion, not both")
+    if not isinstance(skip, int) or isinstance(skip, bool) or not 0 <= skip < num_steps:
+        raise ValueError(f"edit_mask: skip must be an integer in [0, {num_steps}), got {skip!r}")
+    if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.float32, torch.bool):
+        raise ValueError("edit_mask: expected one fp32 or bool tensor [Bp, h, w] (or [h, w] for every row)")
+    hw = tuple(row_shape[-2:])
+    if tuple(mask.shape) not in (hw, (num_latents, *hw)):
+        raise ValueError(f"edit_mask: shape {tuple(mask.shape)} for {num_latents} latents of {hw[0]} x {hw[1]}")
+    if source_trajectory is None:
+        raise ValueError("edit_mask: needs the source_trajectory the background is put back onto")
+    if not isinstance(source_trajectory, torch.Tensor) or source_trajectory.dtype != torch.float32:
+        raise ValueError("edit_mask: source_trajectory is one fp32 tensor [steps - skip, C, h, w]")
+    if tuple(source_trajectory.shape[1:]) != tuple(row_shape) or source_trajectory.dim() != 1 + len(row_shape):
+        raise ValueError(f"edit_mask: trajectory rows of shape {tuple(source_trajectory.shape[1:])} for latents of shape "
+                         f"{tuple(row_shape)}")
+    if source_trajectory.shape[0] != num_steps - skip:
+        raise ValueError(f"edit_mask: {source_trajectory.shape[0]} trajectory rows for a schedule of {num_steps} steps with skip {skip} "
+                         f"({num_steps - skip} edit steps)")
+
+
+def _mask_rows(mask, num_latents, device):
+    """the device buffer of an edit mask: fp32 [Bp, h, w], one mask per batch row"""
+    m = mask.to(device).float()
+    return (m[None].expand(num_latents, -1, -1) if m.dim() == 2 else m).contiguous().clone()
+
+
 class FusedDenoiser:
     def __init__(self, model, context: torch.Tensor, num_latents: int, latent_hw, guidance_scale: Optional[float],
                  mode: str = "denoise", uncond_list: Optional[List[torch.Tensor]] = None, use_graph: bool = True,
                  added_cond_kwargs=None, source_trajectory: Optional[torch.Tensor] = None,
-                 noise_maps: Optional[torch.Tensor] = None, skip: int = 0):
+                 noise_maps: Optional[torch.Tensor] = None, skip: int = 0, edit_mask: Optional[torch.Tensor] = None):
         """context: [2*Bp,77,C] (uncond, cond) for mode 'denoise' with CFG, [Bp,77,C] for 'invert' / no-CFG.
         added_cond_kwargs: SDXL's {"text_embeds" [B, 1280], "time_ids" [B, 6]} (one row per UNet batch row); they are
         constant over the steps, so they fold into the per-step time-embedding rows (then one row PER BATCH ROW).
@@ -162,12 +200,21 @@ class FusedDenoiser:
         noise_maps, skip: edit-friendly DDPM inversion -- fp32 [S - skip, C, h, w], the maps of `p2p.inversion.ddpm.DDPMInversion`; the
         loop runs the S - skip timesteps `timesteps[skip:]` from y_skip, step i is the eta = 1 update with map i (every batch row
         reads the same map), and `guidance_scale` may be a sequence of one scale per latent (the source row takes the scale its
-        maps were extracted with)."""
+        maps were extracted with).
+        edit_mask, source_trajectory, skip: DiffEdit -- fp32 or bool [Bp, h, w] (or [h, w]), nonzero = edited, with the trajectory of
+        a PARTIAL inversion, fp32 [S - skip, C, h, w], row i = z*_{S-skip-1-i}; the loop runs `timesteps[skip:]` from z*_{S-skip} and
+        after step i every row is x' inside its mask and the trajectory row outside it (a select, in the launch of the update)."""
         self.model, self.unet, self.sched = model, model.unet, model.scheduler
         dev = self.unet.device
         self.mode = mode
         self.cfg = guidance_scale is not None
-        if source_trajectory is not None:
+        if edit_mask is not None:
+            check_edit_mask(edit_mask, mode=mode, cfg=self.cfg, uncond_list=uncond_list, noise_maps=noise_maps,
+                            source_trajectory=source_trajectory, row_shape=(self.unet.config.in_channels, *latent_hw),
+                            num_steps=len(self.sched.timesteps), skip=skip, num_latents=num_latents)
+            if added_cond_kwargs is not None:
+                raise ValueError("edit_mask: DiffEdit is built for the SD1.x / SD2.x pipelines (no added_cond_kwargs)")
+        elif source_trajectory is not None:
             check_source_trajectory(source_trajectory, mode=mode, cfg=self.cfg, uncond_list=uncond_list,
                                     row_shape=(self.unet.config.in_channels, *latent_hw), num_steps=len(self.sched.timesteps))
         if noise_maps is not None:
@@ -176,9 +223,9 @@ class FusedDenoiser:
                              guidance_scale=guidance_scale, num_latents=num_latents)
             if added_cond_kwargs is not None:
                 raise ValueError("noise_maps: DDPM inversion is built for the SD1.x / SD2.x pipelines (no added_cond_kwargs)")
-        elif skip:
+        elif skip and edit_mask is None:
             raise ValueError("skip: only a loop with noise maps starts inside the schedule")
-        self.skip = skip if noise_maps is not None else 0
+        self.skip = skip if (noise_maps is not None or edit_mask is not None) else 0
         self.Bp = num_latents
         self.B = 2 * num_latents if self.cfg else num_latents
         if context.shape[0] != self.B:
@@ -203,6 +250,8 @@ class FusedDenoiser:
         # likewise the noise maps and the per-row guidance scales of a DDPM inversion edit
         self.maps = None if noise_maps is None else noise_maps.to(dev).contiguous().clone()
         self.g_rows = None
+        # and the edit masks of a DiffEdit loop, one per batch row
+        self.mask = None if edit_mask is None else _mask_rows(edit_mask, num_latents, dev)
         self._fill(context, guidance_scale, uncond_list, added_cond_kwargs)
         self.use_graph = use_graph
         self.graph = None
@@ -221,6 +270,8 @@ class FusedDenoiser:
             ts = ts[self.skip:]
             coef = [self.sched.ddpm_coeffs(t) for t in ts]
         else:
+            if self.mask is not None:       # DiffEdit decodes the tail of the schedule
+                ts = ts[self.skip:]
             coef = [self.sched.step_coeffs(t) for t in ts]
         g = float(guidance_scale) if self.cfg and self.maps is None else 1.0
         self.num_steps = len(ts)
@@ -268,18 +319,26 @@ class FusedDenoiser:
         return cfg_shared_prefix_reason(mode=self.mode, cfg=self.cfg, enabled=CFG_SHARED_PREFIX and type(self)._step_body is FusedDenoiser._step_body,
                                         **facts(tuple(self.lat.shape[-2:]), ctx_len))
 
-    def _key(self, context, uncond_list, source_trajectory=None, noise_maps=None, skip=0):
+    def _key(self, context, uncond_list, source_trajectory=None, noise_maps=None, skip=0, edit_mask=None):
         plan = self.unet._plan
         return (id(self.unet), self.mode, self.Bp, tuple(self.lat.shape[-2:]), self.cfg, tuple(context.shape),
                 None if uncond_list is None else len(uncond_list), len(self.sched.timesteps),
                 None if plan is None else plan.signature(self.unet), self._shared_reason(context.shape[1]) is None,
-                source_trajectory is not None, noise_maps is not None, skip if noise_maps is not None else 0,
-                getattr(self.unet, "attn_key_splits", 1))
+                edit_mask is not None, source_trajectory is not None, noise_maps is not None,
+                skip if (noise_maps is not None or edit_mask is not None) else 0, getattr(self.unet, "attn_key_splits", 1))
 
     def rebind(self, context, guidance_scale, uncond_list, added_cond_kwargs=None, source_trajectory=None, noise_maps=None,
-               skip=0):
+               skip=0, edit_mask=None):
         """point a captured loop at the next image: new tables, new cross-attention K/V, the new controller's plan, the next
-        image's inversion trajectory or noise maps and guidance scales"""
+        image's inversion trajectory or noise maps and guidance scales, or its edit masks"""
+        if (edit_mask is None) != (self.mask is None) or (edit_mask is not None and skip != self.skip):
+            raise ValueError("rebind: a loop captured with an edit mask serves only jobs that bring a mask and the same skip, and the "
+                             "reverse")
+        if edit_mask is not None:
+            check_edit_mask(edit_mask, mode=self.mode, cfg=self.cfg, uncond_list=uncond_list, noise_maps=noise_maps,
+                            source_trajectory=source_trajectory, row_shape=tuple(self.lat.shape[1:]),
+                            num_steps=len(self.sched.timesteps), skip=skip, num_latents=self.Bp)
+            self.mask.copy_(_mask_rows(edit_mask, self.Bp, self.mask.device))
         if (noise_maps is None) != (self.maps is None) or (noise_maps is not None and skip != self.skip):
             raise ValueError("rebind: a loop captured with noise maps serves only jobs that bring maps of the same skip, and the reverse")
         if noise_maps is not None:
@@ -290,8 +349,9 @@ class FusedDenoiser:
         if (source_trajectory is None) != (self.traj is None):
             raise ValueError("rebind: a loop captured with a source trajectory serves only jobs that bring one, and the reverse")
         if source_trajectory is not None:
-            check_source_trajectory(source_trajectory, mode=self.mode, cfg=self.cfg, uncond_list=uncond_list,
-                                    row_shape=tuple(self.lat.shape[1:]), num_steps=len(self.sched.timesteps))
+            if edit_mask is None:
+                check_source_trajectory(source_trajectory, mode=self.mode, cfg=self.cfg, uncond_list=uncond_list,
+                                        row_shape=tuple(self.lat.shape[1:]), num_steps=len(self.sched.timesteps))
             self.traj.copy_(source_trajectory)
         self._fill(context, guidance_scale, uncond_list, added_cond_kwargs)
         if self.ctx_table is None:          # K/V of the fixed context live in tensors the graph reads: refresh in place, by the
@@ -323,6 +383,9 @@ class FusedDenoiser:
             eps = self.unet(self.lat_in, encoder_hidden_states=self.ctx, temb_row=self.temb_cur)["sample"]
         if self.maps is not None:
             hip.cfg_ddpm_step(eps[: self.Bp], eps[self.Bp:], self.lat, self.coef_cur, self.g_rows, self.maps, self.step, out=self.lat)
+        elif self.mask is not None:
+            hip.cfg_ddim_step(eps[: self.Bp], eps[self.Bp:], self.lat, self.coef_cur, out=self.lat,
+                              masked=(self.traj, self.step, self.mask))
         elif self.cfg:
             hip.cfg_ddim_step(eps[: self.Bp], eps[self.Bp:], self.lat, self.coef_cur, out=self.lat,
                               rect=None if self.traj is None else (self.traj, self.step))
@@ -477,7 +540,9 @@ class CfgSplitDenoiser(FusedDenoiser):
     (`p2p.model.register.register_attention_control`); its counters advance on both."""
 
     def __init__(self, model, context, num_latents, latent_hw, guidance_scale: float, group=None, uncond_list=None,
-                 use_graph: bool = True, source_trajectory=None, noise_maps=None, skip=0):
+                 use_graph: bool = True, source_trajectory=None, noise_maps=None, skip=0, edit_mask=None):
+        if edit_mask is not None:
+            raise ValueError("CFG split: DiffEdit (edit_mask) is not built for the two-GPU split; run the edit on one GPU")
         if noise_maps is not None or skip:
             raise ValueError("CFG split: edit-friendly DDPM inversion (noise_maps) is not built for the two-GPU split; run the edit "
                              "on one GPU")
@@ -583,28 +648,30 @@ class CfgSplitDenoiser(FusedDenoiser):
 
 
 def acquire(model, context, num_latents, latent_hw, guidance_scale, mode="denoise", uncond_list=None,
-            use_graph=True, added_cond_kwargs=None, source_trajectory=None, noise_maps=None, skip=0) -> FusedDenoiser:
+            use_graph=True, added_cond_kwargs=None, source_trajectory=None, noise_maps=None, skip=0,
+            edit_mask=None) -> FusedDenoiser:
     """a FusedDenoiser for this job: a pooled one with a captured graph of the same shape / plan signature, re-pointed
     at the new context, tables and controller — or a new one.  source_trajectory: Direct Inversion (`FusedDenoiser`); loops
     with and without one never share a pool entry.  noise_maps, skip: edit-friendly DDPM inversion (`FusedDenoiser`;
-    guidance_scale may then be one scale per latent); presence of maps and skip are part of the pool key"""
+    guidance_scale may then be one scale per latent); presence of maps and skip are part of the pool key.  edit_mask (with
+    source_trajectory and skip): DiffEdit (`FusedDenoiser`); loops with and without a mask never share a pool entry"""
     if REUSE_GRAPHS and use_graph:
         probe = FusedDenoiser.__new__(FusedDenoiser)
         probe.unet, probe.sched, probe.mode = model.unet, model.scheduler, mode
         probe.cfg, probe.Bp = guidance_scale is not None, num_latents
         probe.lat = torch.empty(0, 0, *latent_hw)
-        key = probe._key(context, uncond_list, source_trajectory, noise_maps, skip)
+        key = probe._key(context, uncond_list, source_trajectory, noise_maps, skip, edit_mask)
         free = _POOL.get(key)
         if free:
             loop = free.pop()
-            loop.rebind(context, guidance_scale, uncond_list, added_cond_kwargs, source_trajectory, noise_maps, skip)
+            loop.rebind(context, guidance_scale, uncond_list, added_cond_kwargs, source_trajectory, noise_maps, skip, edit_mask)
             return loop
         loop = FusedDenoiser(model, context, num_latents, latent_hw, guidance_scale, mode, uncond_list, use_graph,
-                             added_cond_kwargs, source_trajectory, noise_maps, skip)
+                             added_cond_kwargs, source_trajectory, noise_maps, skip, edit_mask)
         loop._pool_key = key
         return loop
     return FusedDenoiser(model, context, num_latents, latent_hw, guidance_scale, mode, uncond_list, use_graph,
-                         added_cond_kwargs, source_trajectory, noise_maps, skip)
+                         added_cond_kwargs, source_trajectory, noise_maps, skip, edit_mask)
 
 
 def drop_pool():

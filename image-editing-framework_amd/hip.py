@@ -371,6 +371,37 @@ def heuristic_plan(M: int, N: int, K: int):
     return tile, splits
 
 
+# ---- plans that do not follow the batch ---------------------------------------------------------------
+# Tile, split-K count and kernel family of the fp16-storage front-end follow M = batch rows x tokens, and another split count sums K in
+# another order: the same row gives other last bits (of fp16 roundings) in a launch of another batch.  Inside `plans_per_row(rows)` a
+# launch whose M is a multiple of `rows` is planned as ONE of its rows is planned (M / rows): every row then runs the arithmetic of a
+# batch-1 launch whatever the batch.  The plan is that of the small shape, so this costs speed; for passes whose result must not
+# depend on how their rows are chunked over launches (`DiffEdit.infer_mask`).
+_PLAN_ROWS = 1
+
+
+class plans_per_row:
+    def __init__(self, rows: int):
+        if not isinstance(rows, int) or rows < 1:
+            raise ValueError(f"plans_per_row: rows must be a positive integer, got {rows!r}")
+        self.rows = rows
+
+    def __enter__(self):
+        global _PLAN_ROWS
+        self.saved, _PLAN_ROWS = _PLAN_ROWS, self.rows
+        return self
+
+    def __exit__(self, *exc):
+        global _PLAN_ROWS
+        _PLAN_ROWS = self.saved
+        return False
+
+
+def _plan_m(M: int) -> int:
+    """the M a launch of M rows is planned for (`plans_per_row`)"""
+    return M // _PLAN_ROWS if _PLAN_ROWS > 1 and M % _PLAN_ROWS == 0 else M
+
+
 def pick_plan(M: int, N: int, K: int, conv: bool = False, variant: str = ""):
     """(tile, splits, stages); `variant` ("|u": the convolution with the fused nearest-2x upsample) has its own table key
     and falls back to the plain key of the same (M, N, K)"""
@@ -877,9 +908,10 @@ def gemm(a, w, bias=None, residual=None, rowvec=None, rows_per_batch=0, out=None
                                                                       out_scale=out_scale, tile_hint=t, splits=sp, stages=st,
                                                                       geglu=geglu))
             del wc
-        p.tile_hint, p.splits, p.stages = pick_plan(M, N, K)
+        Mp = _plan_m(M)
+        p.tile_hint, p.splits, p.stages = pick_plan(Mp, N, K)
         if (geglu or ln is not None or row_stats) and p.splits > 1:
-            p.tile_hint, p.splits, p.stages = heuristic_plan(M, N, K)[0], 1, 2
+            p.tile_hint, p.splits, p.stages = heuristic_plan(Mp, N, K)[0], 1, 2
     else:
         p.tile_hint, p.splits, p.stages = tile_hint, max(1, splits), stages
     ws = _fill_epilogue(p, _rows_ld, "gemm", M, N, a.device, bias, rowvec, rows_per_batch, residual, p.splits)
@@ -941,13 +973,14 @@ def conv3x3(x, w, bias=None, x2=None, stride=1, upsample=False, rowvec=None, res
                                                                             splits=sp, extra=extra, stages=st,
                                                                             pad_hi_only=pad_hi_only), variant=variant)
             del wc
-        p.tile_hint, p.splits, p.stages = pick_plan(M, Cout, K, conv=True, variant=variant)
+        Mp = _plan_m(M)
+        p.tile_hint, p.splits, p.stages = pick_plan(Mp, Cout, K, conv=True, variant=variant)
         halo_ok = g.halo_geom
-        if halo_ok and HALO_HEURISTIC and f"conv|{M}|{Cout}|{K}{variant}" not in _plan_table() and (
-                not upsample or f"conv|{M}|{Cout}|{K}" not in _plan_table()):
+        if halo_ok and HALO_HEURISTIC and f"conv|{Mp}|{Cout}|{K}{variant}" not in _plan_table() and (
+                not upsample or f"conv|{Mp}|{Cout}|{K}" not in _plan_table()):
             # no measured plan for this shape: the halo kernel (256 x 80 tiles) beat the implicit GEMM on every plain 3x3
             # convolution that was tuned; cut K (whole 64-channel blocks) until ~256 workgroups exist
-            tiles = -(-M // 256) * -(-Cout // 80)
+            tiles = -(-Mp // 256) * -(-Cout // 80)
             ncb = (C1 + C2) // 64
             sp = 1
             while tiles * sp < 192 and sp * 2 <= ncb and sp < 16:
@@ -956,7 +989,7 @@ def conv3x3(x, w, bias=None, x2=None, stride=1, upsample=False, rowvec=None, res
                 p.tile_hint, p.splits, p.stages = 15, sp, 4
         if p.tile_hint in _HALO_TILES and (not halo_ok or (upsample and p.tile_hint != 15) or p.splits > (C1 + C2) // 64):
             # the table is keyed by (M, N, K) alone: a convolution of another geometry that shares the key
-            p.tile_hint, p.splits, p.stages = heuristic_plan(M, Cout, K) + (2,)
+            p.tile_hint, p.splits, p.stages = heuristic_plan(Mp, Cout, K) + (2,)
     else:
         p.tile_hint, p.splits, p.stages = tile_hint, max(1, splits), stages
     ws = _fill_epilogue(p, _rows_ld, "conv3x3", M, Cout, x.device, bias, rowvec, g.rows_per_batch, residual, p.splits)
@@ -1708,14 +1741,45 @@ def attn_apply(probs, v, heads, out=None):
 
 
 # ------------------------------------------------------------------------------- sampler
-def cfg_ddim_step(eps_u, eps_c, x, coef, out=None, x0_out=None, rect=None):
+def cfg_ddim_step(eps_u, eps_c, x, coef, out=None, x0_out=None, rect=None, masked=None):
     """x' from (eps_u, eps_c, x) with coef = device fp32 [a_from, a_to, guidance]; eps_u None => no CFG.
     rect = (traj, step): Direct Inversion in the same launch -- batch row 0 of x [Bp, ...] becomes x'[0] + (z - x'[0]) with
-    z = traj[clamp(step[0], 0, S - 1)]; traj device fp32 [S, *x.shape[1:]], step device int32 [1] (read by the kernel)."""
+    z = traj[clamp(step[0], 0, S - 1)]; traj device fp32 [S, *x.shape[1:]], step device int32 [1] (read by the kernel).
+    masked = (traj, step, mask): DiffEdit in the same launch -- x [Bp, C, h, w]; row b keeps x'[b] where mask[b] != 0 and takes
+    z = traj[clamp(step[0], 0, rows - 1)] elsewhere (a select); mask device fp32 [Bp, h, w], traj device fp32 [rows, C, h, w]."""
     lib = load()
     _dev32(eps_c, "eps_c")
     _dev32(x, "x")
     _dev32(coef, "coef")
+    if masked is not None:
+        if rect is not None:
+            raise ValueError("cfg_ddim_step: rect and masked are two different steps; choose one")
+        traj, step, mask = masked
+        _dev32(traj, "masked trajectory")
+        _dev32(mask, "mask")
+        if eps_u is not None:
+            _dev32(eps_u, "eps_u")
+        if x.dim() != 4 or eps_c.shape != x.shape or (eps_u is not None and eps_u.shape != x.shape):
+            raise ValueError(f"cfg_ddim_step: a masked step takes eps and x as [Bp, C, h, w] of one shape, got {tuple(eps_c.shape)} and "
+                             f"{tuple(x.shape)}")
+        if traj.dim() != 4 or traj.shape[0] < 1 or traj.shape[1:] != x.shape[1:]:
+            raise ValueError(f"cfg_ddim_step: the trajectory must be [steps, {', '.join(map(str, x.shape[1:]))}] (x without its batch "
+                             f"dimension), got {tuple(traj.shape)}")
+        if tuple(mask.shape) != (x.shape[0], *x.shape[2:]):
+            raise ValueError(f"cfg_ddim_step: the mask must be [{x.shape[0]}, {x.shape[2]}, {x.shape[3]}] (one per batch row), got "
+                             f"{tuple(mask.shape)}")
+        if _devi32(step, "masked step") is None or step.numel() != 1:
+            raise TypeError("masked step: expected a device int32 tensor of one element")
+        if out is None:
+            out = torch.empty_like(x)
+        for t, name in ((out, "out"), (x0_out, "x0_out")):
+            if t is not None and (_dev32(t, name).shape != x.shape):
+                raise ValueError(f"cfg_ddim_step: {name} must have the shape of x")
+        _check(lib.ief_cfg_ddim_step_masked_f32(_ptr(eps_u), eps_c.data_ptr(), x.data_ptr(), out.data_ptr(), _ptr(x0_out),
+                                                coef.data_ptr(), x.numel(), x[0].numel(), x.shape[2] * x.shape[3], traj.data_ptr(),
+                                                traj.shape[0], step.data_ptr(), mask.data_ptr(), _stream()),
+               "ief_cfg_ddim_step_masked_f32")
+        return out
     if out is None:
         out = torch.empty_like(x)
     if rect is not None:
@@ -1788,6 +1852,41 @@ def ddpm_noise_maps(eps_u, eps_c, x_t, x_prev, coef_rows, out=None):
         out = torch.empty_like(x_t)
     _check(lib.ief_ddpm_noise_maps_f32(_ptr(eps_u), eps_c.data_ptr(), x_t.data_ptr(), x_prev.data_ptr(), out.data_ptr(),
                                        coef_rows.data_ptr(), x_t.shape[0], x_t[0].numel(), _stream()), "ief_ddpm_noise_maps_f32")
+    return out
+
+
+def diffedit_map_accum(eps_a, eps_b, acc):
+    """DiffEdit's difference map (`ief_diffedit_map_accum_f32`): acc[p] += sum_r sum_c |eps_a[r, c, p] - eps_b[r, c, p]| in row and
+    channel order, every operation rounded in fp32 -- chunking the rows over launches does not change a bit.  eps_a, eps_b device
+    fp32 [R, C, h, w]; acc device fp32 [h, w], updated in place (the caller zeroes it before the first chunk)."""
+    lib = load()
+    for t, name in ((eps_a, "eps_a"), (eps_b, "eps_b"), (acc, "acc")):
+        _dev32(t, name)
+    if eps_a.dim() != 4 or eps_a.shape[0] < 1 or eps_b.shape != eps_a.shape:
+        raise ValueError(f"diffedit_map_accum: eps_a and eps_b must be [R, C, h, w] of one shape, got {tuple(eps_a.shape)} and "
+                         f"{tuple(eps_b.shape)}")
+    if tuple(acc.shape) != tuple(eps_a.shape[2:]):
+        raise ValueError(f"diffedit_map_accum: acc must be [{eps_a.shape[2]}, {eps_a.shape[3]}], got {tuple(acc.shape)}")
+    _check(lib.ief_diffedit_map_accum_f32(eps_a.data_ptr(), eps_b.data_ptr(), acc.data_ptr(), eps_a.shape[0], eps_a.shape[1],
+                                          acc.numel(), _stream()), "ief_diffedit_map_accum_f32")
+    return acc
+
+
+def diffedit_mask(acc, count: int, ratio: float = 3.0, thres: float = 0.5, out=None):
+    """DiffEdit's mask rule (`ief_diffedit_mask_f32`): d = acc / count, v = min(max(d, 0), ratio mean(d)) / (ratio mean(d)),
+    out = 1.0 where v > thres else 0.0; a zero map gives a zero mask.  acc device fp32 [h, w]; out device fp32 of acc's shape."""
+    lib = load()
+    _dev32(acc, "acc")
+    if acc.numel() < 1:
+        raise ValueError("diffedit_mask: acc has no elements")
+    if not isinstance(count, int) or isinstance(count, bool) or count < 1:
+        raise ValueError(f"diffedit_mask: count must be a positive integer, got {count!r}")
+    if out is None:
+        out = torch.empty_like(acc)
+    if _dev32(out, "out").shape != acc.shape or out.data_ptr() == acc.data_ptr():
+        raise ValueError("diffedit_mask: out must have acc's shape and its own memory")
+    _check(lib.ief_diffedit_mask_f32(acc.data_ptr(), out.data_ptr(), acc.numel(), count, float(ratio), float(thres), _stream()),
+           "ief_diffedit_mask_f32")
     return out
 
 

@@ -228,6 +228,31 @@ int ief_cfg_ddpm_step_f32(const float* eps_u, const float* eps_c, const float* x
  * IEF_EINVAL: a null eps_c / x_t / x_prev / z_out / coef_rows; IEF_ESHAPE: R <= 0, row_elems <= 0. */
 int ief_ddpm_noise_maps_f32(const float* eps_u, const float* eps_c, const float* x_t, const float* x_prev, float* z_out,
                             const float* coef_rows, int R, long long row_elems, void* stream);
+/* DiffEdit (Couairon, Verbeek, Schwenk, Cord, "DiffEdit: Diffusion-based semantic image editing with mask guidance"): the CFG + DDIM
+ * step of ief_cfg_ddim_step_f32 in the same launch, and every batch row keeps x' only where ITS binary mask is set; elsewhere the
+ * element is put back onto the stored inversion trajectory.  For element i = b row_elems + c hw + p:
+ *   x_out = mask[b][p] != 0 ? x' : z[c hw + p],   z = traj[min(max(step[0], 0), traj_rows - 1)]
+ * a select, so inside the mask x_out equals ief_cfg_ddim_step_f32's bit for bit and outside it the trajectory's; x0_out (optional) is
+ * the un-masked x0 prediction, the plain step's everywhere.  mask: DEVICE fp32 [n / row_elems][hw]; traj: DEVICE fp32
+ * [traj_rows][row_elems]; step: DEVICE int32 [1], read by the kernel and clamped as ief_select_step clamps it.  eps_u == NULL:
+ * eps = eps_c; x_out == x allowed.
+ * IEF_EINVAL: a null eps_c / x / x_out / coef / traj / step / mask; IEF_ESHAPE: n <= 0, row_elems <= 0, n % row_elems != 0, hw <= 0,
+ * row_elems % hw != 0, traj_rows <= 0; IEF_EALIGN: a pointer off the 4-byte grid.  Nothing is launched by a refused call. */
+int ief_cfg_ddim_step_masked_f32(const float* eps_u, const float* eps_c, const float* x, float* x_out, float* x0_out,
+                                 const float* coef, long long n, long long row_elems, long long hw,
+                                 const float* traj, int traj_rows, const int* step, const float* mask, void* stream);
+/* DiffEdit's difference map: eps_a, eps_b fp32 [R][C][hw], acc fp32 [hw] (zeroed by the caller before the first launch):
+ *   acc[p] = (..((acc[p] + s_0) + s_1)..) + s_{R-1},   s_r = (..(|a_r0p - b_r0p| + |a_r1p - b_r1p|)..) + |a_r(C-1)p - b_r(C-1)p|
+ * every operation rounded in fp32, rows and channels in order: R rows in one launch and the same rows over several launches give
+ * the same bits.  One writer per element, no atomics.
+ * IEF_EINVAL: a null pointer; IEF_ESHAPE: R <= 0, C <= 0, hw <= 0; IEF_EALIGN: a pointer off the 4-byte grid. */
+int ief_diffedit_map_accum_f32(const float* eps_a, const float* eps_b, float* acc, int R, int C, int hw, void* stream);
+/* DiffEdit's mask rule in one workgroup, any hw >= 1: d = acc / count; m = the mean of d over the hw pixels (fixed order: per-lane
+ * strided partials of 256 lanes, a butterfly inside each wave, then the four waves in wave order);
+ *   v = min(max(d, 0), ratio m) / (ratio m)  (an IEEE division);   mask_out[p] = v > thres ? 1.0f : 0.0f
+ * m == 0 gives v = NaN, which compares false: an all-zero mask.  mask_out fp32 [hw], must not overlap acc.
+ * IEF_EINVAL: a null pointer; IEF_ESHAPE: hw <= 0, count <= 0; IEF_EALIGN: a pointer off the 4-byte grid. */
+int ief_diffedit_mask_f32(const float* acc, float* mask_out, int hw, int count, float ratio, float thres, void* stream);
 /* sinusoidal timestep embedding, flip_sin_to_cos, shift 0: out fp16 [B][dim] = [cos | sin] */
 int ief_timestep_embedding_f16(const float* t, ief_half* out, int B, int dim, void* stream);
 /* out = a + b elementwise on fp16 (residual add when a hook owns Attention.forward) */
