@@ -905,6 +905,21 @@ __global__ __launch_bounds__(256, (D > 80) ? 1 : 2) void attn_flash_x3_kernel(co
 //   (80-byte rows) and D = 80 need none.  Nothing is read past a row: the score product's padding lanes (d >= D) and the
 //   transposing V reads of head-dim columns >= D take their address from column 0 -- their operand is multiplied by the zero
 //   padding of Q, respectively lands in output rows >= D that are never stored.
+//   D % 32 != 0 (FOLD): the padding rows of the LAST O^T tile do work instead.  d = 40: its A operand is ONE fragment set, rows 0..7
+//   V hi columns 32..39, rows 8..15 V lo of the same columns (a per-lane offset of the transposing read: V lo = V hi + PL), rows
+//   16..23 the constant 1.0 from a small LDS region behind the buffers: two MFMAs per 16-key step, (T1, P hi) and (T1, P lo),
+//   instead of three and one read set instead of two; O columns 32..39 = rows 0..7 + rows 8..15 (same lane, registers j and 4 + j;
+//   the P lo V lo term it picks up only adds accuracy) and rows 16..23 ARE the softmax row sum l = sum (P hi + P lo) over all
+//   keys of both lane halves: no vector adds per tile, no exchange at the end, rescaled with O by the lazy maximum.  d = 80: rows
+//   16..31 of the third tile take V lo columns 64..79 (8 MFMAs per step instead of 9); no room for the ones, the vector row sum stays.
+//   D % 16 != 0 (BIAS; d = 40, every form but CLS): the score product's padding does work too.  Q is scaled to log2 units once per
+//   wave and split again; padding column 40 of the last d group holds hi / lo of the exponent's bias LOGSP - m in Q and 1.0 (K hi)
+//   / 0 (K lo) from two constant chunks in K, so the accumulators leave the MFMA as the exponent and exp2 takes them as they are:
+//   no scale-and-bias FMA per score.  m is kept an INTEGER (ceil of the maximum: the bias is exact in fp16 hi / lo) and starts at
+//   LOGSP (bias 0 = the padding as loaded); the first tile of a walk sets it to ceil(max) in EITHER direction -- a row whose scores
+//   all lie far below zero would otherwise end with l = 0 -- and the rare update path shifts the tile's exponents by m_old - m_new
+//   in vector code and rewrites the bias element.  Per 64-key tile and wave at d = 40 (gfx950 assembly): MFMA 42 -> 38, transposing
+//   reads 32 -> 24, v_add_f32 34 -> 0, v_fma_f32 31 -> 0; 126 VGPRs, no scratch.
 //   One barrier per tile: [own DMA of tile t landed] barrier [issue tile t + 1 into the other buffer] scores, softmax, P V.
 //   NWV waves per workgroup (32 queries each).  d = 40: 8 waves / 256 queries: two workgroups (80 KiB of LDS, 16 waves) per CU --
 //   four 40-KiB workgroups of 4 waves are exactly the CU's 160 KiB and were NOT co-resident (measured: still a second round);
@@ -966,7 +981,28 @@ __global__ __launch_bounds__(64 * NWV, D <= 40 ? 4 : 2) void attn_flash_x3p_kern
     constexpr bool SWZ = D == 64;
     constexpr float LOGSP = 10.f, THR = 5.f;
     constexpr bool BATCH_READS = X3P_FLASH_BATCH_READS != 0;
-    __shared__ __attribute__((aligned(1024))) half_t smem_p[2 * 4 * PL];
+    // FOLD: the last O^T tile has REM = D % 32 real rows; its padding rows carry V lo (and, ONES, a row of 1.0: the row sum)
+    constexpr int REM = D % 32;
+    constexpr bool FOLD = REM == 8 || REM == 16, ONES = REM == 8;
+    static_assert(REM == 0 || FOLD, "the last O^T tile is whole, or has room for V lo beside V hi");
+    // ONES: a constant region behind the two buffers, all 1.0; a lane that reads it adds the same per-step row offsets as the
+    // lanes that read V, so it spans the tile's last step: (KT - 8) rows of D halves + the 8-byte granule
+    constexpr int ONE_AT = 2 * 4 * PL, ONE_N = ONES ? (KT - 8) * D + 8 : 0;
+    __shared__ __attribute__((aligned(1024))) half_t smem_p[ONE_AT + ONE_N];
+    // BIAS (the score product has padding columns too, D % 16 != 0; not CLS, whose running maximum starts at -1e30 and whose tiles
+    // can be masked whole): Q is scaled to log2 units once, and padding column D of the LAST d group carries the exponent's bias
+    // LOGSP - m through the MFMA -- Q holds hi / lo of the bias there, K hi reads 1.0 and K lo 0 from two constant 16-byte chunks
+    // that sit in the gaps of the ones region (halves 8..15 and 16..23 of every 32-row sub-tile stride; the ones are read at
+    // multiples of 8 rows + 0..3).  m stays an INTEGER (ceil of the maximum), so the bias is exact in fp16 hi / lo; the
+    // accumulators leave the MFMA as the exponent itself
+    constexpr bool BIAS = ONES && D % 16 != 0 && !CLS;
+    static_assert(!BIAS || ((KS - 1) * 32 * D + 24 <= ONE_N && (8 * D) % 32 == 0), "the K constants fit the gaps of the ones region");
+    if constexpr (ONES) {                        // written once; the loop's first barrier publishes it
+        for (int i = threadIdx.x; i < ONE_N / 2; i += 64 * NWV) {
+            const int r = (2 * i) % (32 * D);
+            ((unsigned*)(smem_p + ONE_AT))[i] = (BIAS && r >= 8 && r < 24) ? (r == 8 ? 0x00003C00u : 0u) : 0x3C003C00u;
+        }
+    }
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 31, lh = lane >> 5;
@@ -1011,6 +1047,18 @@ __global__ __launch_bounds__(64 * NWV, D <= 40 ? 4 : 2) void attn_flash_x3p_kern
 #pragma unroll
             for (int j = 0; j < 8; ++j) { qh[g][j] = 0; ql[g][j] = 0; }
         }
+    }
+    const float sc2 = p.scale * 1.44269504088896341f;      // scores in log2 units (operand scale 1)
+    if constexpr (BIAS) {                        // q' = (q hi + q lo) sc2, split again: the zero padding stays zero
+#pragma unroll
+        for (int g = 0; g < DG; ++g)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const float f = ((float)qh[g][j] + (float)ql[g][j]) * sc2;
+                const half_t hh = (half_t)f;
+                qh[g][j] = hh;
+                ql[g][j] = (half_t)(f - (float)hh);
+            }
     }
     // staging: the 4 NP pieces of a tile are dealt round-robin to the waves; piece q = plane q / NP, chunks 64 (q % NP) + lane of it,
     // chunk c -> (row c / CPR, 16-byte chunk c % CPR)
@@ -1069,13 +1117,21 @@ __global__ __launch_bounds__(64 * NWV, D <= 40 ? 4 : 2) void attn_flash_x3p_kern
         if (col >= D) col = 0;                   // feeds output rows >= D only (never stored)
         voff[tt] = col;
     }
+    // FOLD: the one fragment set of the last tile, by the tile row cw .. cw + 3 this lane's granule feeds: rows < REM V hi, rows
+    // < 2 REM V lo of the same columns (PL halves on from V hi), the rest (ONES) the constant 1.0 -- rows 2 REM .. 3 REM - 1 are the
+    // softmax row sum, summed over the keys by the MFMA itself; what lies above them is never looked at
+    int vfl = 0;                                 // halves from the tile's V hi plane (a ones lane: from the constant region) to this lane's granule in the step at row 0
+    if constexpr (FOLD) {
+        const int cw = 16 * ((lane >> 4) & 1) + 4 * (L16 & 3);
+        voff[DT - 1] = 0;
+        vfl = cw >= 2 * REM ? 0 : vrow * D + 32 * (DT - 1) + (cw < REM ? cw : PL + cw - REM);
+    }
     f32x16 o[DT];
 #pragma unroll
     for (int t = 0; t < DT; ++t)
 #pragma unroll
         for (int r = 0; r < 16; ++r) o[t][r] = 0.f;
-    float m_run = CLS ? -1e30f : -INFINITY, l_run = 0.f;
-    const float sc2 = p.scale * 1.44269504088896341f;      // scores in log2 units (operand scale 1)
+    float m_run = BIAS ? LOGSP : CLS ? -1e30f : -INFINITY, l_run = 0.f;      // BIAS: the bias LOGSP - m starts at 0 = Q's padding
     // CLS: the class word of this wave's 32 queries (q0 is a multiple of 32; a wave past N reads nothing and stores nothing)
     unsigned qw = 0;
     if constexpr (CLS) qw = q0 < p.N ? p.q_cls[q0 >> 5] : 0u;
@@ -1100,6 +1156,12 @@ __global__ __launch_bounds__(64 * NWV, D <= 40 ? 4 : 2) void attn_flash_x3p_kern
         const half_t* Kl = Kh + PL;
         const half_t* Vh = Kl + PL;
         const half_t* Vl = Vh + PL;
+        // BIAS: the last d group's K fragments; its padding lanes (lh = 1) read the constants [1, 0 x 7] and [0 x 8]
+        const half_t* khb = Kh + koff[DG - 1];
+        const half_t* klb = Kl + koff[DG - 1];
+        if constexpr (BIAS) {
+            if (lh) { khb = smem_p + ONE_AT + 8; klb = smem_p + ONE_AT + 16; }
+        }
         __builtin_amdgcn_s_setprio(1);                      // matrix phases run at raised priority: at equal priority the vector streams of
         f32x16 sacc[KS];                                    // the SIMD's other waves take the issue port and the MFMAs of this one starve
 #pragma unroll
@@ -1111,6 +1173,11 @@ __global__ __launch_bounds__(64 * NWV, D <= 40 ? 4 : 2) void attn_flash_x3p_kern
             half8_t kh[DG], kl[DG];
 #pragma unroll
             for (int g = 0; g < DG; ++g) {
+                if (BIAS && g == DG - 1) {
+                    kh[g] = *(const half8_t*)(khb + u * 32 * D);
+                    kl[g] = *(const half8_t*)(klb + u * 32 * D);
+                    continue;
+                }
                 kh[g] = *(const half8_t*)(Kh + u * 32 * D + koff[g]);
                 kl[g] = *(const half8_t*)(Kl + u * 32 * D + koff[g]);
             }
@@ -1163,25 +1230,70 @@ __global__ __launch_bounds__(64 * NWV, D <= 40 ? 4 : 2) void attn_flash_x3p_kern
                 mxb = __builtin_fmaxf(mxb, sacc[0][8 + r]);
             }
         }
-        float mx = fmaxf(mxa, mxb) * sc2;
-        if (__builtin_amdgcn_ballot_w64(mx > m_run + THR) != 0) {
-            mx = fmaxf(mx, __shfl_xor(mx, 32));
-            const float m_new = fmaxf(m_run, mx);
-            const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);      // first tile: exp2(-inf) = 0, O and l are 0
+        if constexpr (BIAS) {
+            // the accumulators are s' - m + LOGSP (s' the score in log2 units).  m moves on the first tile of the walk -- to ceil(max),
+            // DOWN from its start where the scores lie below it -- and where a score passes the threshold; that path shifts the
+            // tile's exponents by m_old - m_new in vector code and rewrites the bias element of Q
+            float mx = fmaxf(mxa, mxb);
+            const bool first = t == t_beg;
+            if (first || __builtin_amdgcn_ballot_w64(mx > LOGSP + THR) != 0) {
+                mx = fmaxf(mx, __shfl_xor(mx, 32));
+                float m_new = ceilf(mx - (LOGSP - m_run));
+                if (!first) m_new = fmaxf(m_run, m_new);
+                if (!(m_new > -INFINITY)) m_new = m_run;            // no key of this row in the tile
+                const float dlt = m_run - m_new;
+                const float alpha = first ? 0.f : __builtin_amdgcn_exp2f(dlt);      // first tile: O and l are 0
 #pragma unroll
-            for (int tt = 0; tt < DT; ++tt)
+                for (int tt = 0; tt < DT; ++tt)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) o[tt][r] *= alpha;
-            l_run *= alpha;
-            m_run = m_new;
+                    for (int r = 0; r < 16; ++r) o[tt][r] *= alpha;
+#pragma unroll
+                for (int u = 0; u < KS; ++u)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) sacc[u][r] += dlt;
+                m_run = m_new;
+                if (lh) {
+                    const float mb = LOGSP - m_new;
+                    const half_t hh = (half_t)mb;
+                    qh[DG - 1][0] = hh;
+                    ql[DG - 1][0] = (half_t)(mb - (float)hh);
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < KS; ++u)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) sacc[u][r] = __builtin_amdgcn_exp2f(sacc[u][r]);
+        } else {
+            float mx = fmaxf(mxa, mxb) * sc2;
+            if (__builtin_amdgcn_ballot_w64(mx > m_run + THR) != 0) {
+                mx = fmaxf(mx, __shfl_xor(mx, 32));
+                const float m_new = fmaxf(m_run, mx);
+                const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);      // first tile: exp2(-inf) = 0, O and l are 0
+#pragma unroll
+                for (int tt = 0; tt < DT; ++tt)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) o[tt][r] *= alpha;
+                l_run *= alpha;
+                m_run = m_new;
+            }
+            const float mb = LOGSP - m_run;
+            if constexpr (ONES) {                               // the row sum is a row of O^T (below)
+#pragma unroll
+                for (int u = 0; u < KS; ++u)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) sacc[u][r] = __builtin_amdgcn_exp2f(__builtin_fmaf(sacc[u][r], sc2, mb));
+            } else {
+                float ls = 0.f;
+#pragma unroll
+                for (int u = 0; u < KS; ++u)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) { sacc[u][r] = __builtin_amdgcn_exp2f(__builtin_fmaf(sacc[u][r], sc2, mb)); ls += sacc[u][r]; }
+                l_run += ls;
+            }
         }
-        const float mb = LOGSP - m_run;
-        float ls = 0.f;
-#pragma unroll
-        for (int u = 0; u < KS; ++u)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { sacc[u][r] = __builtin_amdgcn_exp2f(__builtin_fmaf(sacc[u][r], sc2, mb)); ls += sacc[u][r]; }
-        l_run += ls;
+        // FOLD: this lane's granule of the last tile's fragment set in the step at row 0
+        const half_t* vf = nullptr;
+        if constexpr (FOLD) vf = ((ONES && (lane & 16)) ? smem_p + ONE_AT : Vh) + vfl;      // tile rows >= 16 = 2 REM: lanes 16..31 and 48..63
         __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int u = 0; u < KS; ++u) {
@@ -1202,6 +1314,14 @@ __global__ __launch_bounds__(64 * NWV, D <= 40 ? 4 : 2) void attn_flash_x3p_kern
                 for (int tt = 0; tt < DT; ++tt) {
                     // keys {4 lh .. + 3} and {8 + 4 lh .. + 3} of this 16-key step: rows r0, r0 + 8 of the tile
                     const int r0 = u * 32 + 16 * s2 + vrow;
+                    if constexpr (FOLD) {
+                        if (tt == DT - 1) {                  // one read set: [V hi | V lo | 1] in the tile's rows
+                            const half4 a0 = x3_lds_tr_read(vf + (u * 32 + 16 * s2) * D), a1 = x3_lds_tr_read(vf + (u * 32 + 16 * s2 + 8) * D);
+#pragma unroll
+                            for (int j = 0; j < 4; ++j) { vh[tt][j] = a0[j]; vh[tt][4 + j] = a1[j]; }
+                            continue;
+                        }
+                    }
                     const int c = voff[tt];
                     const int o0 = r0 * D + (SWZ ? ((((c >> 3) ^ (r0 & 7)) << 3) | (c & 7)) : c);
                     const int o1 = (r0 + 8) * D + (SWZ ? ((((c >> 3) ^ ((r0 + 8) & 7)) << 3) | (c & 7)) : c);
@@ -1213,6 +1333,11 @@ __global__ __launch_bounds__(64 * NWV, D <= 40 ? 4 : 2) void attn_flash_x3p_kern
                 if constexpr (BATCH_READS) __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int tt = 0; tt < DT; ++tt) {
+                    if (FOLD && tt == DT - 1) {              // rows of V hi and of V lo each take P hi + P lo: all four terms
+                        o[tt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh[tt], pl, o[tt], 0, 0, 0);
+                        o[tt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh[tt], ph, o[tt], 0, 0, 0);
+                        continue;
+                    }
                     o[tt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vl[tt], ph, o[tt], 0, 0, 0);
                     o[tt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh[tt], pl, o[tt], 0, 0, 0);
                     o[tt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh[tt], ph, o[tt], 0, 0, 0);
@@ -1222,7 +1347,14 @@ __global__ __launch_bounds__(64 * NWV, D <= 40 ? 4 : 2) void attn_flash_x3p_kern
         }
         __builtin_amdgcn_s_setprio(0);
     }
-    const float l_tot = l_run + __shfl_xor(l_run, 32);
+    if constexpr (FOLD) {                                    // the last tile's columns: V hi rows + V lo rows, REM rows = REM / 2 registers apart
+#pragma unroll
+        for (int r = 0; r < REM / 2; ++r) o[DT - 1][r] += o[DT - 1][REM / 2 + r];
+    }
+    // ONES: tile rows 16 .. 23 hold the row sum over ALL keys (register 8 of both lane halves), rescaled with O
+    float l_tot;
+    if constexpr (ONES) l_tot = o[DT - 1][8];
+    else l_tot = l_run + __shfl_xor(l_run, 32);
     if constexpr (SPLIT) {                                   // the partial (O, m, l) of this split; lanes li and li + 32 share m_run
         if (qi < p.N) {
             const long long rows = (long long)p.B * p.heads * p.N, row = ((long long)b * p.heads + h) * p.N + qi;
