@@ -93,8 +93,126 @@ class StepCounter:
         self.cur_step, self.cur_att_layer = 0, 0
 
 
+# ------------------------------------------------------------------------------------------ LEDITS++: host tables
+LEDITS_MAX_CONCEPTS = 8
+
+
+def ledits_rank(q: float, n: int):
+    """(lo, frac) of torch.quantile's linear rule over n values with the arithmetic pinned: q (n - 1) in double, its floor, and
+    the remainder rounded to fp32 -- t = v_(lo) + frac (v_(lo + 1) - v_(lo)).  frac lies in [0, 1): a remainder that rounds to 1.0f
+    moves to the next rank."""
+    import numpy as np
+    q = float(q)
+    if not 0.0 <= q <= 1.0:
+        raise ValueError(f"LEDITS++: a threshold is a quantile in [0, 1], got {q!r}")
+    if n < 1:
+        raise ValueError("ledits_rank: n must be >= 1")
+    pos = q * (n - 1)
+    lo = int(pos // 1)
+    frac = float(np.float32(pos - lo))
+    if frac >= 1.0:
+        lo, frac = lo + 1, 0.0
+    if lo >= n - 1:
+        lo, frac = n - 1, 0.0
+    return lo, frac
+
+
+def ledits_rank_table(qs, n: int):
+    """fp32 [E, 2] = [lo, frac] per concept (`ief_ledits_attn_mask_f32` / `ief_ledits_guidance_mask_f32`); lo < 2^24 is exact"""
+    return torch.tensor([list(ledits_rank(q, n)) for q in qs], dtype=torch.float32).reshape(-1, 2)
+
+
+def ledits_taps(sigma: float = 0.5):
+    """the nine fp32 taps of the 3 x 3 smoothing, row-major: the normalised 2-D Gaussian, formed in double"""
+    g = torch.exp(-(torch.arange(3, dtype=torch.float64) - 1.0) ** 2 / (2.0 * float(sigma) ** 2))
+    k = torch.outer(g, g)
+    return (k / k.sum()).to(torch.float32).flatten()
+
+
+def ledits_token_weights(token_counts):
+    """fp32 [E, 2, XL] = (u_e, v_e) for `ief_cross_blend_mass_f32`: u_e = 0 (no source row), v_e = 1 on tokens 1 .. n_e of concept
+    e's tokenisation (between BOS and EOS), 0 elsewhere"""
+    w = torch.zeros(len(token_counts), 2, XL)
+    for e, n in enumerate(token_counts):
+        n = int(n)
+        if not 1 <= n <= ControlPlan.CTX_TOKENS - 2:
+            raise ValueError(f"LEDITS++: concept {e} has {n} tokens between BOS and EOS (1 .. {ControlPlan.CTX_TOKENS - 2})")
+        w[e, 1, 1:1 + n] = 1.0
+    return w
+
+
+def _per_concept(value, E, name, kind=float, none_ok=False):
+    vals = list(value) if isinstance(value, (list, tuple)) else [value]
+    if len(vals) == 1:
+        vals = vals * E
+    if len(vals) != E:
+        raise ValueError(f"LEDITS++: {len(vals)} values of {name} for {E} concepts (one value, or one per concept)")
+    return [None if (v is None and none_ok) else kind(v) for v in vals]
+
+
+def ledits_scale_table(num_steps: int, scales, reverse=(), warmup=0, cooldown=None):
+    """fp32 [num_steps + 1, E]: the guidance scale of concept e in edit step i (counted from 0 at the first step the edit runs),
+    sign and gate folded in: -scale for a concept in `reverse` (its direction is removed), 0 while i < warmup_e and from
+    i >= cooldown_e on (None: no cool-down), 0 in the row past the schedule.  A zero switches the concept off in that step."""
+    scales = list(scales) if isinstance(scales, (list, tuple)) else [scales]
+    E = len(scales)
+    warm = _per_concept(warmup, E, "warm-up steps", int)
+    cool = _per_concept(cooldown, E, "cool-down steps", int, none_ok=True)
+    rev = set(int(r) for r in reverse)
+    if any(not 0 <= r < E for r in rev):
+        raise ValueError(f"LEDITS++: a reversed concept index outside [0, {E})")
+    if any(w < 0 for w in warm) or any(c is not None and c < 0 for c in cool):
+        raise ValueError("LEDITS++: warm-up and cool-down steps are >= 0")
+    tab = torch.zeros(num_steps + 1, E, dtype=torch.float32)
+    for e in range(E):
+        s = -float(scales[e]) if e in rev else float(scales[e])
+        for i in range(num_steps):
+            if i >= warm[e] and (cool[e] is None or i < cool[e]):
+                tab[i, e] = s
+    return tab
+
+
+def check_ledits(E, thresholds=(), *, sdxl=False, cfg_split=False, uncond_list=None, source_trajectory=None, edit_mask=None,
+                 controller=False):
+    """what a LEDITS++ edit refuses (host-side facts only; raises ValueError)"""
+    if sdxl:
+        raise ValueError("LEDITS++: built for the SD1.x / SD2.x pipelines, not for an SDXL UNet")
+    if cfg_split:
+        raise ValueError("LEDITS++: the batch is [uncond | concepts], not two halves: not built for the two-GPU CFG split")
+    if uncond_list is not None:
+        raise ValueError("LEDITS++ together with uncond_list: the edit has no null-text embeddings")
+    if source_trajectory is not None:
+        raise ValueError("LEDITS++ together with source_trajectory: the edit has no source branch to rectify")
+    if edit_mask is not None:
+        raise ValueError("LEDITS++ together with edit_mask: the method makes its own masks")
+    if controller:
+        raise ValueError("LEDITS++: an attention controller, hook or control plan is installed; the masks on top of the "
+                         "controllers are out of scope")
+    if not isinstance(E, int) or not 1 <= E <= LEDITS_MAX_CONCEPTS:
+        raise ValueError(f"LEDITS++: 1 .. {LEDITS_MAX_CONCEPTS} edit concepts, got {E!r}")
+    for q in thresholds:
+        if not 0.0 <= float(q) <= 1.0:
+            raise ValueError(f"LEDITS++: a threshold is a quantile in [0, 1], got {q!r}")
+
+
+def ledits_cross_mask_refusal(precision, x3p, modules, latent_hw):
+    """None, or why the cross-attention mask cannot be served: it stands where LocalBlend's fused form stands.
+    modules: (heads, head dim, queries) of the five modules `p2p.model.register.blend_modules` names"""
+    if precision != "f16x3" or not x3p:
+        return "the cross-attention mask runs on the operand-planes path of the f16x3 mode only (pass cross_attn_mask=False)"
+    if len(modules) != 5 or any(N != ControlPlan.MAP_TOKENS for _, _, N in modules):
+        return (f"the 16 x 16 cross-attention modules have {[N for _, _, N in modules]} queries at the UNet's configured sample "
+                f"size, not five times {ControlPlan.MAP_TOKENS}")
+    for heads, d, _ in modules:
+        if heads > 64 or d % 8:
+            return f"a 16 x 16 cross-attention module has {heads} heads of dim {d} (at most 64 heads, head dim a multiple of 8)"
+    if latent_hw[0] % 16 or latent_hw[1] % 16:
+        return f"latents of {latent_hw[0]} x {latent_hw[1]} are no multiple of the 16 x 16 map"
+    return None
+
+
 class ControlPlan:
-    """kind: 'empty' | 'p2p' | 'masactrl' | 'masactrl_mask' | 'masactrl_mask_auto' | 'masactrl_union' | 'pnp'"""
+    """kind: 'empty' | 'p2p' | 'masactrl' | 'masactrl_mask' | 'masactrl_mask_auto' | 'masactrl_union' | 'pnp' | 'ledits'"""
     MASA_KINDS = ("masactrl", "masactrl_mask", "masactrl_mask_auto", "masactrl_union")
     GATED_KINDS = ("masactrl_mask", "masactrl_mask_auto")
     MAP_TOKENS, CTX_TOKENS = 256, 77
@@ -104,12 +222,14 @@ class ControlPlan:
                  self_window=(0, 0), self_max_tokens: int = 256, masa_steps=(), masa_layers=(),
                  pnp_layers=(), pnp_qk_steps: int = 0, pnp_conv_steps: int = 0, cond_only: bool = False,
                  mask_s: Optional[torch.Tensor] = None, mask_t: Optional[torch.Tensor] = None, mask_tokens=(),
-                 auto_slots=None, auto_layers=None, auto_thres: float = 0.1, auto_ref=(), auto_cur=(), blend=None):
+                 auto_slots=None, auto_layers=None, auto_thres: float = 0.1, auto_ref=(), auto_cur=(), blend=None, ledits=None):
         """cond_only: the UNet batch holds ONLY the conditional rows [cond_src, cond_tgt...] — the half a controller acts
         on (`attention_base.py:20-22`) — as on the conditional rank of a 2-GPU CFG split (`denoise.CfgSplitDenoiser`) and
         in the reference's LOW_RESOURCE protocol (:18-19)
         blend ('p2p' only): None, or (execution indices of the five modules LocalBlend reads, per-step weights fp32
-        [steps+1, Bp, 2, XL] = (u_i, v_i), threshold)"""
+        [steps+1, Bp, 2, XL] = (u_i, v_i), threshold)
+        ledits ('ledits' only): dict(scale fp32 [steps+1, E], thresholds [E], token_counts [E], cross_mask, intersect_mask, modules
+        (execution indices of the five 16 x 16 cross-attention modules; used with cross_mask), latent_hw, channels)"""
         self.controller = controller
         self.kind = kind
         self.device = torch.device(device)
@@ -185,6 +305,9 @@ class ControlPlan:
         self.auto_ref, self.auto_cur = [int(i) for i in auto_ref], [int(i) for i in auto_cur]
         self._auto = None                          # (slots fp32 [K, 2, 256], weights fp32 [2, 77], thres fp32 [1])
         self._auto_cls = {}                        # (exec index, N) -> (k_cls, q_cls) int32 [N / 32]
+        self.led = None
+        if kind == "ledits":
+            self._init_ledits(**ledits)
         self.pnp_layers = set(pnp_layers)          # id() of the Attention modules whose Q/K are injected
         self.pnp_qk_steps, self.pnp_conv_steps = int(pnp_qk_steps), int(pnp_conv_steps)
         self._pnp = {}                             # B -> (qk_table, qk_cur, conv_table, conv_cur)
@@ -338,6 +461,8 @@ class ControlPlan:
         summed over the reference tokens, that of row c_tgt over the current tokens (q fp32 [B, N, C], k fp32 [B, 77, C])"""
         if self.blend_w is not None:
             return self._blend_mass(B, N, attn, q, k)
+        if self.kind == "ledits":
+            return self._ledits_mass(B, N, attn, q, k)
         if self.kind != "masactrl_mask_auto":
             return
         slot = self.auto_slots.get(attn._exec_index)
@@ -374,6 +499,59 @@ class ControlPlan:
         if self.blend_w is not None and not self.muted:
             hip.local_blend(self.blend_acc, self.blend_thres, x)
         return x
+
+    # ------------------------------------------------------------------ LEDITS++ ('ledits')
+    def _init_ledits(self, scale, thresholds, token_counts, cross_mask, intersect_mask, modules, latent_hw, channels):
+        """the device tables of a LEDITS++ edit on the UNet batch [uncond | concept_1 .. concept_E] of ONE latent.  Everything a
+        step varies with is a row of `scale`, selected by the LOOP's device step counter (`ledits_step`): this plan keeps no
+        counter of its own moving, so a warm-up forward needs no muting."""
+        dev = self.device
+        E, (h, w) = int(scale.shape[1]), latent_hw
+        check_ledits(E, thresholds)
+        if len(thresholds) != E or len(token_counts) != E or tuple(scale.shape) != (self.num_steps + 1, E):
+            raise ValueError(f"LEDITS++: {E} concepts need {E} thresholds, {E} token counts and a scale table "
+                             f"[{self.num_steps + 1}, {E}]")
+        if h * w > 16384 or not 1 <= channels <= 16:
+            raise ValueError(f"LEDITS++: latents of {channels} x {h} x {w}; the mask kernels hold h w <= 16384 pixels and <= 16 channels")
+        self.num_prompts, self.batch = E, 1 + E
+        led = self.led = {"E": E, "cross": bool(cross_mask), "intersect": bool(intersect_mask), "hw": (int(h), int(w)),
+                          "modules": tuple(int(i) for i in modules) if cross_mask else ()}
+        f32 = dict(dtype=torch.float32, device=dev)
+        led["scale"] = scale.to(**f32).contiguous()
+        led["scale_cur"] = torch.zeros(E, **f32)
+        led["w"] = ledits_token_weights(token_counts).to(dev)
+        led["taps"] = ledits_taps().to(dev)
+        led["rank_attn"] = ledits_rank_table(thresholds, self.MAP_TOKENS).to(dev)
+        led["rank_pix"] = ledits_rank_table(thresholds, h * w).to(dev)
+        led["acc"] = torch.zeros(E, self.MAP_TOKENS, **f32)
+        led["m1"] = torch.zeros(E, self.MAP_TOKENS, **f32)
+        led["mask"] = torch.zeros(E, h, w, **f32)
+        led["thres"] = torch.zeros(E, **f32)
+
+    def _ledits_mass(self, B: int, N: int, attn, q, k):
+        """one of the five 16 x 16 modules adds the head-mean map of every concept row, summed over the concept's own tokens"""
+        led = self.led
+        if attn._exec_index not in led["modules"]:
+            return
+        if N != self.MAP_TOKENS:
+            raise RuntimeError(f"{attn.layer_name}: the cross-attention mask was lowered for the UNet's configured sample size, where "
+                               f"this module has {self.MAP_TOKENS} queries; it runs at {N}")
+        if B != self.batch or q.shape[0] != B or k.shape[0] != B or k.shape[1] != self.CTX_TOKENS:
+            raise RuntimeError(f"LEDITS++: cross-attention of batch {tuple(q.shape)} x {tuple(k.shape)}; the rule is stated for the "
+                               f"batch [uncond | {led['E']} concepts] and {self.CTX_TOKENS} prompt tokens")
+        hip.cross_blend_mass(q, k, attn.heads, attn.scale, 1, led["w"], led["acc"])
+
+    def ledits_step(self, eps, lat, coef_cur, maps, step):
+        """after the UNet of a step: the implicit masks and the guided eta = 1 update of the ONE latent `lat`, in place.  eps fp32
+        [1 + E, C, h, w]; step: the loop's device counter, which picks the scale row and the noise map"""
+        led = self.led
+        hip.select_step(led["scale"], led["scale_cur"], step)
+        m1 = hip.ledits_attn_mask(led["acc"], led["taps"], led["rank_attn"], out=led["m1"]) if led["cross"] else None
+        mask = None
+        if led["cross"] or led["intersect"]:
+            mask, _ = hip.ledits_guidance_mask(eps, m1, led["rank_pix"] if led["intersect"] else None, out=led["mask"],
+                                               thres_out=led["thres"] if led["intersect"] else None)
+        hip.ledits_ddpm_step(eps, mask, led["scale_cur"], lat, coef_cur, maps, step, out=lat)
 
     def _rewound(self, step: int):
         """the step counter was set from outside a forward: at step 0 a new run begins and the blend accumulator starts empty"""
@@ -455,6 +633,9 @@ class ControlPlan:
             inj = (unet.up_blocks[1].resnets[0 if unet.cfg.addition_embed else 1]._inject is self
                    if len(unet.up_blocks) > 1 else False)
             return ("pnp", tuple(sorted(idx[i] for i in self.pnp_layers)), self.num_steps, bool(inj))
+        if self.kind == "ledits":             # which launches run and on which modules; concepts, scales and thresholds are data
+            led = self.led
+            return ("ledits", led["E"], self.num_steps, led["cross"], led["intersect"], led["modules"], led["hw"])
         return (self.kind,)
 
     def load_from(self, other: "ControlPlan", B: int):
@@ -510,6 +691,9 @@ class ControlPlan:
             self.pnp_qk_steps, self.pnp_conv_steps = other.pnp_qk_steps, other.pnp_conv_steps
             self._pnp[B][0].copy_(other._pnp[B][0])
             self._pnp[B][2].copy_(other._pnp[B][2])
+        elif self.kind == "ledits":
+            for name in ("scale", "w", "rank_attn", "rank_pix"):
+                self.led[name].copy_(other.led[name])
 
     # ------------------------------------------------------------------ per-forward protocol
     def applies(self, B: int) -> bool:
@@ -524,6 +708,15 @@ class ControlPlan:
         return True
 
     def begin_forward(self, B: int):
+        if self.kind == "ledits":
+            # the method reads the CURRENT step's maps (unlike LocalBlend's running sum): the accumulator is emptied every forward,
+            # inside the captured graph; nothing else of this plan moves with a forward, so a muted warm-up runs it whole
+            if B != self.batch:
+                raise RuntimeError(f"LEDITS++ was lowered for {self.led['E']} concepts (UNet batch {self.batch}) but the UNet was "
+                                   f"called with batch {B}")
+            if self.led["cross"]:
+                self.led["acc"].zero_()
+            return
         if not self.applies(B):
             return
         if not self.captured:
@@ -565,7 +758,7 @@ class ControlPlan:
     def end_forward(self, B: int):
         if (self.kind in self.MASA_KINDS or self.kind == "pnp") and not self.muted:
             hip.advance_step(self.step)
-        elif self.kind != "empty" and not self.muted and B == self.batch:
+        elif self.kind not in ("empty", "ledits") and not self.muted and B == self.batch:
             hip.advance_step(self.step)
 
     def layer_done(self, attn):

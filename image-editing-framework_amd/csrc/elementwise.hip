@@ -2,6 +2,7 @@
 // SiLU, casts, and the per-step table select that lets ONE captured graph serve all 50 steps.
 #include "ief_common.h"
 #include "ief_params.h"
+#include "ddpm_step.h"
 
 // eps = eps_u + g (eps_c - eps_u);  x0 = (x - sqrt(1-a_f) eps) / sqrt(a_f);  x' = sqrt(a_t) x0 + sqrt(1-a_t) eps
 // Same operation order as the reference's scheduler.step / ddim_reverse so fp32 results stay
@@ -125,21 +126,8 @@ extern "C" int ief_cfg_ddim_step_masked_f32(const float* eps_u, const float* eps
 // Edit-friendly DDPM inversion (Huberman-Spiegelglas et al., "An Edit Friendly DDPM Noise Space"): the eta = 1 update
 //   eps = eps_u + g (eps_c - eps_u);  x0 = (x - sqrt(1-a_f) eps) / sqrt(a_f);  mu = sqrt(a_t) x0 + dir eps;  x' = mu + sigma z
 // with sigma and dir = sqrt(1 - a_t - sigma^2) handed in (the host forms them in fp64), and its inverse z = (x_prev - mu) / sigma.
-// Both kernels take mu from ddpm_mu_elem, so the step undoes the extraction on the same eps up to the roundings of z itself.  With
-// sigma = 0 and dir = sqrtf(1 - a_t) mu is cfg_ddim_elem's x', operation for operation.
-struct DdpmCoef { float sb_f, sa_f, sa_t, sigma, dir; };
-__device__ __forceinline__ DdpmCoef ddpm_coef(const float* __restrict__ coef) {
-    const float a_f = coef[0], a_t = coef[1];
-    return {sqrtf(1.0f - a_f), sqrtf(a_f), sqrtf(a_t), coef[2], coef[3]};
-}
-__device__ __forceinline__ float ddpm_mu_elem(const DdpmCoef& c, float g, const float* __restrict__ eu, const float* __restrict__ ec,
-                                              const float* __restrict__ x, float* __restrict__ x0o, long long i) {
-    float e = ec[i];
-    if (eu) { const float u = eu[i]; e = u + g * (e - u); }
-    const float x0 = (x[i] - c.sb_f * e) / c.sa_f;
-    if (x0o) x0o[i] = x0;
-    return c.sa_t * x0 + c.dir * e;
-}
+// Both kernels take mu from ddpm_mu_elem (ddpm_step.h, shared with ledits.hip), so the step undoes the extraction on the same eps
+// up to the roundings of z itself.  With sigma = 0 and dir = sqrtf(1 - a_t) mu is cfg_ddim_elem's x', operation for operation.
 // row of element i; launches of the sampler stay far below 2^32 elements, where one 32-bit division does
 __device__ __forceinline__ long long ddpm_row_of(long long i, long long row_elems, bool small) {
     return small ? (long long)((unsigned)i / (unsigned)row_elems) : i / row_elems;

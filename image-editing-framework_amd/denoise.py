@@ -12,6 +12,8 @@ overhead would exceed the GPU time.  Here the whole step is captured once:
     [Direct Inversion: the same launch moves the source row (row 0) back onto the stored inversion trajectory]
     [edit-friendly DDPM inversion: CFG with a scale per batch row + the eta = 1 update with the stored noise map of this step instead]
     [DiffEdit: the same launch puts every row back onto the stored inversion trajectory outside that row's edit mask]
+    [LEDITS++: the batch is [uncond | concept_1 .. concept_E] on ONE latent; after the UNet the implicit masks (two one-workgroup
+     launches) and the masked multi-concept guidance + eta = 1 update with this step's stored noise map]
     [P2P plan with a LocalBlend: the word-masked blend of the updated latents, in place]
     advance_step
 (on the f16x3 planes trunk the UNet takes the latents themselves and runs what both halves of the CFG batch share once: no copy;
@@ -47,7 +49,7 @@ _said = set()
 
 
 def cfg_shared_prefix_reason(*, mode, cfg, x3p, aug, first_block_cross, native, fused_cross, ln_folded, plan_on_first_self,
-                             taps=False, enabled=True):
+                             taps=False, enabled=True, ledits=False):
     """None where a CFG denoising step may run the prefix its two halves share once (at Bp rows), else the reason why not -- a pure
     function of host-side facts (`UNet2DConditionModel.cfg_shared_facts` collects the model's):
       mode / cfg          the loop is `denoise` with classifier-free guidance (inversion and the no-CFG loops have no second half)
@@ -59,7 +61,10 @@ def cfg_shared_prefix_reason(*, mode, cfg, x3p, aug, first_block_cross, native, 
       ln_folded           IEF_X3P_FOLD_LN=1 (an A/B form of the transformer blocks that has no seam)
       plan_on_first_self  the control plan redirects rows of the first self-attention in some step (`ControlPlan.controls_first_self`)
       taps                a debugging forward that records intermediate tensors at full batch
-      enabled             IEF_CFG_SHARED_PREFIX"""
+      enabled             IEF_CFG_SHARED_PREFIX
+      ledits              a LEDITS++ loop: 1 + E rows on one latent, not two halves (widening the prefix to them is out of scope)"""
+    if ledits:
+        return "the LEDITS++ batch is [uncond | concepts] on one latent, not two halves"
     if not enabled:
         return "switched off (IEF_CFG_SHARED_PREFIX=0)"
     if mode != "denoise" or not cfg:
@@ -181,6 +186,32 @@ def check_edit_mask(mask, *, mode, cfg, uncond_list, noise_maps, source_trajecto
                          f"({num_steps - skip} edit steps)")
 
 
+def check_ledits_loop(plan, *, unet_plan, mode, guidance_scale, uncond_list, source_trajectory, edit_mask, noise_maps, skip,
+                      row_shape, num_steps, num_latents, context_rows, added_cond_kwargs=None):
+    """the argument checks of a LEDITS++ loop (host-side facts only; raises ValueError): `plan` is the 'ledits' control plan
+    registered on the UNet; the loop runs ONE latent at UNet batch 1 + E = [uncond | concepts] on the noise maps of an edit-friendly
+    DDPM inversion, and the scales travel in the plan (`guidance_scale` stays None)"""
+    from .control import check_ledits
+    if getattr(plan, "kind", None) != "ledits":
+        raise ValueError("ledits: expected the 'ledits' ControlPlan registered on the UNet")
+    check_ledits(plan.led["E"], sdxl=added_cond_kwargs is not None, uncond_list=uncond_list, source_trajectory=source_trajectory,
+                 edit_mask=edit_mask, controller=unet_plan is not plan)
+    if guidance_scale is not None:
+        raise ValueError("ledits: the guidance scales of the concepts travel in the plan; guidance_scale stays None")
+    if noise_maps is None:
+        raise ValueError("ledits: the edit runs on the noise maps of an edit-friendly DDPM inversion (noise_maps=)")
+    check_noise_maps(noise_maps, mode=mode, cfg=True, uncond_list=None, source_trajectory=None, row_shape=row_shape,
+                     num_steps=num_steps, skip=skip)
+    if num_latents != 1:
+        raise ValueError(f"ledits: ONE latent per loop, got {num_latents}")
+    if context_rows != 1 + plan.led["E"]:
+        raise ValueError(f"ledits: the context holds [uncond | {plan.led['E']} concepts] = {1 + plan.led['E']} rows, got {context_rows}")
+    if plan.num_steps != num_steps - skip:
+        raise ValueError(f"ledits: the plan's scale table covers {plan.num_steps} edit steps, the loop runs {num_steps - skip}")
+    if tuple(row_shape[-2:]) != plan.led["hw"]:
+        raise ValueError(f"ledits: the plan was lowered for latents of {plan.led['hw']}, the loop runs {tuple(row_shape[-2:])}")
+
+
 def _mask_rows(mask, num_latents, device):
     """the device buffer of an edit mask: fp32 [Bp, h, w], one mask per batch row"""
     m = mask.to(device).float()
@@ -191,7 +222,8 @@ class FusedDenoiser:
     def __init__(self, model, context: torch.Tensor, num_latents: int, latent_hw, guidance_scale: Optional[float],
                  mode: str = "denoise", uncond_list: Optional[List[torch.Tensor]] = None, use_graph: bool = True,
                  added_cond_kwargs=None, source_trajectory: Optional[torch.Tensor] = None,
-                 noise_maps: Optional[torch.Tensor] = None, skip: int = 0, edit_mask: Optional[torch.Tensor] = None):
+                 noise_maps: Optional[torch.Tensor] = None, skip: int = 0, edit_mask: Optional[torch.Tensor] = None,
+                 ledits=None):
         """context: [2*Bp,77,C] (uncond, cond) for mode 'denoise' with CFG, [Bp,77,C] for 'invert' / no-CFG.
         added_cond_kwargs: SDXL's {"text_embeds" [B, 1280], "time_ids" [B, 6]} (one row per UNet batch row); they are
         constant over the steps, so they fold into the per-step time-embedding rows (then one row PER BATCH ROW).
@@ -203,21 +235,34 @@ class FusedDenoiser:
         maps were extracted with).
         edit_mask, source_trajectory, skip: DiffEdit -- fp32 or bool [Bp, h, w] (or [h, w]), nonzero = edited, with the trajectory of
         a PARTIAL inversion, fp32 [S - skip, C, h, w], row i = z*_{S-skip-1-i}; the loop runs `timesteps[skip:]` from z*_{S-skip} and
-        after step i every row is x' inside its mask and the trajectory row outside it (a select, in the launch of the update)."""
+        after step i every row is x' inside its mask and the trajectory row outside it (a select, in the launch of the update).
+        ledits, noise_maps, skip: LEDITS++ -- the 'ledits' `control.ControlPlan` registered on the UNet (E concepts); num_latents is
+        1, context [1 + E, 77, C] = [uncond | concept_1 .. concept_E], guidance_scale None (the per-step scales are the plan's);
+        every row of the UNet batch is the one latent, and the step ends with the plan's masks and `ief_ledits_ddpm_step_f32`."""
         self.model, self.unet, self.sched = model, model.unet, model.scheduler
         dev = self.unet.device
         self.mode = mode
         self.cfg = guidance_scale is not None
-        if edit_mask is not None:
+        self.ledits = ledits
+        if ledits is not None:
+            check_ledits_loop(ledits, unet_plan=self.unet._plan, mode=mode, guidance_scale=guidance_scale, uncond_list=uncond_list,
+                              source_trajectory=source_trajectory, edit_mask=edit_mask, noise_maps=noise_maps, skip=skip,
+                              row_shape=(self.unet.config.in_channels, *latent_hw), num_steps=len(self.sched.timesteps),
+                              num_latents=num_latents, context_rows=context.shape[0], added_cond_kwargs=added_cond_kwargs)
+        elif getattr(self.unet._plan, "kind", None) == "ledits":
+            raise ValueError("a 'ledits' control plan is registered on the UNet: its loop is built with ledits=plan")
+        if ledits is None and edit_mask is not None:
             check_edit_mask(edit_mask, mode=mode, cfg=self.cfg, uncond_list=uncond_list, noise_maps=noise_maps,
                             source_trajectory=source_trajectory, row_shape=(self.unet.config.in_channels, *latent_hw),
                             num_steps=len(self.sched.timesteps), skip=skip, num_latents=num_latents)
             if added_cond_kwargs is not None:
                 raise ValueError("edit_mask: DiffEdit is built for the SD1.x / SD2.x pipelines (no added_cond_kwargs)")
-        elif source_trajectory is not None:
+        elif ledits is None and source_trajectory is not None:
             check_source_trajectory(source_trajectory, mode=mode, cfg=self.cfg, uncond_list=uncond_list,
                                     row_shape=(self.unet.config.in_channels, *latent_hw), num_steps=len(self.sched.timesteps))
-        if noise_maps is not None:
+        if ledits is not None:
+            pass                              # check_ledits_loop has checked the maps and the skip
+        elif noise_maps is not None:
             check_noise_maps(noise_maps, mode=mode, cfg=self.cfg, uncond_list=uncond_list, source_trajectory=source_trajectory,
                              row_shape=(self.unet.config.in_channels, *latent_hw), num_steps=len(self.sched.timesteps), skip=skip,
                              guidance_scale=guidance_scale, num_latents=num_latents)
@@ -228,6 +273,8 @@ class FusedDenoiser:
         self.skip = skip if (noise_maps is not None or edit_mask is not None) else 0
         self.Bp = num_latents
         self.B = 2 * num_latents if self.cfg else num_latents
+        if ledits is not None:
+            self.B = 1 + ledits.led["E"]
         if context.shape[0] != self.B:
             raise ValueError(f"context batch {context.shape[0]} != UNet batch {self.B}")
         h, w = latent_hw
@@ -242,6 +289,8 @@ class FusedDenoiser:
             _said.add(self.shared_reason)       # a planes model that could share and does not: said once per reason
             _log.warning("CFG step without the shared prefix: %s", self.shared_reason)
         self.lat_in = self.lat if (self.shared or not self.cfg) else torch.zeros(self.B, C, h, w, dtype=torch.float32, device=dev)
+        if ledits is not None:              # every row of [uncond | concepts] is the one latent
+            self.lat_in = torch.zeros(self.B, C, h, w, dtype=torch.float32, device=dev)
         self.step = torch.zeros(1, dtype=torch.int32, device=dev)
         self.coef_cur = torch.zeros(4, dtype=torch.float32, device=dev)
         self.coef_table = self.temb_table = self.temb_cur = self.ctx = self.ctx_table = None
@@ -285,7 +334,8 @@ class FusedDenoiser:
 
         if self.maps is not None:         # rows {a, p, sigma, dir}; the guidance scales travel per batch row
             put("coef_table", torch.tensor(coef, dtype=torch.float32, device=dev))
-            put("g_rows", torch.tensor(guidance_rows(guidance_scale, self.Bp), dtype=torch.float32, device=dev))
+            if self.ledits is None:
+                put("g_rows", torch.tensor(guidance_rows(guidance_scale, self.Bp), dtype=torch.float32, device=dev))
         else:
             put("coef_table", torch.tensor([[a, b, g, 0.0] for a, b in coef], dtype=torch.float32, device=dev))
         aug = self.unet.aug_embedding(added_cond_kwargs)          # None unless the UNet has SDXL's additional embedding
@@ -317,20 +367,33 @@ class FusedDenoiser:
         if facts is None:
             return "the UNet has no shared-prefix form"
         return cfg_shared_prefix_reason(mode=self.mode, cfg=self.cfg, enabled=CFG_SHARED_PREFIX and type(self)._step_body is FusedDenoiser._step_body,
+                                        ledits=getattr(self, "ledits", None) is not None,
                                         **facts(tuple(self.lat.shape[-2:]), ctx_len))
 
-    def _key(self, context, uncond_list, source_trajectory=None, noise_maps=None, skip=0, edit_mask=None):
+    def _key(self, context, uncond_list, source_trajectory=None, noise_maps=None, skip=0, edit_mask=None, ledits=None):
         plan = self.unet._plan
-        return (id(self.unet), self.mode, self.Bp, tuple(self.lat.shape[-2:]), self.cfg, tuple(context.shape),
-                None if uncond_list is None else len(uncond_list), len(self.sched.timesteps),
-                None if plan is None else plan.signature(self.unet), self._shared_reason(context.shape[1]) is None,
-                edit_mask is not None, source_trajectory is not None, noise_maps is not None,
-                skip if (noise_maps is not None or edit_mask is not None) else 0, getattr(self.unet, "attn_key_splits", 1))
+        key = (id(self.unet), self.mode, self.Bp, tuple(self.lat.shape[-2:]), self.cfg, tuple(context.shape),
+               None if uncond_list is None else len(uncond_list), len(self.sched.timesteps),
+               None if plan is None else plan.signature(self.unet), self._shared_reason(context.shape[1]) is None,
+               edit_mask is not None, source_trajectory is not None, noise_maps is not None,
+               skip if (noise_maps is not None or edit_mask is not None) else 0, getattr(self.unet, "attn_key_splits", 1))
+        # a LEDITS++ loop says so itself (its plan's signature, above, carries E, the mask mode and the module indices)
+        return key if ledits is None else key + ("ledits",)
 
     def rebind(self, context, guidance_scale, uncond_list, added_cond_kwargs=None, source_trajectory=None, noise_maps=None,
-               skip=0, edit_mask=None):
+               skip=0, edit_mask=None, ledits=None):
         """point a captured loop at the next image: new tables, new cross-attention K/V, the new controller's plan, the next
-        image's inversion trajectory or noise maps and guidance scales, or its edit masks"""
+        image's inversion trajectory or noise maps and guidance scales, or its edit masks; a LEDITS++ loop takes the next
+        image's concepts, scales and thresholds from the freshly registered plan"""
+        if (ledits is None) != (self.ledits is None):
+            raise ValueError("rebind: a LEDITS++ loop serves only LEDITS++ jobs, and the reverse")
+        if ledits is not None:
+            check_ledits_loop(ledits, unet_plan=self.unet._plan, mode=self.mode, guidance_scale=guidance_scale, uncond_list=uncond_list,
+                              source_trajectory=source_trajectory, edit_mask=edit_mask, noise_maps=noise_maps, skip=skip,
+                              row_shape=tuple(self.lat.shape[1:]), num_steps=len(self.sched.timesteps), num_latents=self.Bp,
+                              context_rows=context.shape[0], added_cond_kwargs=added_cond_kwargs)
+            if skip != self.skip or ledits.signature(self.unet) != self.plan.signature(self.unet):
+                raise ValueError("rebind: a LEDITS++ loop serves only jobs of the same skip and plan signature")
         if (edit_mask is None) != (self.mask is None) or (edit_mask is not None and skip != self.skip):
             raise ValueError("rebind: a loop captured with an edit mask serves only jobs that bring a mask and the same skip, and the "
                              "reverse")
@@ -342,9 +405,10 @@ class FusedDenoiser:
         if (noise_maps is None) != (self.maps is None) or (noise_maps is not None and skip != self.skip):
             raise ValueError("rebind: a loop captured with noise maps serves only jobs that bring maps of the same skip, and the reverse")
         if noise_maps is not None:
-            check_noise_maps(noise_maps, mode=self.mode, cfg=self.cfg, uncond_list=uncond_list, source_trajectory=source_trajectory,
-                             row_shape=tuple(self.lat.shape[1:]), num_steps=len(self.sched.timesteps), skip=skip,
-                             guidance_scale=guidance_scale, num_latents=self.Bp)
+            if ledits is None:              # check_ledits_loop has checked a LEDITS++ job's maps
+                check_noise_maps(noise_maps, mode=self.mode, cfg=self.cfg, uncond_list=uncond_list, source_trajectory=source_trajectory,
+                                 row_shape=tuple(self.lat.shape[1:]), num_steps=len(self.sched.timesteps), skip=skip,
+                                 guidance_scale=guidance_scale, num_latents=self.Bp)
             self.maps.copy_(noise_maps)
         if (source_trajectory is None) != (self.traj is None):
             raise ValueError("rebind: a loop captured with a source trajectory serves only jobs that bring one, and the reverse")
@@ -373,6 +437,14 @@ class FusedDenoiser:
         hip.select_step(self.coef_table, self.coef_cur, self.step)
         if self.ctx_table is not None:
             hip.select_step(self.ctx_table, self.ctx, self.step)
+        if self.ledits is not None:
+            # [uncond | concept_1 .. concept_E], all rows on the same latent and time embedding; then the implicit masks and the
+            # masked multi-concept guidance with the eta = 1 update (`ControlPlan.ledits_step`)
+            self.lat_in.copy_(self.lat.expand_as(self.lat_in))
+            eps = self.unet(self.lat_in, encoder_hidden_states=self.ctx, temb_row=self.temb_cur)["sample"]
+            self.plan.ledits_step(eps, self.lat, self.coef_cur, self.maps, self.step)
+            hip.advance_step(self.step)
+            return
         if self.cfg and self.shared:
             # the UNet takes the Bp latents themselves: no CFG batch copy, and what both halves share is computed once
             eps = self.unet(self.lat, encoder_hidden_states=self.ctx, temb_row=self.temb_cur, cfg_pair=True)["sample"]
@@ -541,6 +613,8 @@ class CfgSplitDenoiser(FusedDenoiser):
 
     def __init__(self, model, context, num_latents, latent_hw, guidance_scale: float, group=None, uncond_list=None,
                  use_graph: bool = True, source_trajectory=None, noise_maps=None, skip=0, edit_mask=None):
+        if getattr(model.unet._plan, "kind", None) == "ledits":
+            raise ValueError("CFG split: LEDITS++ runs [uncond | concepts] on one latent, not two halves; run the edit on one GPU")
         if edit_mask is not None:
             raise ValueError("CFG split: DiffEdit (edit_mask) is not built for the two-GPU split; run the edit on one GPU")
         if noise_maps is not None or skip:
@@ -649,29 +723,31 @@ class CfgSplitDenoiser(FusedDenoiser):
 
 def acquire(model, context, num_latents, latent_hw, guidance_scale, mode="denoise", uncond_list=None,
             use_graph=True, added_cond_kwargs=None, source_trajectory=None, noise_maps=None, skip=0,
-            edit_mask=None) -> FusedDenoiser:
+            edit_mask=None, ledits=None) -> FusedDenoiser:
     """a FusedDenoiser for this job: a pooled one with a captured graph of the same shape / plan signature, re-pointed
     at the new context, tables and controller — or a new one.  source_trajectory: Direct Inversion (`FusedDenoiser`); loops
     with and without one never share a pool entry.  noise_maps, skip: edit-friendly DDPM inversion (`FusedDenoiser`;
     guidance_scale may then be one scale per latent); presence of maps and skip are part of the pool key.  edit_mask (with
-    source_trajectory and skip): DiffEdit (`FusedDenoiser`); loops with and without a mask never share a pool entry"""
+    source_trajectory and skip): DiffEdit (`FusedDenoiser`); loops with and without a mask never share a pool entry.  ledits (with
+    noise_maps and skip; guidance_scale None): LEDITS++ (`FusedDenoiser`), the 'ledits' plan registered on the UNet -- its signature
+    (E, the mask mode, the module indices) is part of the pool key, so pooled loops of different kinds never mix"""
     if REUSE_GRAPHS and use_graph:
         probe = FusedDenoiser.__new__(FusedDenoiser)
         probe.unet, probe.sched, probe.mode = model.unet, model.scheduler, mode
-        probe.cfg, probe.Bp = guidance_scale is not None, num_latents
+        probe.cfg, probe.Bp, probe.ledits = guidance_scale is not None, num_latents, ledits
         probe.lat = torch.empty(0, 0, *latent_hw)
-        key = probe._key(context, uncond_list, source_trajectory, noise_maps, skip, edit_mask)
+        key = probe._key(context, uncond_list, source_trajectory, noise_maps, skip, edit_mask, ledits)
         free = _POOL.get(key)
         if free:
             loop = free.pop()
-            loop.rebind(context, guidance_scale, uncond_list, added_cond_kwargs, source_trajectory, noise_maps, skip, edit_mask)
+            loop.rebind(context, guidance_scale, uncond_list, added_cond_kwargs, source_trajectory, noise_maps, skip, edit_mask, ledits)
             return loop
         loop = FusedDenoiser(model, context, num_latents, latent_hw, guidance_scale, mode, uncond_list, use_graph,
-                             added_cond_kwargs, source_trajectory, noise_maps, skip, edit_mask)
+                             added_cond_kwargs, source_trajectory, noise_maps, skip, edit_mask, ledits)
         loop._pool_key = key
         return loop
     return FusedDenoiser(model, context, num_latents, latent_hw, guidance_scale, mode, uncond_list, use_graph,
-                         added_cond_kwargs, source_trajectory, noise_maps, skip, edit_mask)
+                         added_cond_kwargs, source_trajectory, noise_maps, skip, edit_mask, ledits)
 
 
 def drop_pool():

@@ -1890,6 +1890,104 @@ def diffedit_mask(acc, count: int, ratio: float = 3.0, thres: float = 0.5, out=N
     return out
 
 
+def _ledits_rank(rank, E, who):
+    if tuple(_dev32(rank, "rank").shape) != (E, 2):
+        raise ValueError(f"{who}: rank must be [{E}, 2] = [lo, frac] per concept, got {tuple(rank.shape)}")
+    return rank
+
+
+def ledits_attn_mask(acc, taps, rank, out=None):
+    """LEDITS++'s cross-attention mask M1 (`ief_ledits_attn_mask_f32`): per concept e the 16 x 16 mass acc[e] is smoothed with the
+    nine `taps` (3 x 3, row-major tap order, reflect padding) and thresholded at its quantile,
+        t = v_(lo) + frac (v_(lo + 1) - v_(lo));  out[e] = 1.0 where smoothed >= t else 0.0
+    with exact order statistics.  acc device fp32 [E, 256] (or [E, 16, 16]), 1 <= E <= 8; taps device fp32 [9]; rank device fp32
+    [E, 2] = [lo, frac] per concept (`ledits.rank_table`); out device fp32 of acc's shape, its own memory."""
+    lib = load()
+    _dev32(acc, "acc")
+    _dev32(taps, "taps")
+    if acc.dim() < 2 or acc[0].numel() != 256:
+        raise ValueError(f"ledits_attn_mask: acc must be [E, 256], got {tuple(acc.shape)}")
+    E = acc.shape[0]
+    if taps.numel() != 9:
+        raise ValueError(f"ledits_attn_mask: taps are the nine weights of a 3 x 3 filter, got {taps.numel()} elements")
+    _ledits_rank(rank, E, "ledits_attn_mask")
+    if out is None:
+        out = torch.empty_like(acc)
+    if _dev32(out, "out").shape != acc.shape or out.data_ptr() == acc.data_ptr():
+        raise ValueError("ledits_attn_mask: out must have acc's shape and its own memory")
+    _check(lib.ief_ledits_attn_mask_f32(acc.data_ptr(), taps.data_ptr(), rank.data_ptr(), out.data_ptr(), E, _stream()),
+           "ief_ledits_attn_mask_f32")
+    return out
+
+
+def ledits_guidance_mask(eps, m1=None, rank=None, out=None, thres_out=None):
+    """LEDITS++'s per-concept mask M (`ief_ledits_guidance_mask_f32`): for concept e and pixel p
+        s[p] = sum_c |eps[1 + e, c, p] - eps[0, c, p]| m,  m = m1[e, cell(p)]  (1 without m1; cell = the 16 x 16 cell of p)
+        t = the `rank[e]` quantile of s (exact order statistics);  out[e, p] = 1.0 where s[p] >= t and m != 0 else 0.0
+    channels in order, every operation rounded in fp32.  rank None: no threshold, out is m1 spread to the pixels.  eps device fp32
+    [1 + E, C, h, w], row 0 the unconditional estimate, h w <= 16384, C <= 16, 1 <= E <= 8 (h, w multiples of 16 with m1); m1 device
+    fp32 [E, 256] of 0.0 / 1.0; rank device fp32 [E, 2]; out device fp32 [E, h, w]; thres_out device fp32 [E] receives t.
+    Returns (out, thres_out); thres_out stays None (and unwritten) without rank."""
+    lib = load()
+    _dev32(eps, "eps")
+    if eps.dim() != 4 or eps.shape[0] < 2:
+        raise ValueError(f"ledits_guidance_mask: eps must be [1 + E, C, h, w] with E >= 1, got {tuple(eps.shape)}")
+    E, C, H, W = eps.shape[0] - 1, eps.shape[1], eps.shape[2], eps.shape[3]
+    if m1 is not None and (_dev32(m1, "m1").dim() < 2 or m1.shape[0] != E or m1[0].numel() != 256):
+        raise ValueError(f"ledits_guidance_mask: m1 must be [{E}, 256], got {tuple(m1.shape)}")
+    if rank is not None:
+        _ledits_rank(rank, E, "ledits_guidance_mask")
+        if thres_out is None:
+            thres_out = torch.empty(E, dtype=torch.float32, device=eps.device)
+        if _dev32(thres_out, "thres_out").numel() != E:
+            raise ValueError(f"ledits_guidance_mask: thres_out must hold {E} elements")
+    if out is None:
+        out = torch.empty((E, H, W), dtype=torch.float32, device=eps.device)
+    if tuple(_dev32(out, "out").shape) != (E, H, W):
+        raise ValueError(f"ledits_guidance_mask: out must be [{E}, {H}, {W}], got {tuple(out.shape)}")
+    _check(lib.ief_ledits_guidance_mask_f32(eps.data_ptr(), _ptr(m1), _ptr(rank), out.data_ptr(),
+                                            _ptr(thres_out) if rank is not None else None, E, C, H, W, _stream()),
+           "ief_ledits_guidance_mask_f32")
+    return out, (thres_out if rank is not None else None)
+
+
+def ledits_ddpm_step(eps, mask, scale, x, coef, noise, step, out=None, x0_out=None):
+    """The step of a LEDITS++ edit on ONE latent (`ief_ledits_ddpm_step_f32`): with eps [1 + E, C, h, w], row 0 unconditional,
+        eps' = eps[0] + sum_e scale[e] mask[e] (eps[1 + e] - eps[0]);  mu = sqrt(a_to) x0 + dir eps';  x' = mu + sigma noise[clamp(step[0])]
+    the sum in concept order from 0, a concept with scale[e] == 0 skipped; the mean is `cfg_ddpm_step`'s (one device function), so E = 1
+    without a mask IS that step.  mask device fp32 [E, h, w] or None (all ones); scale device fp32 [E] (sign and gate folded in);
+    x device fp32 [1, C, h, w] or [C, h, w]; coef = device fp32 [a_from, a_to, sigma, dir]; noise device fp32 [rows, C, h, w]; step
+    device int32 [1] (read by the kernel)."""
+    lib = load()
+    for t, name in ((eps, "eps"), (scale, "scale"), (x, "x"), (coef, "coef"), (noise, "noise maps")):
+        _dev32(t, name)
+    if eps.dim() != 4 or eps.shape[0] < 2:
+        raise ValueError(f"ledits_ddpm_step: eps must be [1 + E, C, h, w] with E >= 1, got {tuple(eps.shape)}")
+    E, hw = eps.shape[0] - 1, eps.shape[2] * eps.shape[3]
+    if x.numel() != eps[0].numel() or tuple(x.shape[-3:]) != tuple(eps.shape[1:]):
+        raise ValueError(f"ledits_ddpm_step: x is ONE latent [{', '.join(map(str, eps.shape[1:]))}], got {tuple(x.shape)}")
+    if mask is not None and tuple(_dev32(mask, "mask").shape) != (E,) + tuple(eps.shape[2:]):
+        raise ValueError(f"ledits_ddpm_step: mask must be [{E}, {eps.shape[2]}, {eps.shape[3]}], got {tuple(mask.shape)}")
+    if scale.numel() != E:
+        raise ValueError(f"ledits_ddpm_step: {scale.numel()} scales for {E} concepts")
+    if coef.numel() != 4:
+        raise ValueError(f"ledits_ddpm_step: coef is [a_from, a_to, sigma, dir], got {coef.numel()} elements")
+    if noise.dim() != 4 or noise.shape[0] < 1 or noise.shape[1:] != eps.shape[1:]:
+        raise ValueError(f"ledits_ddpm_step: the noise maps must be [steps, {', '.join(map(str, eps.shape[1:]))}], got "
+                         f"{tuple(noise.shape)}")
+    if _devi32(step, "step") is None or step.numel() != 1:
+        raise TypeError("step: expected a device int32 tensor of one element")
+    if out is None:
+        out = torch.empty_like(x)
+    for t, name in ((out, "out"), (x0_out, "x0_out")):
+        if t is not None and (_dev32(t, name).shape != x.shape):
+            raise ValueError(f"ledits_ddpm_step: {name} must have the shape of x")
+    _check(lib.ief_ledits_ddpm_step_f32(eps.data_ptr(), _ptr(mask), scale.data_ptr(), x.data_ptr(), out.data_ptr(), _ptr(x0_out),
+                                        coef.data_ptr(), x.numel(), hw, noise.data_ptr(), noise.shape[0], step.data_ptr(), E,
+                                        _stream()), "ief_ledits_ddpm_step_f32")
+    return out
+
+
 def ddim_step(eps, x, a_from: float, a_to: float):
     """scheduler.step on device tensors: returns (x_prev, x0)."""
     coef = torch.tensor([a_from, a_to, 1.0], dtype=torch.float32, device=x.device)

@@ -51,12 +51,14 @@ class DDPMInversion(ddim_inversion):
         return torch.cat([xts, x0c[None]]).to(x0.device).contiguous()
 
     @torch.no_grad()
-    def noise_maps(self, model, x0, prompt, guidance_scale=3.5, skip=0, rows_per_launch=4, generator=None):
+    def noise_maps(self, model, x0, prompt, guidance_scale=3.5, skip=0, rows_per_launch=4, generator=None, uncond_only=None):
         """-> (y_skip [1, C, h, w], maps fp32 [S - skip, C, h, w], xts [S + 1, C, h, w]).  guidance_scale 3.5 and skip 0 are the
         paper's extraction defaults (its edits then skip 36 % of the steps).  Rows skip ... S - 1 go through the UNet
         `rows_per_launch` at a time: one forward at batch 2 K = [K unconditional | K conditional] rows with the chunk's K
         time-embedding rows repeated for both halves, then one extraction launch.  The last chunk is simply shorter (eager
-        launches: nothing is captured, so nothing needs padding)."""
+        launches: nothing is captured, so nothing needs padding).  uncond_only: None = the unconditional-only form (batch K, one
+        half) exactly when the source prompt is empty; False forces both halves (what an empty prompt ran before that form existed);
+        True with a non-empty prompt is a ValueError."""
         unet, sched = model.unet, model.scheduler
         if not (all(m.is_native() for m in unet.attention_modules()) and getattr(unet, "_plan", None) is None):
             raise RuntimeError("DDPMInversion: an attention hook is installed; invert before registering controllers")
@@ -80,15 +82,26 @@ class DDPMInversion(ddim_inversion):
         coef = torch.tensor([[*sched.ddpm_coeffs(t), g] for t in ts], dtype=torch.float32, device=dev)
         temb = unet.time_rows(torch.tensor(ts, dtype=torch.float32, device=dev))          # [S, width]
         maps = torch.empty(S - skip, *xts.shape[1:], dtype=torch.float32, device=dev)
-        ctxs = {}         # one context tensor per chunk size: the cross-attention K/V cache is keyed on the tensor, so the full
+        # an EMPTY source prompt (LEDITS++'s default) makes the conditional row the unconditional one: eps_u + g (eps_c - eps_u) is
+        # eps_u whatever g, so only that row runs -- chunks at batch K instead of 2 K, and the extraction takes eps_u = None
+        if uncond_only is None:
+            uncond_only = prompt[0] == ""
+        elif uncond_only and prompt[0] != "":
+            raise ValueError("noise_maps: the unconditional-only form stands for an EMPTY source prompt")
+        ctxs = {}       # one context tensor per chunk size: the cross-attention K/V cache is keyed on the tensor, so the full
         for r0 in range(skip, S, K):      # chunks project their K/V once
             r1 = min(r0 + K, S)
             k = r1 - r0
             y = xts[r0:r1]
             if k not in ctxs:
-                ctxs[k] = unet._act(torch.cat([uncond.expand(k, -1, -1), cond.expand(k, -1, -1)]).to(dev).contiguous())
+                halves = [uncond.expand(k, -1, -1)] if uncond_only else [uncond.expand(k, -1, -1), cond.expand(k, -1, -1)]
+                ctxs[k] = unet._act(torch.cat(halves).to(dev).contiguous())
             ctx = ctxs[k]
             rows = temb[r0:r1]
+            if uncond_only:
+                eps = unet(y.contiguous(), encoder_hidden_states=ctx, temb_row=rows.contiguous())["sample"]
+                hip.ddpm_noise_maps(None, eps, y, xts[r0 + 1:r1 + 1], coef[r0:r1], out=maps[r0 - skip:r1 - skip])
+                continue
             eps = unet(torch.cat([y, y]), encoder_hidden_states=ctx, temb_row=torch.cat([rows, rows]).contiguous())["sample"]
             hip.ddpm_noise_maps(eps[:k], eps[k:], y, xts[r0 + 1:r1 + 1], coef[r0:r1], out=maps[r0 - skip:r1 - skip])
         return xts[skip:skip + 1].clone(), maps, xts

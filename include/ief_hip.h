@@ -253,6 +253,42 @@ int ief_diffedit_map_accum_f32(const float* eps_a, const float* eps_b, float* ac
  * m == 0 gives v = NaN, which compares false: an all-zero mask.  mask_out fp32 [hw], must not overlap acc.
  * IEF_EINVAL: a null pointer; IEF_ESHAPE: hw <= 0, count <= 0; IEF_EALIGN: a pointer off the 4-byte grid. */
 int ief_diffedit_mask_f32(const float* acc, float* mask_out, int hw, int count, float ratio, float thres, void* stream);
+/* LEDITS++ (Brack et al., "LEDITS++: Limitless Image Editing using Text-to-Image Models", CVPR 2024), three launches
+ * (csrc/ledits.hip).  All arithmetic fp32, every operation rounded on its own, in a fixed order; one writer per element, no atomics
+ * on global memory.  THE QUANTILE RULE of the two mask launches, for n values v >= 0, a rank lo in [0, n - 1] and a fraction frac
+ * in [0, 1):  t = v_(lo) + frac (v_(hi) - v_(lo)),  hi = min(lo + 1, n - 1),  v_(k) the k-th smallest value (k from 0), both order
+ * statistics exact (a radix select over the bit patterns); the bit of an element is  value >= t.  rank: DEVICE fp32 [E][2] =
+ * {lo, frac} per concept, lo a whole number; the host forms q (n - 1) in double, takes its floor and rounds the remainder to fp32
+ * (torch.quantile's linear rule with the arithmetic pinned).
+ * ief_ledits_attn_mask_f32: acc fp32 [E][256], the 16 x 16 cross-attention mass of each concept's own tokens.  Per concept a 3 x 3
+ * smoothing with the nine fp32 taps, (..((0 + taps[0] a_00) + taps[1] a_01)..) + taps[8] a_22 in row-major tap order, REFLECT
+ * padding (index -1 reads 1, index 16 reads 14); then the quantile rule over the 256 smoothed values.  m1_out fp32 [E][256] holds
+ * 0.0 / 1.0 and must not overlap acc.  One workgroup per concept.
+ * IEF_EINVAL: a null pointer; IEF_ESHAPE: E outside [1, 8]; IEF_EALIGN: a pointer off the 4-byte grid.  Nothing is launched by a
+ * refused call (this holds for all three). */
+int ief_ledits_attn_mask_f32(const float* acc, const float* taps, const float* rank, float* m1_out, int E, void* stream);
+/* eps fp32 [1 + E][C][H W]: row 0 the unconditional estimate, row 1 + e concept e's.  Per concept e and pixel p
+ *   s[p] = (..(|d_0p| m + |d_1p| m)..) + |d_(C-1)p| m,   d_cp = eps[1 + e][c][p] - eps[0][c][p],   m = m1[e][cell(p)]
+ * with cell = (floor(16 y / H), floor(16 x / W)), the nearest rule of ief_local_blend_f32; m1 == NULL: m = 1.  Then the quantile
+ * rule over the H W values of s:  mask_out[e][p] = (s[p] >= t && m != 0) ? 1.0f : 0.0f,  thres_out[e] = t.  rank == NULL: no
+ * threshold, mask_out is m1 spread to the pixels (all ones without m1); eps and thres_out are not touched and may be NULL.
+ * m1 fp32 [E][256] holding 0.0 / 1.0; mask_out fp32 [E][H W]; thres_out fp32 [E].  One workgroup per concept, s staged in LDS.
+ * IEF_EINVAL: a null mask_out, or rank without eps or thres_out; IEF_ESHAPE: E outside [1, 8], C outside [1, 16], H < 1, W < 1,
+ * H W > 16384, or m1 given and H or W no multiple of 16; IEF_EALIGN: a pointer off the 4-byte grid. */
+int ief_ledits_guidance_mask_f32(const float* eps, const float* m1, const float* rank, float* mask_out, float* thres_out, int E,
+                                 int C, int H, int W, void* stream);
+/* The masked multi-concept guidance and the eta = 1 update on ONE latent row x fp32 [row_elems] = [C][hw].  For element i, pixel
+ * p = i % hw:   g = (..((0 + w_0) + w_1)..) + w_(E-1),   w_e = (scale[e] mask[e][p]) (eps[1 + e][i] - eps[0][i])
+ * where a concept with scale[e] == 0 is skipped, not multiplied;  eps' = eps[0][i] + g;  then x0, mu and x_out = mu + sigma z from
+ * eps' exactly as ief_cfg_ddpm_step_f32 forms them from its eps (the same device function): with E = 1, mask == NULL and
+ * scale = {g} the two launches agree bit for bit.  eps fp32 [1 + E][row_elems]; mask fp32 [E][hw] or NULL (every value 1); scale:
+ * DEVICE fp32 [E] for the current step, sign and warm-up / cool-down gate folded in; coef, noise, noise_rows, step as there.
+ * x0_out optional; x_out == x allowed.
+ * IEF_EINVAL: a null eps / scale / x / x_out / coef / noise / step; IEF_ESHAPE: E outside [1, 8], hw outside [1, 16384],
+ * row_elems no multiple of hw or outside [hw, 16 hw], noise_rows <= 0; IEF_EALIGN: a pointer off the 4-byte grid. */
+int ief_ledits_ddpm_step_f32(const float* eps, const float* mask, const float* scale, const float* x, float* x_out, float* x0_out,
+                             const float* coef, long long row_elems, long long hw, const float* noise, int noise_rows,
+                             const int* step, int E, void* stream);
 /* sinusoidal timestep embedding, flip_sin_to_cos, shift 0: out fp16 [B][dim] = [cos | sin] */
 int ief_timestep_embedding_f16(const float* t, ief_half* out, int B, int dim, void* stream);
 /* out = a + b elementwise on fp16 (residual add when a hook owns Attention.forward) */
