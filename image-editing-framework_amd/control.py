@@ -541,9 +541,10 @@ class ControlPlan:
                                f"batch [uncond | {led['E']} concepts] and {self.CTX_TOKENS} prompt tokens")
         hip.cross_blend_mass(q, k, attn.heads, attn.scale, 1, led["w"], led["acc"])
 
-    def ledits_step(self, eps, lat, coef_cur, maps, step):
+    def ledits_step(self, eps, lat, coef_cur, maps, step, x0_prev=None):
         """after the UNet of a step: the implicit masks and the guided eta = 1 update of the ONE latent `lat`, in place.  eps fp32
-        [1 + E, C, h, w]; step: the loop's device counter, which picks the scale row and the noise map"""
+        [1 + E, C, h, w]; step: the loop's device counter, which picks the scale row and the noise map.  x0_prev (an order-2 loop's
+        buffer, with its five-column coef_cur): the second-order SDE-DPM-Solver++ update instead (`hip.ledits_dpmpp_step`)"""
         led = self.led
         hip.select_step(led["scale"], led["scale_cur"], step)
         m1 = hip.ledits_attn_mask(led["acc"], led["taps"], led["rank_attn"], out=led["m1"]) if led["cross"] else None
@@ -551,6 +552,9 @@ class ControlPlan:
         if led["cross"] or led["intersect"]:
             mask, _ = hip.ledits_guidance_mask(eps, m1, led["rank_pix"] if led["intersect"] else None, out=led["mask"],
                                                thres_out=led["thres"] if led["intersect"] else None)
+        if x0_prev is not None:
+            hip.ledits_dpmpp_step(eps, mask, led["scale_cur"], lat, coef_cur, maps, step, x0_prev, out=lat)
+            return
         hip.ledits_ddpm_step(eps, mask, led["scale_cur"], lat, coef_cur, maps, step, out=lat)
 
     def _rewound(self, step: int):

@@ -192,6 +192,89 @@ extern "C" int ief_ddpm_noise_maps_f32(const float* eps_u, const float* eps_c, c
     return IEF_OK;
 }
 
+// The same step at solver order 2 (dpmpp_mu_of, ddpm_step.h): coef = {a_from, a_to, sigma, dir, c2}, and x0_prev [n] carries the x0
+// prediction from one step of a batch row to the next -- read (only where c2 != 0) and written by the lane that owns the element.
+// With c2 == 0 the outputs are cfg_ddpm_kernel's bit for bit.
+__global__ __launch_bounds__(256) void cfg_dpmpp_kernel(const float* __restrict__ eu, const float* __restrict__ ec,
+                                                        const float* __restrict__ x, float* __restrict__ xo,
+                                                        float* __restrict__ x0o, float* __restrict__ x0_prev,
+                                                        const float* __restrict__ coef, const float* __restrict__ g_rows,
+                                                        long long n, long long row_elems, const float* __restrict__ noise,
+                                                        int noise_rows, const int* __restrict__ step) {
+    const DdpmCoef c = ddpm_coef(coef);
+    const float c2 = coef[4];
+    const float* __restrict__ z = ddpm_noise_row(noise, noise_rows, step, row_elems);
+    const bool small = n <= 0xffffffffll;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+        const long long b = ddpm_row_of(i, row_elems, small);
+        float e = ec[i];
+        if (eu) { const float u = eu[i]; e = u + g_rows[b] * (e - u); }
+        const float x0p = c2 == 0.0f ? 0.0f : x0_prev[i];
+        float x0;
+        const float mu = dpmpp_mu_of(c, c2, e, x[i], x0p, &x0);
+        if (x0o) x0o[i] = x0;
+        x0_prev[i] = x0;
+        xo[i] = ddpm_add_noise(c, mu, z, i - b * row_elems);
+    }
+}
+
+extern "C" int ief_cfg_dpmpp_step_f32(const float* eps_u, const float* eps_c, const float* x, float* x_out, float* x0_out,
+                                      float* x0_prev, const float* coef, const float* g_rows, long long n, long long row_elems,
+                                      const float* noise, int noise_rows, const int* step, void* stream) {
+    if (!eps_c || !x || !x_out || !x0_prev || !coef || !noise || !step || (eps_u && !g_rows)) return IEF_EINVAL;
+    if (n <= 0 || row_elems <= 0 || n % row_elems != 0 || noise_rows <= 0) return IEF_ESHAPE;
+    if (((uintptr_t)eps_u | (uintptr_t)eps_c | (uintptr_t)x | (uintptr_t)x_out | (uintptr_t)x0_out | (uintptr_t)x0_prev |
+         (uintptr_t)coef | (uintptr_t)g_rows | (uintptr_t)noise | (uintptr_t)step) & 3)
+        return IEF_EALIGN;
+    int grid = (int)((n + 255) / 256);
+    if (grid > 2048) grid = 2048;
+    hipLaunchKernelGGL(cfg_dpmpp_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, eps_u, eps_c, x, x_out, x0_out, x0_prev, coef,
+                       g_rows, n, row_elems, noise, noise_rows, step);
+    IEF_LAUNCH_CHECK();
+    return IEF_OK;
+}
+
+// The extraction at order 2: coef_rows[r] = {a_from, a_to, sigma, dir, g, c2}.  ONE lane owns element j of every row and walks the
+// rows in order with the x0 prediction of row r - 1 in a register; row 0 takes it from x0_carry (only where its c2 != 0), the last
+// row's x0 goes back there.  No dependence between lanes, so the maps of a given eps do not depend on how the rows are dealt over
+// launches.  With c2 == 0 in every row z_out is ddpm_noise_maps_kernel's bit for bit.
+__global__ __launch_bounds__(256) void dpmpp_noise_maps_kernel(const float* __restrict__ eu, const float* __restrict__ ec,
+                                                               const float* __restrict__ xt, const float* __restrict__ xp,
+                                                               float* __restrict__ zo, const float* __restrict__ coef_rows,
+                                                               float* __restrict__ x0_carry, int R, long long row_elems) {
+    for (long long j = (long long)blockIdx.x * 256 + threadIdx.x; j < row_elems; j += (long long)gridDim.x * 256) {
+        float x0p = coef_rows[5] == 0.0f ? 0.0f : x0_carry[j];
+        for (int r = 0; r < R; ++r) {
+            const float* __restrict__ cr = coef_rows + 6 * r;
+            const DdpmCoef c = ddpm_coef(cr);
+            const long long i = (long long)r * row_elems + j;
+            float e = ec[i];
+            if (eu) { const float u = eu[i]; e = u + cr[4] * (e - u); }
+            float x0;
+            const float mu = dpmpp_mu_of(c, cr[5], e, xt[i], x0p, &x0);
+            zo[i] = c.sigma == 0.0f ? 0.0f : (xp[i] - mu) / c.sigma;
+            x0p = x0;
+        }
+        x0_carry[j] = x0p;
+    }
+}
+
+extern "C" int ief_dpmpp_noise_maps_f32(const float* eps_u, const float* eps_c, const float* x_t, const float* x_prev,
+                                        float* z_out, const float* coef_rows, float* x0_carry, int R, long long row_elems,
+                                        void* stream) {
+    if (!eps_c || !x_t || !x_prev || !z_out || !coef_rows || !x0_carry) return IEF_EINVAL;
+    if (R <= 0 || row_elems <= 0) return IEF_ESHAPE;
+    if (((uintptr_t)eps_u | (uintptr_t)eps_c | (uintptr_t)x_t | (uintptr_t)x_prev | (uintptr_t)z_out | (uintptr_t)coef_rows |
+         (uintptr_t)x0_carry) & 3)
+        return IEF_EALIGN;
+    int grid = (int)((row_elems + 255) / 256);
+    if (grid > 2048) grid = 2048;
+    hipLaunchKernelGGL(dpmpp_noise_maps_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, eps_u, eps_c, x_t, x_prev, z_out,
+                       coef_rows, x0_carry, R, row_elems);
+    IEF_LAUNCH_CHECK();
+    return IEF_OK;
+}
+
 // diffusers Timesteps(dim, flip_sin_to_cos=True, downscale_freq_shift=0) [ext]: [cos | sin]
 __global__ void timestep_embedding_kernel(const float* __restrict__ t, half_t* __restrict__ out, int B, int dim) {
     const int half_dim = dim >> 1;

@@ -3,6 +3,7 @@
 //   ledits_attn_mask       3 x 3 smoothing of a concept's 16 x 16 cross-attention mass, then a quantile threshold      -> M1
 //   ledits_guidance_mask   s[p] = sum_c |eps_e - eps_u| M1, a quantile threshold over the pixels, AND M1                -> M
 //   ledits_ddpm_step       eps' = eps_u + sum_e scale_e M_e (eps_e - eps_u), then the eta = 1 update of ddpm_step.h
+//   ledits_dpmpp_step      the same guidance, then the second-order SDE-DPM-Solver++ update of ddpm_step.h (the paper's solver)
 // The two mask kernels run ONE workgroup per concept: they are latency, not throughput (256 and at most 16384 values).  Their
 // quantile is torch.quantile's linear rule with the arithmetic pinned, and its two order statistics are EXACT: the values are
 // non-negative, so their bit patterns order as unsigned integers, and a radix select walks those bits a byte at a time over a
@@ -215,6 +216,54 @@ extern "C" int ief_ledits_ddpm_step_f32(const float* eps, const float* mask, con
     const int grid = (int)((row_elems + 255) / 256);     // at most 1024 workgroups
     hipLaunchKernelGGL(ledits_ddpm_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, eps, mask, scale, x, x_out, x0_out, coef,
                        row_elems, (unsigned)hw, noise, noise_rows, step, E);
+    IEF_LAUNCH_CHECK();
+    return IEF_OK;
+}
+
+// The same step at solver order 2 (dpmpp_mu_of, ddpm_step.h): coef = {a_from, a_to, sigma, dir, c2}, and x0_prev [row_elems] carries
+// the x0 prediction from one step to the next -- read (only where c2 != 0) and written by the lane that owns the element.  The
+// guidance is formed exactly as in ledits_ddpm_kernel; with c2 == 0 the outputs are that kernel's bit for bit.
+__global__ __launch_bounds__(256) void ledits_dpmpp_kernel(const float* __restrict__ eps, const float* __restrict__ mask,
+                                                           const float* __restrict__ scale, const float* __restrict__ x,
+                                                           float* __restrict__ xo, float* __restrict__ x0o,
+                                                           float* __restrict__ x0_prev, const float* __restrict__ coef,
+                                                           long long row_elems, unsigned hw, const float* __restrict__ noise,
+                                                           int noise_rows, const int* __restrict__ step, int E) {
+    const DdpmCoef c = ddpm_coef(coef);
+    const float c2 = coef[4];
+    const float* __restrict__ z = ddpm_noise_row(noise, noise_rows, step, row_elems);
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < row_elems; i += (long long)gridDim.x * 256) {
+        const unsigned p = (unsigned)i % hw;             // row_elems <= 16 * 16384
+        const float u = eps[i];
+        float g = 0.0f;
+        for (int e = 0; e < E; ++e) {
+            const float sc = scale[e];
+            if (sc == 0.0f) continue;
+            const float m = mask ? mask[(long long)e * hw + p] : 1.0f;
+            g = g + (sc * m) * (eps[(long long)(1 + e) * row_elems + i] - u);
+        }
+        const float x0p = c2 == 0.0f ? 0.0f : x0_prev[i];
+        float x0;
+        const float mu = dpmpp_mu_of(c, c2, u + g, x[i], x0p, &x0);
+        if (x0o) x0o[i] = x0;
+        x0_prev[i] = x0;
+        xo[i] = ddpm_add_noise(c, mu, z, i);
+    }
+}
+
+extern "C" int ief_ledits_dpmpp_step_f32(const float* eps, const float* mask, const float* scale, const float* x, float* x_out,
+                                         float* x0_out, float* x0_prev, const float* coef, long long row_elems, long long hw,
+                                         const float* noise, int noise_rows, const int* step, int E, void* stream) {
+    if (!eps || !scale || !x || !x_out || !x0_prev || !coef || !noise || !step) return IEF_EINVAL;
+    if (E < 1 || E > LEDITS_MAX_E || hw < 1 || hw > LEDITS_MAX_HW || row_elems < hw || row_elems % hw != 0 ||
+        row_elems / hw > LEDITS_MAX_C || noise_rows <= 0)
+        return IEF_ESHAPE;
+    if (((uintptr_t)eps | (uintptr_t)mask | (uintptr_t)scale | (uintptr_t)x | (uintptr_t)x_out | (uintptr_t)x0_out |
+         (uintptr_t)x0_prev | (uintptr_t)coef | (uintptr_t)noise | (uintptr_t)step) & 3)
+        return IEF_EALIGN;
+    const int grid = (int)((row_elems + 255) / 256);     // at most 1024 workgroups
+    hipLaunchKernelGGL(ledits_dpmpp_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, eps, mask, scale, x, x_out, x0_out, x0_prev,
+                       coef, row_elems, (unsigned)hw, noise, noise_rows, step, E);
     IEF_LAUNCH_CHECK();
     return IEF_OK;
 }

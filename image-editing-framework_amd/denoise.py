@@ -155,6 +155,16 @@ def check_noise_maps(maps, *, mode, cfg, uncond_list, source_trajectory, row_sha
         guidance_rows(guidance_scale, num_latents)
 
 
+def check_solver_order(solver_order, noise_maps):
+    """the solver order of a loop (raises ValueError): 1, or 2 for the second-order multistep SDE-DPM-Solver++, which steps on the
+    noise maps of an edit-friendly DDPM inversion extracted at that order and exists only with them"""
+    if isinstance(solver_order, bool) or solver_order not in (1, 2):
+        raise ValueError(f"solver_order must be 1 or 2, got {solver_order!r}")
+    if solver_order == 2 and noise_maps is None:
+        raise ValueError("solver_order=2: the second-order solver steps on the noise maps of an edit-friendly DDPM inversion "
+                         "(noise_maps=); every other loop is a DDIM loop")
+
+
 def check_edit_mask(mask, *, mode, cfg, uncond_list, noise_maps, source_trajectory, row_shape, num_steps, skip, num_latents):
     """the argument checks of a DiffEdit loop (host-side facts only; raises ValueError): `mask` is fp32 or bool [Bp, h, w] (or
     [h, w], shared by every row), nonzero = edited; `source_trajectory` is fp32 [S - skip, C, h, w] with row i = z*_{S-skip-1-i}, the
@@ -223,7 +233,7 @@ class FusedDenoiser:
                  mode: str = "denoise", uncond_list: Optional[List[torch.Tensor]] = None, use_graph: bool = True,
                  added_cond_kwargs=None, source_trajectory: Optional[torch.Tensor] = None,
                  noise_maps: Optional[torch.Tensor] = None, skip: int = 0, edit_mask: Optional[torch.Tensor] = None,
-                 ledits=None):
+                 ledits=None, solver_order: int = 1):
         """context: [2*Bp,77,C] (uncond, cond) for mode 'denoise' with CFG, [Bp,77,C] for 'invert' / no-CFG.
         added_cond_kwargs: SDXL's {"text_embeds" [B, 1280], "time_ids" [B, 6]} (one row per UNet batch row); they are
         constant over the steps, so they fold into the per-step time-embedding rows (then one row PER BATCH ROW).
@@ -238,7 +248,13 @@ class FusedDenoiser:
         after step i every row is x' inside its mask and the trajectory row outside it (a select, in the launch of the update).
         ledits, noise_maps, skip: LEDITS++ -- the 'ledits' `control.ControlPlan` registered on the UNet (E concepts); num_latents is
         1, context [1 + E, 77, C] = [uncond | concept_1 .. concept_E], guidance_scale None (the per-step scales are the plan's);
-        every row of the UNet batch is the one latent, and the step ends with the plan's masks and `ief_ledits_ddpm_step_f32`."""
+        every row of the UNet batch is the one latent, and the step ends with the plan's masks and `ief_ledits_ddpm_step_f32`.
+        solver_order (with noise_maps): 1 = the eta = 1 update; 2 = the second-order multistep SDE-DPM-Solver++ on maps extracted
+        at order 2 with the same skip (`DDPMInversion.noise_maps(solver_order=2)`): the loop owns the x0 prediction of the previous
+        step and a five-column coefficient table {a, p, sigma, dir, c2} (`DDIMScheduler.dpmpp_table`), and its step ends with
+        `ief_cfg_dpmpp_step_f32` / `ief_ledits_dpmpp_step_f32` inside the captured graph."""
+        check_solver_order(solver_order, noise_maps)
+        self.solver_order = solver_order
         self.model, self.unet, self.sched = model, model.unet, model.scheduler
         dev = self.unet.device
         self.mode = mode
@@ -292,7 +308,11 @@ class FusedDenoiser:
         if ledits is not None:              # every row of [uncond | concepts] is the one latent
             self.lat_in = torch.zeros(self.B, C, h, w, dtype=torch.float32, device=dev)
         self.step = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.coef_cur = torch.zeros(4, dtype=torch.float32, device=dev)
+        self.coef_cur = torch.zeros(5 if solver_order == 2 else 4, dtype=torch.float32, device=dev)
+        # order 2: the x0 prediction the previous step wrote.  Never zeroed: the first step of a run is order 1 and does not read it
+        self.x0_prev = None
+        if solver_order == 2:
+            self.x0_prev = torch.zeros((C, h, w) if ledits is not None else (self.Bp, C, h, w), dtype=torch.float32, device=dev)
         self.coef_table = self.temb_table = self.temb_cur = self.ctx = self.ctx_table = None
         # the graph READS this buffer (row = the device step counter): `rebind` copies the next image's rows into it
         self.traj = None if source_trajectory is None else source_trajectory.to(dev).contiguous().clone()
@@ -317,7 +337,10 @@ class FusedDenoiser:
             coef = [self.sched.reverse_coeffs(t) for t in ts]
         elif self.maps is not None:
             ts = ts[self.skip:]
-            coef = [self.sched.ddpm_coeffs(t) for t in ts]
+            if self.solver_order == 2:      # rows {a, p, sigma, dir, c2}: order 1 on the first and the last step of the run
+                coef = self.sched.dpmpp_table(self.skip, 2)
+            else:
+                coef = [self.sched.ddpm_coeffs(t) for t in ts]
         else:
             if self.mask is not None:       # DiffEdit decodes the tail of the schedule
                 ts = ts[self.skip:]
@@ -332,7 +355,7 @@ class FusedDenoiser:
             else:
                 cur.copy_(value)
 
-        if self.maps is not None:         # rows {a, p, sigma, dir}; the guidance scales travel per batch row
+        if self.maps is not None:         # rows {a, p, sigma, dir} (order 2: and c2); the guidance scales travel per batch row
             put("coef_table", torch.tensor(coef, dtype=torch.float32, device=dev))
             if self.ledits is None:
                 put("g_rows", torch.tensor(guidance_rows(guidance_scale, self.Bp), dtype=torch.float32, device=dev))
@@ -370,7 +393,8 @@ class FusedDenoiser:
                                         ledits=getattr(self, "ledits", None) is not None,
                                         **facts(tuple(self.lat.shape[-2:]), ctx_len))
 
-    def _key(self, context, uncond_list, source_trajectory=None, noise_maps=None, skip=0, edit_mask=None, ledits=None):
+    def _key(self, context, uncond_list, source_trajectory=None, noise_maps=None, skip=0, edit_mask=None, ledits=None,
+             solver_order=1):
         plan = self.unet._plan
         key = (id(self.unet), self.mode, self.Bp, tuple(self.lat.shape[-2:]), self.cfg, tuple(context.shape),
                None if uncond_list is None else len(uncond_list), len(self.sched.timesteps),
@@ -378,13 +402,18 @@ class FusedDenoiser:
                edit_mask is not None, source_trajectory is not None, noise_maps is not None,
                skip if (noise_maps is not None or edit_mask is not None) else 0, getattr(self.unet, "attn_key_splits", 1))
         # a LEDITS++ loop says so itself (its plan's signature, above, carries E, the mask mode and the module indices)
-        return key if ledits is None else key + ("ledits",)
+        key = key if ledits is None else key + ("ledits",)
+        # an order-1 loop keeps the key it always had; an order-2 loop (other launches, a wider table) names its solver
+        return key if solver_order == 1 else key + (("solver_order", solver_order),)
 
     def rebind(self, context, guidance_scale, uncond_list, added_cond_kwargs=None, source_trajectory=None, noise_maps=None,
-               skip=0, edit_mask=None, ledits=None):
+               skip=0, edit_mask=None, ledits=None, solver_order=1):
         """point a captured loop at the next image: new tables, new cross-attention K/V, the new controller's plan, the next
         image's inversion trajectory or noise maps and guidance scales, or its edit masks; a LEDITS++ loop takes the next
         image's concepts, scales and thresholds from the freshly registered plan"""
+        check_solver_order(solver_order, noise_maps)
+        if solver_order != self.solver_order:
+            raise ValueError(f"rebind: a loop captured at solver order {self.solver_order} serves only jobs of that order")
         if (ledits is None) != (self.ledits is None):
             raise ValueError("rebind: a LEDITS++ loop serves only LEDITS++ jobs, and the reverse")
         if ledits is not None:
@@ -442,7 +471,10 @@ class FusedDenoiser:
             # masked multi-concept guidance with the eta = 1 update (`ControlPlan.ledits_step`)
             self.lat_in.copy_(self.lat.expand_as(self.lat_in))
             eps = self.unet(self.lat_in, encoder_hidden_states=self.ctx, temb_row=self.temb_cur)["sample"]
-            self.plan.ledits_step(eps, self.lat, self.coef_cur, self.maps, self.step)
+            if self.x0_prev is None:
+                self.plan.ledits_step(eps, self.lat, self.coef_cur, self.maps, self.step)
+            else:
+                self.plan.ledits_step(eps, self.lat, self.coef_cur, self.maps, self.step, x0_prev=self.x0_prev)
             hip.advance_step(self.step)
             return
         if self.cfg and self.shared:
@@ -453,7 +485,10 @@ class FusedDenoiser:
                 self.lat_in[: self.Bp].copy_(self.lat)
                 self.lat_in[self.Bp:].copy_(self.lat)
             eps = self.unet(self.lat_in, encoder_hidden_states=self.ctx, temb_row=self.temb_cur)["sample"]
-        if self.maps is not None:
+        if self.maps is not None and self.solver_order == 2:
+            hip.cfg_dpmpp_step(eps[: self.Bp], eps[self.Bp:], self.lat, self.coef_cur, self.g_rows, self.maps, self.step, self.x0_prev,
+                               out=self.lat)
+        elif self.maps is not None:
             hip.cfg_ddpm_step(eps[: self.Bp], eps[self.Bp:], self.lat, self.coef_cur, self.g_rows, self.maps, self.step, out=self.lat)
         elif self.mask is not None:
             hip.cfg_ddim_step(eps[: self.Bp], eps[self.Bp:], self.lat, self.coef_cur, out=self.lat,
@@ -612,7 +647,10 @@ class CfgSplitDenoiser(FusedDenoiser):
     (`p2p.model.register.register_attention_control`); its counters advance on both."""
 
     def __init__(self, model, context, num_latents, latent_hw, guidance_scale: float, group=None, uncond_list=None,
-                 use_graph: bool = True, source_trajectory=None, noise_maps=None, skip=0, edit_mask=None):
+                 use_graph: bool = True, source_trajectory=None, noise_maps=None, skip=0, edit_mask=None, solver_order=1):
+        if solver_order != 1:
+            raise ValueError("CFG split: the second-order solver steps on DDPM noise maps, which are not built for the two-GPU "
+                             "split; run the edit on one GPU")
         if getattr(model.unet._plan, "kind", None) == "ledits":
             raise ValueError("CFG split: LEDITS++ runs [uncond | concepts] on one latent, not two halves; run the edit on one GPU")
         if edit_mask is not None:
@@ -723,31 +761,34 @@ class CfgSplitDenoiser(FusedDenoiser):
 
 def acquire(model, context, num_latents, latent_hw, guidance_scale, mode="denoise", uncond_list=None,
             use_graph=True, added_cond_kwargs=None, source_trajectory=None, noise_maps=None, skip=0,
-            edit_mask=None, ledits=None) -> FusedDenoiser:
+            edit_mask=None, ledits=None, solver_order=1) -> FusedDenoiser:
     """a FusedDenoiser for this job: a pooled one with a captured graph of the same shape / plan signature, re-pointed
     at the new context, tables and controller — or a new one.  source_trajectory: Direct Inversion (`FusedDenoiser`); loops
     with and without one never share a pool entry.  noise_maps, skip: edit-friendly DDPM inversion (`FusedDenoiser`;
     guidance_scale may then be one scale per latent); presence of maps and skip are part of the pool key.  edit_mask (with
     source_trajectory and skip): DiffEdit (`FusedDenoiser`); loops with and without a mask never share a pool entry.  ledits (with
     noise_maps and skip; guidance_scale None): LEDITS++ (`FusedDenoiser`), the 'ledits' plan registered on the UNet -- its signature
-    (E, the mask mode, the module indices) is part of the pool key, so pooled loops of different kinds never mix"""
+    (E, the mask mode, the module indices) is part of the pool key, so pooled loops of different kinds never mix.  solver_order
+    (with noise_maps): 2 = the second-order SDE-DPM-Solver++ step (`FusedDenoiser`); part of the pool key, order-1 keys unchanged"""
+    check_solver_order(solver_order, noise_maps)
     if REUSE_GRAPHS and use_graph:
         probe = FusedDenoiser.__new__(FusedDenoiser)
         probe.unet, probe.sched, probe.mode = model.unet, model.scheduler, mode
         probe.cfg, probe.Bp, probe.ledits = guidance_scale is not None, num_latents, ledits
         probe.lat = torch.empty(0, 0, *latent_hw)
-        key = probe._key(context, uncond_list, source_trajectory, noise_maps, skip, edit_mask, ledits)
+        key = probe._key(context, uncond_list, source_trajectory, noise_maps, skip, edit_mask, ledits, solver_order)
         free = _POOL.get(key)
         if free:
             loop = free.pop()
-            loop.rebind(context, guidance_scale, uncond_list, added_cond_kwargs, source_trajectory, noise_maps, skip, edit_mask, ledits)
+            loop.rebind(context, guidance_scale, uncond_list, added_cond_kwargs, source_trajectory, noise_maps, skip, edit_mask, ledits,
+                        solver_order)
             return loop
         loop = FusedDenoiser(model, context, num_latents, latent_hw, guidance_scale, mode, uncond_list, use_graph,
-                             added_cond_kwargs, source_trajectory, noise_maps, skip, edit_mask, ledits)
+                             added_cond_kwargs, source_trajectory, noise_maps, skip, edit_mask, ledits, solver_order)
         loop._pool_key = key
         return loop
     return FusedDenoiser(model, context, num_latents, latent_hw, guidance_scale, mode, uncond_list, use_graph,
-                         added_cond_kwargs, source_trajectory, noise_maps, skip, edit_mask, ledits)
+                         added_cond_kwargs, source_trajectory, noise_maps, skip, edit_mask, ledits, solver_order)
 
 
 def drop_pool():

@@ -1855,6 +1855,70 @@ def ddpm_noise_maps(eps_u, eps_c, x_t, x_prev, coef_rows, out=None):
     return out
 
 
+def cfg_dpmpp_step(eps_u, eps_c, x, coef, g_rows, noise, step, x0_prev, out=None, x0_out=None):
+    """`cfg_ddpm_step` at solver order 2 (`ief_cfg_dpmpp_step_f32`, second-order multistep SDE-DPM-Solver++):
+        mu = sqrt(a_to) x0 + dir eps + c2 (x0 - x0_prev);  x'[b] = mu + sigma noise[clamp(step[0])];  x0_prev := x0
+    coef = device fp32 [a_from, a_to, sigma, dir, c2] (`DDIMScheduler.dpmpp_coeffs`); x0_prev device fp32 of x's shape, updated in
+    place -- with c2 == 0 it is not read into the result and the outputs are `cfg_ddpm_step`'s bit for bit.  Everything else as
+    there."""
+    lib = load()
+    _dev32(eps_c, "eps_c")
+    _dev32(x, "x")
+    _dev32(coef, "coef")
+    _dev32(noise, "noise maps")
+    if eps_u is not None:
+        _dev32(eps_u, "eps_u")
+        _dev32(g_rows, "g_rows")
+    if x.dim() < 2 or eps_c.shape != x.shape or (eps_u is not None and eps_u.shape != x.shape):
+        raise ValueError(f"cfg_dpmpp_step: eps and x must be [Bp, ...] of one shape, got {tuple(eps_c.shape)} and {tuple(x.shape)}")
+    if coef.numel() != 5:
+        raise ValueError(f"cfg_dpmpp_step: coef is [a_from, a_to, sigma, dir, c2], got {coef.numel()} elements")
+    if eps_u is not None and g_rows.numel() != x.shape[0]:
+        raise ValueError(f"cfg_dpmpp_step: {g_rows.numel()} guidance scales for {x.shape[0]} batch rows")
+    if noise.dim() != x.dim() or noise.shape[0] < 1 or noise.shape[1:] != x.shape[1:]:
+        raise ValueError(f"cfg_dpmpp_step: the noise maps must be [steps, {', '.join(map(str, x.shape[1:]))}] (x without its batch "
+                         f"dimension), got {tuple(noise.shape)}")
+    if _devi32(step, "step") is None or step.numel() != 1:
+        raise TypeError("step: expected a device int32 tensor of one element")
+    if x0_prev is None or _dev32(x0_prev, "x0_prev").shape != x.shape:
+        raise ValueError("cfg_dpmpp_step: x0_prev must have the shape of x")
+    if out is None:
+        out = torch.empty_like(x)
+    for t, name in ((out, "out"), (x0_out, "x0_out")):
+        if t is not None and (_dev32(t, name).shape != x.shape):
+            raise ValueError(f"cfg_dpmpp_step: {name} must have the shape of x")
+    _check(lib.ief_cfg_dpmpp_step_f32(_ptr(eps_u), eps_c.data_ptr(), x.data_ptr(), out.data_ptr(), _ptr(x0_out), x0_prev.data_ptr(),
+                                      coef.data_ptr(), _ptr(g_rows) if eps_u is not None else None, x.numel(), x[0].numel(),
+                                      noise.data_ptr(), noise.shape[0], step.data_ptr(), _stream()), "ief_cfg_dpmpp_step_f32")
+    return out
+
+
+def dpmpp_noise_maps(eps_u, eps_c, x_t, x_prev, coef_rows, x0_carry, out=None):
+    """`ddpm_noise_maps` under the order-2 mean (`ief_dpmpp_noise_maps_f32`): the R rows are CONSECUTIVE timesteps of one image,
+    z[r] = (x_prev[r] - mu_r) / sigma_r with mu_r = mu1_r + c2_r (x0_r - x0_{r-1}), x0_r the x0 prediction of row r's own eps.
+    coef_rows device fp32 [R, 6] = [a_from, a_to, sigma, dir, guidance, c2] per row; x0_carry device fp32 of one row's shape: the
+    x0 of the row before row 0 (not read into the result where c2_0 == 0), overwritten with row R - 1's -- so chunks launched in
+    order give the bits of one launch."""
+    lib = load()
+    for t, name in ((eps_c, "eps_c"), (x_t, "x_t"), (x_prev, "x_prev"), (coef_rows, "coef_rows")) + (
+            () if eps_u is None else ((eps_u, "eps_u"),)) + (() if out is None else ((out, "out"),)):
+        _dev32(t, name)
+    if x_t.dim() < 2 or any(t.shape != x_t.shape for t in (eps_c, x_prev) + (() if eps_u is None else (eps_u,)) +
+                            (() if out is None else (out,))):
+        raise ValueError(f"dpmpp_noise_maps: eps, x_t, x_prev and out must be [R, ...] of one shape ({tuple(x_t.shape)})")
+    if tuple(coef_rows.shape) != (x_t.shape[0], 6):
+        raise ValueError(f"dpmpp_noise_maps: coef_rows must be [{x_t.shape[0]}, 6] = [a_from, a_to, sigma, dir, guidance, c2] per "
+                         f"row, got {tuple(coef_rows.shape)}")
+    if x0_carry is None or _dev32(x0_carry, "x0_carry").shape != x_t.shape[1:]:
+        raise ValueError(f"dpmpp_noise_maps: x0_carry must be one row [{', '.join(map(str, x_t.shape[1:]))}]")
+    if out is None:
+        out = torch.empty_like(x_t)
+    _check(lib.ief_dpmpp_noise_maps_f32(_ptr(eps_u), eps_c.data_ptr(), x_t.data_ptr(), x_prev.data_ptr(), out.data_ptr(),
+                                        coef_rows.data_ptr(), x0_carry.data_ptr(), x_t.shape[0], x_t[0].numel(), _stream()),
+           "ief_dpmpp_noise_maps_f32")
+    return out
+
+
 def diffedit_map_accum(eps_a, eps_b, acc):
     """DiffEdit's difference map (`ief_diffedit_map_accum_f32`): acc[p] += sum_r sum_c |eps_a[r, c, p] - eps_b[r, c, p]| in row and
     channel order, every operation rounded in fp32 -- chunking the rows over launches does not change a bit.  eps_a, eps_b device
@@ -1985,6 +2049,42 @@ def ledits_ddpm_step(eps, mask, scale, x, coef, noise, step, out=None, x0_out=No
     _check(lib.ief_ledits_ddpm_step_f32(eps.data_ptr(), _ptr(mask), scale.data_ptr(), x.data_ptr(), out.data_ptr(), _ptr(x0_out),
                                         coef.data_ptr(), x.numel(), hw, noise.data_ptr(), noise.shape[0], step.data_ptr(), E,
                                         _stream()), "ief_ledits_ddpm_step_f32")
+    return out
+
+
+def ledits_dpmpp_step(eps, mask, scale, x, coef, noise, step, x0_prev, out=None, x0_out=None):
+    """`ledits_ddpm_step` at solver order 2 (`ief_ledits_dpmpp_step_f32`): the same masked multi-concept guidance, then the mean of
+    `cfg_dpmpp_step` (one device function), mu = mu1 + c2 (x0 - x0_prev), x0_prev := x0.  coef = device fp32 [a_from, a_to, sigma,
+    dir, c2]; x0_prev device fp32 of x's shape, updated in place; with c2 == 0 the outputs are `ledits_ddpm_step`'s bit for bit."""
+    lib = load()
+    for t, name in ((eps, "eps"), (scale, "scale"), (x, "x"), (coef, "coef"), (noise, "noise maps")):
+        _dev32(t, name)
+    if eps.dim() != 4 or eps.shape[0] < 2:
+        raise ValueError(f"ledits_dpmpp_step: eps must be [1 + E, C, h, w] with E >= 1, got {tuple(eps.shape)}")
+    E, hw = eps.shape[0] - 1, eps.shape[2] * eps.shape[3]
+    if x.numel() != eps[0].numel() or tuple(x.shape[-3:]) != tuple(eps.shape[1:]):
+        raise ValueError(f"ledits_dpmpp_step: x is ONE latent [{', '.join(map(str, eps.shape[1:]))}], got {tuple(x.shape)}")
+    if mask is not None and tuple(_dev32(mask, "mask").shape) != (E,) + tuple(eps.shape[2:]):
+        raise ValueError(f"ledits_dpmpp_step: mask must be [{E}, {eps.shape[2]}, {eps.shape[3]}], got {tuple(mask.shape)}")
+    if scale.numel() != E:
+        raise ValueError(f"ledits_dpmpp_step: {scale.numel()} scales for {E} concepts")
+    if coef.numel() != 5:
+        raise ValueError(f"ledits_dpmpp_step: coef is [a_from, a_to, sigma, dir, c2], got {coef.numel()} elements")
+    if noise.dim() != 4 or noise.shape[0] < 1 or noise.shape[1:] != eps.shape[1:]:
+        raise ValueError(f"ledits_dpmpp_step: the noise maps must be [steps, {', '.join(map(str, eps.shape[1:]))}], got "
+                         f"{tuple(noise.shape)}")
+    if _devi32(step, "step") is None or step.numel() != 1:
+        raise TypeError("step: expected a device int32 tensor of one element")
+    if x0_prev is None or _dev32(x0_prev, "x0_prev").numel() != x.numel():
+        raise ValueError("ledits_dpmpp_step: x0_prev must hold one latent, as x")
+    if out is None:
+        out = torch.empty_like(x)
+    for t, name in ((out, "out"), (x0_out, "x0_out")):
+        if t is not None and (_dev32(t, name).shape != x.shape):
+            raise ValueError(f"ledits_dpmpp_step: {name} must have the shape of x")
+    _check(lib.ief_ledits_dpmpp_step_f32(eps.data_ptr(), _ptr(mask), scale.data_ptr(), x.data_ptr(), out.data_ptr(), _ptr(x0_out),
+                                         x0_prev.data_ptr(), coef.data_ptr(), x.numel(), hw, noise.data_ptr(), noise.shape[0],
+                                         step.data_ptr(), E, _stream()), "ief_ledits_dpmpp_step_f32")
     return out
 
 

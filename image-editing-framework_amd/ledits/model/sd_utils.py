@@ -94,15 +94,21 @@ class LEDITS:
     latent2image = P2P.latent2image             # (vae, latents) -> uint8 [B, H, W, 3]
     image2latent = ddim_inversion.image2latent
 
-    def __init__(self, pipe, num_steps) -> None:
+    def __init__(self, pipe, num_steps, solver_order=1) -> None:
+        """solver_order 2: inversion and edit on the second-order multistep SDE-DPM-Solver++ (the paper's solver, meant for about
+        20 steps); 1 (default): the eta = 1 DDPM update"""
+        if isinstance(solver_order, bool) or solver_order not in (1, 2):
+            raise ValueError(f"LEDITS++: solver_order must be 1 or 2, got {solver_order!r}")
         self.model = pipe
+        self.solver_order = solver_order
         pipe.scheduler.set_timesteps(num_steps)
 
     @torch.no_grad()
     def invert(self, pipe, x0, source_prompt="", source_guidance_scale=3.5, skip=7, rows_per_launch=4, generator=None):
         """-> (y_skip [1, C, h, w], maps fp32 [S - skip, C, h, w]); an empty source prompt runs the unconditional-only extraction"""
         y, maps, _ = DDPMInversion().noise_maps(pipe, x0, [source_prompt], guidance_scale=source_guidance_scale, skip=skip,
-                                                rows_per_launch=rows_per_launch, generator=generator)
+                                                rows_per_launch=rows_per_launch, generator=generator,
+                                                solver_order=self.solver_order)
         return y, maps
 
     @torch.no_grad()
@@ -120,7 +126,7 @@ class LEDITS:
         register_ledits(pipe, plan)
         try:
             loop = acquire(pipe, torch.cat([uncond[:1], cond]), 1, hw, None, noise_maps=maps, skip=skip, ledits=plan,
-                           use_graph=use_graph)
+                           use_graph=use_graph, solver_order=self.solver_order)
             try:
                 if not keep_masks or not (cross_attn_mask or intersect_mask):
                     return loop.run(y_skip), None

@@ -5,7 +5,8 @@ Per image: encode -> the edit-friendly DDPM inversion under `--source_prompt` (e
 per UNet launch) -> the edit from step `--skip` on at UNet batch 1 + E -> `source.png / inversion.png / edit.png` under
 `./test_exp/<relpath>`.  The dataset brings a target prompt and no concepts: `--edit_prompt` names them for every image, and without it
 the item's target prompt is the one concept.  Image i of the dataset draws the noise of its inversion from a CPU generator seeded
-`--seed` + i, whatever the sharding.  `--synthetic N` replaces the (unavailable) PIE download.  Not for SDXL pipelines."""
+`--seed` + i, whatever the sharding.  `--synthetic N` replaces the (unavailable) PIE download.  Not for SDXL pipelines.
+`--num_steps N --solver_order 2`: N steps of the second-order multistep SDE-DPM-Solver++ for inversion and edit (`edit_real.py`)."""
 import argparse
 import json
 import os
@@ -48,7 +49,7 @@ def main(argv=None):
         dist = init_distributed(device)       # rank 0 loads the weights; `load_pipe` broadcasts them (RCCL over xGMI)
     seed_everything(args.seed)
     pipe = load_pipe(args.sd_version, device, precision=args.precision)
-    editor = LEDITS(pipe, NUM_STEPS)
+    editor = LEDITS(pipe, args.num_steps, args.solver_order)
     size = pipe.unet.config.sample_size * pipe.vae_scale_factor
     if args.synthetic > 0:
         root = os.path.join(args.exp_path, "_synthetic_inputs")

@@ -22,7 +22,17 @@ y_S = x0 up to rounding, the target rows take a stronger scale.
 The published code zeroes the last map (its final step is deterministic).  Here EVERY map is kept: with z_{S-1} the source row ends
 on x0 itself, not on the mean of the last step, which is what "the source row reproduces the image" asks for.
 
-Out of scope: SDXL pipelines, eta != 1, chunks that mix rows of several images.
+`solver_order=2` extracts the maps of the second-order multistep SDE-DPM-Solver++ instead (the solver LEDITS++ is published with, for
+about 20 steps).  Its first-order coefficients ARE sigma_i and dir_i, so only the mean changes, by one term on the x0 predictions of
+two consecutive rows:
+
+    x0_i = (y_i - sqrt(1 - a_i) eps_i) / sqrt(a_i);   mu_i = sqrt(p_i) x0_i + dir_i eps_i + c2_i (x0_i - x0_{i-1})
+
+with c2_i from `DDIMScheduler.dpmpp_coeffs` and c2 = 0 on row `skip` and on row S - 1 (`dpmpp_orders`).  x0_{i-1} comes from the UNet
+output at row i - 1, not from a stepped latent: still no chain, and one carry buffer hands it from chunk to chunk
+(`ief_dpmpp_noise_maps_f32`).  The edit must run the same `skip` at order 2 (`ief_cfg_dpmpp_step_f32`).
+
+Out of scope: SDXL pipelines, eta != 1, chunks that mix rows of several images, solver orders above 2.
 """
 import torch
 
@@ -51,14 +61,18 @@ class DDPMInversion(ddim_inversion):
         return torch.cat([xts, x0c[None]]).to(x0.device).contiguous()
 
     @torch.no_grad()
-    def noise_maps(self, model, x0, prompt, guidance_scale=3.5, skip=0, rows_per_launch=4, generator=None, uncond_only=None):
+    def noise_maps(self, model, x0, prompt, guidance_scale=3.5, skip=0, rows_per_launch=4, generator=None, uncond_only=None,
+                   solver_order=1):
         """-> (y_skip [1, C, h, w], maps fp32 [S - skip, C, h, w], xts [S + 1, C, h, w]).  guidance_scale 3.5 and skip 0 are the
         paper's extraction defaults (its edits then skip 36 % of the steps).  Rows skip ... S - 1 go through the UNet
         `rows_per_launch` at a time: one forward at batch 2 K = [K unconditional | K conditional] rows with the chunk's K
         time-embedding rows repeated for both halves, then one extraction launch.  The last chunk is simply shorter (eager
         launches: nothing is captured, so nothing needs padding).  uncond_only: None = the unconditional-only form (batch K, one
         half) exactly when the source prompt is empty; False forces both halves (what an empty prompt ran before that form existed);
-        True with a non-empty prompt is a ValueError."""
+        True with a non-empty prompt is a ValueError.  solver_order 2: the maps of the second-order multistep SDE-DPM-Solver++
+        (`DDIMScheduler.dpmpp_coeffs`; rows skip and S - 1 are order 1, `dpmpp_orders`), for an edit that runs the same skip at
+        order 2: the mean of row i takes c2_i (x0_i - x0_{i-1}) with both x0 predictions from the rows' own UNet outputs -- still
+        no chain -- and one carry buffer hands x0 from a chunk's last row to the next chunk (`ief_dpmpp_noise_maps_f32`)."""
         unet, sched = model.unet, model.scheduler
         if not (all(m.is_native() for m in unet.attention_modules()) and getattr(unet, "_plan", None) is None):
             raise RuntimeError("DDPMInversion: an attention hook is installed; invert before registering controllers")
@@ -79,7 +93,15 @@ class DDPMInversion(ddim_inversion):
         xts = self.sample_xts(model, x0.to(dev), generator)
         uncond, cond = self.get_context(model, prompt).chunk(2)
         g = float(guidance_scale)
-        coef = torch.tensor([[*sched.ddpm_coeffs(t), g] for t in ts], dtype=torch.float32, device=dev)
+        if solver_order not in (1, 2):
+            raise ValueError(f"noise_maps: solver_order must be 1 or 2, got {solver_order!r}")
+        carry = None
+        if solver_order == 2:           # rows {a, p, sigma, dir, g, c2}; rows before `skip` are not extracted (placeholders)
+            rows = [(0.0,) * 5] * skip + sched.dpmpp_table(skip, 2)
+            coef = torch.tensor([[*r[:4], g, r[4]] for r in rows], dtype=torch.float32, device=dev)
+            carry = torch.empty(xts.shape[1:], dtype=torch.float32, device=dev)       # first read after row `skip` wrote it
+        else:
+            coef = torch.tensor([[*sched.ddpm_coeffs(t), g] for t in ts], dtype=torch.float32, device=dev)
         temb = unet.time_rows(torch.tensor(ts, dtype=torch.float32, device=dev))          # [S, width]
         maps = torch.empty(S - skip, *xts.shape[1:], dtype=torch.float32, device=dev)
         # an EMPTY source prompt (LEDITS++'s default) makes the conditional row the unconditional one: eps_u + g (eps_c - eps_u) is
@@ -88,6 +110,13 @@ class DDPMInversion(ddim_inversion):
             uncond_only = prompt[0] == ""
         elif uncond_only and prompt[0] != "":
             raise ValueError("noise_maps: the unconditional-only form stands for an EMPTY source prompt")
+
+        def extract(eu, ec, y, y_next, rows, out):
+            if carry is None:
+                hip.ddpm_noise_maps(eu, ec, y, y_next, rows, out=out)
+            else:
+                hip.dpmpp_noise_maps(eu, ec, y, y_next, rows, carry, out=out)
+
         ctxs = {}       # one context tensor per chunk size: the cross-attention K/V cache is keyed on the tensor, so the full
         for r0 in range(skip, S, K):      # chunks project their K/V once
             r1 = min(r0 + K, S)
@@ -100,8 +129,8 @@ class DDPMInversion(ddim_inversion):
             rows = temb[r0:r1]
             if uncond_only:
                 eps = unet(y.contiguous(), encoder_hidden_states=ctx, temb_row=rows.contiguous())["sample"]
-                hip.ddpm_noise_maps(None, eps, y, xts[r0 + 1:r1 + 1], coef[r0:r1], out=maps[r0 - skip:r1 - skip])
+                extract(None, eps, y, xts[r0 + 1:r1 + 1], coef[r0:r1], out=maps[r0 - skip:r1 - skip])
                 continue
             eps = unet(torch.cat([y, y]), encoder_hidden_states=ctx, temb_row=torch.cat([rows, rows]).contiguous())["sample"]
-            hip.ddpm_noise_maps(eps[:k], eps[k:], y, xts[r0 + 1:r1 + 1], coef[r0:r1], out=maps[r0 - skip:r1 - skip])
+            extract(eps[:k], eps[k:], y, xts[r0 + 1:r1 + 1], coef[r0:r1], out=maps[r0 - skip:r1 - skip])
         return xts[skip:skip + 1].clone(), maps, xts

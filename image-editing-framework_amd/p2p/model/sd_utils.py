@@ -24,7 +24,7 @@ import torch
 from tqdm import tqdm
 
 from ... import hip
-from ...denoise import acquire, check_noise_maps, check_source_trajectory, guidance_rows, run_interleaved
+from ...denoise import acquire, check_noise_maps, check_solver_order, check_source_trajectory, guidance_rows, run_interleaved
 from .register import register_attention_control, unregister_attention_control
 
 
@@ -86,7 +86,7 @@ class P2P:
                               latent: Optional[torch.FloatTensor] = None, low_resource: bool = False,
                               uncond_embeddings_list=None, height: Optional[int] = None, width: Optional[int] = None,
                               return_latents: bool = False, cfg_split_group=None, source_trajectory=None, noise_maps=None,
-                              skip: int = 0):
+                              skip: int = 0, solver_order: int = 1):
         """cfg_split_group (not a reference argument): a torch.distributed group of TWO ranks that run this ONE edit
         together — rank 0 the unconditional rows of the CFG batch, rank 1 the conditional rows, one eps exchange per
         step (`denoise.CfgSplitDenoiser`); both ranks return the same latents / images.
@@ -96,7 +96,10 @@ class P2P:
         noise_maps, skip (not reference arguments): edit-friendly DDPM inversion -- fp32 [S - skip, C, h, w] from
         `inversion.ddpm.DDPMInversion.noise_maps`, `latent` = its y_skip; the edit runs `timesteps[skip:]` (the controller counts
         them from 0), every step is the eta = 1 update with that step's map on every row, and `guidance_scale` may be a sequence
-        of one scale per prompt (the source prompt takes the scale the maps were extracted with)."""
+        of one scale per prompt (the source prompt takes the scale the maps were extracted with).
+        solver_order (with noise_maps): 2 = the second-order multistep SDE-DPM-Solver++ step on maps extracted at order 2 with the
+        same skip (`DDPMInversion.noise_maps(solver_order=2)`); 1 (default) = the eta = 1 update."""
+        check_solver_order(solver_order, noise_maps)
         if source_trajectory is not None and uncond_embeddings_list is not None:
             raise ValueError("source_trajectory together with uncond_embeddings_list: choose Direct Inversion or null-text "
                              "embeddings, not both")
@@ -129,7 +132,7 @@ class P2P:
         if _fusable(model, controller, low_resource):
             loop = acquire(model, context, batch_size, (height // 8, width // 8), guidance_scale,
                                  uncond_list=uncond_embeddings_list, added_cond_kwargs=added_cond_kwargs,
-                                 source_trajectory=source_trajectory, noise_maps=noise_maps, skip=skip)
+                                 source_trajectory=source_trajectory, noise_maps=noise_maps, skip=skip, solver_order=solver_order)
             try:
                 latents = loop.run(latents)
             finally:
@@ -143,6 +146,9 @@ class P2P:
             step = torch.zeros(1, dtype=torch.int32, device=model.device)
             g_rows = torch.tensor(guidance_rows(guidance_scale, batch_size), dtype=torch.float32, device=model.device)
             ddpm = (noise_maps.to(model.device).contiguous(), g_rows, step)
+            if solver_order == 2:       # the loop's own x0 prediction of the previous step, and the five-column row of each timestep
+                ts = model.scheduler.timesteps[skip:].tolist()
+                ddpm += (torch.zeros_like(latents, dtype=torch.float32), dict(zip(ts, model.scheduler.dpmpp_table(skip, 2))))
             for i, t in enumerate(tqdm(model.scheduler.timesteps[skip:], desc="Now doing P2P editing")):
                 step.fill_(i)               # the host's step index, where the captured loop reads its device counter
                 latents = self.diffusion_step(model, controller, latents, context, t, None, ddpm=ddpm)
@@ -213,7 +219,8 @@ class P2P:
         [(prompts, controller, x_T, uncond_embeddings_list)] (null-text embeddings, as `P2P_NTI`) or
         [(prompts, controller, x_T, None, source_trajectory)] (Direct Inversion, as `text2image_ldm_stable`) or
         [(prompts, controller, y_skip, None, None, (noise_maps, skip, guidance scales))] (edit-friendly DDPM inversion: the sixth
-        element; its scales, one per prompt or one number, replace `guidance_scale` for that job);
+        element; its scales, one per prompt or one number, replace `guidance_scale` for that job; a fourth entry is the job's
+        solver order, 1 where it is left out);
         every controller must be one of the lowered classes.  Each job's loop is captured while its controller is
         registered, then all loops are stepped in turn on their own streams (`denoise.run_interleaved`).  Returns
         [(images uint8 [len(prompts),H,W,3], x_T)] — the same values as one `text2image_ldm_stable` call per job."""
@@ -228,7 +235,8 @@ class P2P:
                 source_trajectory = job[4] if len(job) > 4 else None
                 if source_trajectory is not None and uncond_list is not None:
                     raise ValueError("edit_many: a job brings a source trajectory or null-text embeddings, not both")
-                noise_maps, skip, g_job = job[5] if len(job) > 5 and job[5] is not None else (None, 0, guidance_scale)
+                noise_maps, skip, g_job = job[5][:3] if len(job) > 5 and job[5] is not None else (None, 0, guidance_scale)
+                solver_order = job[5][3] if len(job) > 5 and job[5] is not None and len(job[5]) > 3 else 1
                 if noise_maps is not None and (uncond_list is not None or source_trajectory is not None):
                     raise ValueError("edit_many: a job brings ONE of noise maps, a source trajectory and null-text embeddings")
                 register_attention_control(model, controller)
@@ -240,7 +248,7 @@ class P2P:
                 loop = acquire(model, torch.cat([uncond_embeddings, text_embeddings]), len(prompt),
                                      (height // 8, width // 8), g_job, uncond_list=uncond_list,
                                      added_cond_kwargs=added_cond_kwargs, source_trajectory=source_trajectory,
-                                     noise_maps=noise_maps, skip=skip)
+                                     noise_maps=noise_maps, skip=skip, solver_order=solver_order)
                 loop.start(latents)
                 loops.append(loop)
                 firsts.append(latent)
@@ -257,7 +265,8 @@ class P2P:
         """one eager step (`sd_utils.py:67-79`, XL: :175-186); CFG + DDIM update fused in one kernel.  rect = (trajectory, step):
         Direct Inversion's move of the source row in that kernel (`hip.cfg_ddim_step`), in front of the controller's callback as
         in the captured step.  ddpm = (noise maps, g_rows, step): the eta = 1 update of an edit-friendly DDPM inversion edit instead
-        (`hip.cfg_ddpm_step`; guidance_scale is then unused), likewise in front of the callback."""
+        (`hip.cfg_ddpm_step`; guidance_scale is then unused), likewise in front of the callback; with two more entries (x0_prev,
+        {timestep: dpmpp_coeffs row}) the second-order step (`hip.cfg_dpmpp_step`, x0_prev updated in place)."""
         latents = latents.float().contiguous()
         if low_resource:
             bp = latents.shape[0]
@@ -269,7 +278,11 @@ class P2P:
                              added_cond_kwargs=added_cond_kwargs)["sample"]
             eps_u, eps_c = eps.chunk(2)
         if ddpm is not None:
-            maps, g_rows, step = ddpm
+            maps, g_rows, step = ddpm[:3]
+            if len(ddpm) > 3:
+                coef = torch.tensor(ddpm[4][int(t)], dtype=torch.float32, device=latents.device)
+                latents = hip.cfg_dpmpp_step(eps_u.contiguous(), eps_c.contiguous(), latents, coef, g_rows, maps, step, ddpm[3])
+                return latents if controller is None else controller.step_callback(latents)
             coef = torch.tensor(model.scheduler.ddpm_coeffs(int(t)), dtype=torch.float32, device=latents.device)
             latents = hip.cfg_ddpm_step(eps_u.contiguous(), eps_c.contiguous(), latents, coef, g_rows, maps, step)
             return latents if controller is None else controller.step_callback(latents)

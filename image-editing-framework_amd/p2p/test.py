@@ -27,7 +27,8 @@ chain: `--invert_batch K` is the number of ROWS (timesteps of ONE image) per UNe
 edits as for `ddim`.  `--ddpm_guidance_src 3.5` / `--ddpm_guidance_tar 15` / `--skip 18` (36 % of the 50 steps) are the paper's
 settings; image i of a shard draws its noise from a CPU generator seeded `--seed` + i, whatever the schedule.  `--in_flight` does not
 change the pixels; K is part of the numerics in the fp32-storage modes (a batched forward equals batch-1 forwards to 1e-6 of eps, as
-for the batched DDIM inversion).  Not for SDXL pipelines.
+for the batched DDIM inversion).  Not for SDXL pipelines.  `--num_steps N --solver_order 2` (ddpm only): N steps of the second-order
+multistep SDE-DPM-Solver++ for inversion and edit (`edit_real.py`); `--skip` then defaults to int(0.36 N).
 """
 import argparse
 import json
@@ -148,7 +149,7 @@ def run_items(pipe, editor, invertor, items, size, device, inversion_type="ddim"
 def _run_ddpm_chunk(pipe, editor, invertor, chunk, originals, device, ddpm, first_index):
     """edit-friendly DDPM inversion of the images of `chunk` (one after the other: every image fills its own UNet batches), then
     their edits in flight through `P2P.edit_many` -> [uint8 images [2,H,W,3]] per image, those of `edit_one` on each"""
-    S, skip = 50, ddpm["skip"]
+    S, skip, order = ddpm.get("num_steps", 50), ddpm["skip"], ddpm.get("solver_order", 1)
     jobs, ctrls = [], []
     for j, ((_, src, tgt), im) in enumerate(zip(chunk, originals)):
         latent = invertor.image2latent(model=pipe, image=im, device=device, dtype=torch.float32)
@@ -157,7 +158,7 @@ def _run_ddpm_chunk(pipe, editor, invertor, chunk, originals, device, ddpm, firs
         ctrl = cls(prompts=[src, tgt], tokenizer=pipe.tokenizer, num_steps=S - skip, cross_replace_steps=0.8,
                    self_replace_steps=0.6, device=device)
         ctrls.append(ctrl)
-        jobs.append(([src, tgt], ctrl, y_skip, None, None, (maps, skip, (ddpm["guidance_src"], ddpm["guidance_tar"]))))
+        jobs.append(([src, tgt], ctrl, y_skip, None, None, (maps, skip, (ddpm["guidance_src"], ddpm["guidance_tar"]), order)))
     results = [im for im, _ in editor.edit_many(pipe, jobs, num_inference_steps=S)]
     for ctrl in ctrls:
         ctrl.reset()
@@ -222,7 +223,7 @@ def main(argv=None):
         editor = (P2P_XL if xl else P2P)(model=pipe, num_inference_steps=50)
         invertor = DirectInversion_XL() if xl else DirectInversion()
     elif args.inversion_type == "ddpm":
-        editor = P2P(model=pipe, num_inference_steps=50)
+        editor = P2P(model=pipe, num_inference_steps=args.num_steps)
         invertor = DDPMInversion()
     else:
         raise ValueError("Please choose right inversion type")

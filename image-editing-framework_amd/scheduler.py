@@ -99,6 +99,51 @@ class DDIMScheduler:
         return a_t, a_p, float(np.float32(np.sqrt(v))), float(np.float32(np.sqrt(d)))
 
     @staticmethod
+    def dpmpp_c2(a_before: float, a_t: float, a_prev: float) -> float:
+        """the coefficient of the second-order correction of the multistep SDE-DPM-Solver++ step a_t -> a_prev that follows the
+        step a_before -> a_t: with lambda(a) = 1/2 log(a / (1 - a)), h = lambda(a_prev) - lambda(a_t), h_before = lambda(a_t) -
+        lambda(a_before) and v = (1 - a_prev) (1 - e^{-2h}) in `ddpm_coeffs`' form,
+            c2 = 1/2 sqrt(a_prev) (v / (1 - a_prev)) (h / h_before)
+        in fp64, rounded to fp32 once (a python float that holds an fp32 value)."""
+        if not 0.0 < a_before < a_t < a_prev < 1.0:
+            raise ValueError(f"dpmpp_c2: an order-2 step needs 0 < a_before < a_t < a_prev < 1, got {a_before}, {a_t}, {a_prev}")
+        lam = lambda a: 0.5 * np.log(a / (1.0 - a))
+        v = max(0.0, (1.0 - a_prev) / (1.0 - a_t) * (1.0 - a_t / a_prev))
+        h, h_before = lam(a_prev) - lam(a_t), lam(a_t) - lam(a_before)
+        return float(np.float32(0.5 * np.sqrt(a_prev) * (v / (1.0 - a_prev)) * (h / h_before)))
+
+    def dpmpp_coeffs(self, t: int, order2: bool):
+        """(a_t, a_prev, sigma, dir, c2) of the SDE-DPM-Solver++ step at timestep t.  The first four ARE `ddpm_coeffs(t)`: with
+        lambda(a) = 1/2 log(a / (1 - a)) and h = lambda(a_prev) - lambda(a_t), sigma_prev^2 (1 - e^{-2h}) is its v and
+        sigma_prev e^{-h} its dir, so the first-order solver is the eta = 1 update.  c2 (`dpmpp_c2`) weighs the correction
+        x0 - x0_before of an order-2 step, 0.0 for an order-1 step; the step before this one ran t + T // S.  `dpmpp_orders` says
+        which steps of a schedule are order 2 (never the first one run, never the last)."""
+        coef = self.ddpm_coeffs(t)
+        if not order2:
+            return (*coef, 0.0)
+        before = int(t) + self.config.num_train_timesteps // self.num_inference_steps
+        if before >= self.config.num_train_timesteps:
+            raise ValueError(f"dpmpp_coeffs: no step runs before timestep {int(t)} of this schedule; its step is order 1")
+        return (*coef, self.dpmpp_c2(float(self.alphas_cumprod[before]), coef[0], coef[1]))
+
+    @staticmethod
+    def dpmpp_orders(num_steps: int, skip: int, solver_order: int):
+        """the order of step i = 0 .. num_steps - 1 of a schedule whose run starts at step `skip` (steps before it are not run and
+        count as order 1): order 1 on the first step run, on the last step (the published multistep solver's final step, where h
+        jumps to the end of the schedule) and everywhere for solver_order 1; order 2 otherwise"""
+        if solver_order not in (1, 2):
+            raise ValueError(f"solver_order must be 1 or 2, got {solver_order!r}")
+        if not isinstance(skip, int) or isinstance(skip, bool) or not 0 <= skip < num_steps:
+            raise ValueError(f"skip must be an integer in [0, {num_steps}), got {skip!r}")
+        return [2 if (solver_order == 2 and skip < i < num_steps - 1) else 1 for i in range(num_steps)]
+
+    def dpmpp_table(self, skip: int, solver_order: int):
+        """[dpmpp_coeffs(t_i, order of step i)] for the steps i = skip .. S - 1 of the current schedule"""
+        ts = self.timesteps.tolist()
+        orders = self.dpmpp_orders(len(ts), skip, solver_order)
+        return [self.dpmpp_coeffs(t, o == 2) for t, o in zip(ts[skip:], orders[skip:])]
+
+    @staticmethod
     def linear_form(a_from: float, a_to: float):
         """x' = cx * x + ce * eps  for  x0=(x-sqrt(1-a_from)eps)/sqrt(a_from); x'=sqrt(a_to)x0+sqrt(1-a_to)eps.
 

@@ -228,6 +228,28 @@ int ief_cfg_ddpm_step_f32(const float* eps_u, const float* eps_c, const float* x
  * IEF_EINVAL: a null eps_c / x_t / x_prev / z_out / coef_rows; IEF_ESHAPE: R <= 0, row_elems <= 0. */
 int ief_ddpm_noise_maps_f32(const float* eps_u, const float* eps_c, const float* x_t, const float* x_prev, float* z_out,
                             const float* coef_rows, int R, long long row_elems, void* stream);
+/* The same step at solver order 2 (second-order multistep SDE-DPM-Solver++, the solver LEDITS++ is published with).  sigma and dir of
+ * the eta = 1 update ARE the solver's first-order coefficients, so the step is that update plus one correction on the x0 predictions
+ * of two consecutive steps:   mu = mu1 + c2 (x0 - x0_prev),   every operation rounded in fp32 in this order;  c2 == 0 (an order-1
+ * step) does not read x0_prev into the result and gives ief_cfg_ddpm_step_f32's x_out and x0_out bit for bit.
+ * coef: DEVICE fp32 [5] = {a_from, a_to, sigma, dir, c2}; x0_prev: DEVICE fp32 [n], the x0 prediction the previous step of the same
+ * batch row wrote -- read and overwritten with this step's x0 by the lane that owns the element (nothing to zero before a first
+ * step, whose c2 is 0).  Everything else as ief_cfg_ddpm_step_f32.
+ * IEF_EINVAL: a null eps_c / x / x_out / x0_prev / coef / noise / step, or eps_u without g_rows; IEF_ESHAPE: n <= 0, row_elems <= 0,
+ * n % row_elems != 0, noise_rows <= 0; IEF_EALIGN: a pointer off the 4-byte grid. */
+int ief_cfg_dpmpp_step_f32(const float* eps_u, const float* eps_c, const float* x, float* x_out, float* x0_out, float* x0_prev,
+                           const float* coef, const float* g_rows, long long n, long long row_elems,
+                           const float* noise, int noise_rows, const int* step, void* stream);
+/* the extraction under that mean, R rows at R consecutive timesteps in one launch: z_out[r] = (x_prev[r] - mu_r) / sigma_r with
+ * mu_r = mu1_r + c2_r (x0_r - x0_(r-1)), x0_r the x0 prediction of row r's own eps (no chain over stepped latents).  One lane owns
+ * element j of every row and walks the rows in order; row 0 takes x0_(-1) from x0_carry (not read into the result where c2_0 == 0)
+ * and the last row's x0 is written back to it, so consecutive launches over the rows of one image give the bits of one launch.
+ * coef_rows: DEVICE fp32 [R][6] = {a_from, a_to, sigma, dir, g, c2}; x0_carry: DEVICE fp32 [row_elems].  sigma_r == 0 gives a zero
+ * row; with c2 == 0 in every row z_out is ief_ddpm_noise_maps_f32's bit for bit.
+ * IEF_EINVAL: a null eps_c / x_t / x_prev / z_out / coef_rows / x0_carry; IEF_ESHAPE: R <= 0, row_elems <= 0; IEF_EALIGN: a pointer
+ * off the 4-byte grid. */
+int ief_dpmpp_noise_maps_f32(const float* eps_u, const float* eps_c, const float* x_t, const float* x_prev, float* z_out,
+                             const float* coef_rows, float* x0_carry, int R, long long row_elems, void* stream);
 /* DiffEdit (Couairon, Verbeek, Schwenk, Cord, "DiffEdit: Diffusion-based semantic image editing with mask guidance"): the CFG + DDIM
  * step of ief_cfg_ddim_step_f32 in the same launch, and every batch row keeps x' only where ITS binary mask is set; elsewhere the
  * element is put back onto the stored inversion trajectory.  For element i = b row_elems + c hw + p:
@@ -289,6 +311,13 @@ int ief_ledits_guidance_mask_f32(const float* eps, const float* m1, const float*
 int ief_ledits_ddpm_step_f32(const float* eps, const float* mask, const float* scale, const float* x, float* x_out, float* x0_out,
                              const float* coef, long long row_elems, long long hw, const float* noise, int noise_rows,
                              const int* step, int E, void* stream);
+/* The same step at solver order 2: the guidance formed exactly as above, then the mean of ief_cfg_dpmpp_step_f32 (the same device
+ * function).  coef: DEVICE fp32 [5] = {a_from, a_to, sigma, dir, c2}; x0_prev: DEVICE fp32 [row_elems], read and overwritten with this
+ * step's x0 prediction by the lane that owns the element.  c2 == 0 gives ief_ledits_ddpm_step_f32's outputs bit for bit.
+ * IEF_EINVAL: a null eps / scale / x / x_out / x0_prev / coef / noise / step; IEF_ESHAPE and IEF_EALIGN as there. */
+int ief_ledits_dpmpp_step_f32(const float* eps, const float* mask, const float* scale, const float* x, float* x_out, float* x0_out,
+                              float* x0_prev, const float* coef, long long row_elems, long long hw, const float* noise,
+                              int noise_rows, const int* step, int E, void* stream);
 /* sinusoidal timestep embedding, flip_sin_to_cos, shift 0: out fp16 [B][dim] = [cos | sin] */
 int ief_timestep_embedding_f16(const float* t, ief_half* out, int B, int dim, void* stream);
 /* out = a + b elementwise on fp16 (residual add when a hook owns Attention.forward) */
