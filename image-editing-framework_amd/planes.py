@@ -145,6 +145,15 @@ def heuristic_plan(M, N, K, conv=False):
     return tile, splits
 
 
+def halo_fallback_plan(M, N, ncb):
+    """the halo form's plan for a shape the table does not hold: cut K (whole channel blocks) until ~256 workgroups exist"""
+    tiles = -(-M // 256) * (N // 80)
+    sp = 1
+    while tiles * sp < 192 and sp * 2 <= ncb // 2 and sp < 16:
+        sp *= 2
+    return 11, sp
+
+
 def pick_plan(M, N, K, conv=False, variant=""):
     hit = _plan_table().get(f"{'conv' if conv else 'gemm'}|{M}|{N}|{K}{variant}")
     if hit is None:
@@ -383,11 +392,7 @@ def conv3x3(x, w, bias=None, x2=None, stride=1, upsample=False, rowvec=None, res
         if hit is not None and (hit[0] not in _HALO or (phase_ok if hit[0] == 13 else halo_ok)):
             p.tile, p.splits = hit[0], hit[1]
         elif halo_ok:
-            tiles, ncb = -(-M // 256) * (Cout // 80), (C1 + C2) // 32
-            sp = 1
-            while tiles * sp < 192 and sp * 2 <= ncb // 2 and sp < 16:       # cut K (whole channel blocks) until ~256 workgroups exist
-                sp *= 2
-            p.tile, p.splits = 11, sp
+            p.tile, p.splits = halo_fallback_plan(M, Cout, (C1 + C2) // 32)
         else:
             p.tile, p.splits = heuristic_plan(M, Cout, K, conv=True)        # (the table is keyed WITH the variant: no plain-key fallback)
             if TILE_FORCE and TILE_FORCE < 10:

@@ -3,6 +3,9 @@ UNet launches, per layer shape, cache-cold, on the current GPU; writes the table
 
     python tests/tune_plans_x3.py out.json [config=sd15] [latent]      batches 4 / 2 / 1 (edit, synthesis / CFG split, inversion)
     IEF_TUNE_KEEP=1: keep the committed table and tune only the shapes it lacks
+
+After a retune run `pytest tests/test_x3p_plan_classes.py`: a plan whose split-K slab picture (tile x variant, mid-tap starts, short
+or empty slabs, ragged channel blocks) no case of `tests/test_gpu_x3p_splitk.py` runs fails there until such a case is added.
 """
 import os
 import sys
