@@ -76,12 +76,20 @@ extern "C" int ief_conv_in_f32(const float* x, const ief_half* w, const float* b
                                int B, int Cin, int H, int Wd, int Cout, void* stream) {
     if (!x || !w || !out) return IEF_EINVAL;
     if (B <= 0 || H <= 0 || Wd <= 0 || Cin <= 0 || Cin > CIN_MAX || Cout <= 0 || (Cout & 7) || Cout > 2048) return IEF_ESHAPE;
-    int nsl = (Cout + CI_CMAX - 1) / CI_CMAX;   // fewest equal slices of <= CI_CMAX channels, each a multiple of 8
-    while (nsl <= Cout / 8 && (Cout % nsl || ((Cout / nsl) & 7))) ++nsl;
-    if (nsl > Cout / 8) return IEF_ESHAPE;
+    // w is read and out is written in 16-byte pieces (8 halves); x and bias one float at a time
+    if (((uintptr_t)w | (uintptr_t)out) & 15) return IEF_EALIGN;
+    if (((uintptr_t)x | (uintptr_t)bias) & 3) return IEF_EALIGN;
+    // fewest equal slices of <= CI_CMAX channels, each a multiple of 8, whose fp32 weights fit the 64 KiB of LDS beside the
+    // input rows (Cin = 8: 256 channels would need 81 KiB, 128 do with 45 KiB)
+    int nsl = (Cout + CI_CMAX - 1) / CI_CMAX;
+    size_t lds = 0;
+    for (;; ++nsl) {
+        if (nsl > Cout / 8) return IEF_ESHAPE;
+        if (Cout % nsl || ((Cout / nsl) & 7)) continue;
+        lds = ((size_t)9 * Cin * (Cout / nsl) + (size_t)CI_PIX * 9 * Cin) * sizeof(float);
+        if (lds <= 64 * 1024) break;
+    }
     const int Cc = Cout / nsl;
-    const size_t lds = ((size_t)9 * Cin * Cc + (size_t)CI_PIX * 9 * Cin) * sizeof(float);
-    if (lds > 64 * 1024) return IEF_ESHAPE;
     const long long total = (long long)B * H * Wd;
     hipLaunchKernelGGL(conv_in_kernel, dim3((unsigned)((total + CI_PIX - 1) / CI_PIX), Cout / Cc), dim3(256), lds,
                        (hipStream_t)stream, x, w, bias, out, B, Cin, H, Wd, Cout);
@@ -158,7 +166,8 @@ __global__ __launch_bounds__(256) void conv_out_kernel(const half_t* __restrict_
     }
 }
 
-// fallback for wide inputs (C > 512) or weight sets past the LDS budget: the plain loop, one chunk at a time
+// fallback for wide inputs (C > 384: more than 3 chunks per lane and tap) or weight sets past the 48 KiB LDS budget: the plain
+// loop, one chunk at a time
 __global__ __launch_bounds__(256) void conv_out_wide_kernel(const half_t* __restrict__ x, const half_t* __restrict__ w,
                                                             const float* __restrict__ bias, float* __restrict__ out,
                                                             int B, int C, int H, int Wd, int Cout) {
@@ -208,6 +217,9 @@ extern "C" int ief_conv_out_f32(const ief_half* x, const ief_half* w, const floa
                                 int B, int C, int H, int Wd, int Cout, void* stream) {
     if (!x || !w || !out) return IEF_EINVAL;
     if (B <= 0 || H <= 0 || Wd <= 0 || C <= 0 || (C & 7) || Cout <= 0 || Cout > COUT_MAX) return IEF_ESHAPE;
+    // x and w are read in 16-byte pieces (8 halves) by every kernel below; bias and out one float at a time
+    if (((uintptr_t)x | (uintptr_t)w) & 15) return IEF_EALIGN;
+    if (((uintptr_t)bias | (uintptr_t)out) & 3) return IEF_EALIGN;
     const long long total = (long long)B * H * Wd;
     const size_t lds = (size_t)Cout * 9 * C * sizeof(half_t);
     const dim3 grid((unsigned)((total + 15) / 16));

@@ -360,6 +360,7 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(half_t* __restrict__ 
 extern "C" int ief_softmax_rows_f16(ief_half* x, int rows, int L, void* stream) {
     if (!x) return IEF_EINVAL;
     if (rows <= 0 || L <= 0 || (L & 7) || L > 256 * 8 * SM_MAXCH) return IEF_ESHAPE;
+    if ((uintptr_t)x & 15) return IEF_EALIGN;    // 8 halves at a time
     hipLaunchKernelGGL(softmax_rows_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, x, L);
     IEF_LAUNCH_CHECK();
     return IEF_OK;

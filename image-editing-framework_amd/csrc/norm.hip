@@ -228,6 +228,8 @@ extern "C" int ief_groupnorm_silu_f16(const ief_half* x, const ief_half* x2, int
     if ((C1 & 7) || (C2 & 7) || (C % groups) || C > 8 * 1024) return IEF_ESHAPE;
     hipStream_t st = (hipStream_t)stream;
     const int cpg_ = C / groups;
+    // every form reads and writes channel PAIRS at least (4 bytes), gamma / beta / the statistics one float at a time
+    if (((uintptr_t)x | (C2 > 0 ? (uintptr_t)x2 : 0) | (uintptr_t)out | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)partial) & 3) return IEF_EALIGN;
     // single launch when one (batch, group) slab is small enough for one workgroup to stream twice quickly
     if (!(cpg_ & 1) && !(C1 & 1) && (cpg_ >> 1) <= 256 && (long long)HW * cpg_ * 2 <= 48 * 1024) {
         const int cp2 = cpg_ >> 1;
@@ -251,6 +253,8 @@ extern "C" int ief_groupnorm_silu_f16(const ief_half* x, const ief_half* x2, int
     // statistics: up to 1024 threads (C8 * PY), PY bounded by the pixels a block owns
     int per = (HW + splits - 1) / splits;
     if (C > GN_PART_FLOATS) return IEF_ESHAPE;
+    // the three launches move 8 halves / 4 floats at a time
+    if (((uintptr_t)x | (C2 > 0 ? (uintptr_t)x2 : 0) | (uintptr_t)out | (uintptr_t)gamma | (uintptr_t)beta) & 15) return IEF_EALIGN;
     int PYs = 256 / C8;                    // ~256-thread blocks, several pixels per thread
     if (PYs > per) PYs = per;
     if (PYs > GN_PART_FLOATS / C) PYs = GN_PART_FLOATS / C;
@@ -393,6 +397,9 @@ extern "C" int ief_groupnorm_cstat_f16(const ief_half* x, const ief_half* x2, in
     if (B <= 0 || HW <= 0 || groups <= 0 || groups > GN_MAX_GROUPS) return IEF_ESHAPE;
     if ((C1 & 7) || (C2 & 7) || (C % groups) || C > 8 * 1024) return IEF_ESHAPE;
     if (bm1 <= 0 || (HW % bm1) || (C2 > 0 && (bm2 <= 0 || (HW % bm2)))) return IEF_ESHAPE;
+    // both forms move 8 halves / 4 floats at a time; the producers' pairs and the folded statistics one float at a time
+    if (((uintptr_t)x | (C2 > 0 ? (uintptr_t)x2 : 0) | (uintptr_t)out | (uintptr_t)gamma | (uintptr_t)beta) & 15) return IEF_EALIGN;
+    if (((uintptr_t)cstat1 | (C2 > 0 ? (uintptr_t)cstat2 : 0) | (uintptr_t)stats) & 3) return IEF_EALIGN;
     hipStream_t st = (hipStream_t)stream;
     // one launch when a workgroup's share of the fold is small: slices of whole groups and whole 8-channel chunks
     {
@@ -485,6 +492,7 @@ extern "C" int ief_layernorm_f16(const ief_half* x, ief_half* out, const float* 
                                  int rows, int C, float eps, void* stream) {
     if (!x || !out || !gamma || !beta) return IEF_EINVAL;
     if (rows <= 0 || C <= 0 || (C & 7) || C > 8 * 64 * LN_MAXCH) return IEF_ESHAPE;
+    if (((uintptr_t)x | (uintptr_t)out | (uintptr_t)gamma | (uintptr_t)beta) & 15) return IEF_EALIGN;    // 8 halves / 4 floats at a time
     hipLaunchKernelGGL(layernorm_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, x, out, gamma, beta,
                        rows, C, eps);
     IEF_LAUNCH_CHECK();
@@ -510,6 +518,7 @@ __global__ __launch_bounds__(256) void geglu_kernel(const half_t* __restrict__ i
 extern "C" int ief_geglu_f16(const ief_half* in, ief_half* out, int rows, int Ch, void* stream) {
     if (!in || !out) return IEF_EINVAL;
     if (rows <= 0 || Ch <= 0 || (Ch & 7)) return IEF_ESHAPE;
+    if (((uintptr_t)in | (uintptr_t)out) & 15) return IEF_EALIGN;    // 8 halves at a time
     const long long total = (long long)rows * (Ch / 8);
     int grid = (int)((total + 255) / 256);
     if (grid > 4096) grid = 4096;

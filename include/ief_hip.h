@@ -117,7 +117,10 @@ int ief_conv3x3_f16(const IefGemmParams* p, void* stream);
 
 /* conv_in: latent NCHW fp32 [B,Cin,H,W] (Cin<=8) -> NHWC fp16 [B,H,W,Cout]; W [3][3][Cin][Cout] fp16 (k-major).
  * conv_out: NHWC fp16 [B,H,W,C] -> NCHW fp32 [B,Cout,H,W] (Cout<=8); W [Cout][3][3][C] fp16.
- * (UNet2DConditionModel.conv_in / conv_out, called at /root/reference/p2p/model/sd_utils.py:73) */
+ * (UNet2DConditionModel.conv_in / conv_out, called at /root/reference/p2p/model/sd_utils.py:73)
+ * conv_in splits Cout into the fewest equal slices (multiples of 8, <= 256 channels) whose fp32 weights fit 64 KiB of LDS.
+ * Operands moved 8 halves at a time (w and out of conv_in, x and w of conv_out) must be 16-byte aligned, the fp32 ones 4-byte
+ * aligned: IEF_EALIGN otherwise, nothing launched. */
 int ief_conv_in_f32(const float* x, const ief_half* w, const float* bias, ief_half* out,
                     int B, int Cin, int H, int Wd, int Cout, void* stream);
 int ief_conv_out_f32(const ief_half* x, const ief_half* w, const float* bias, float* out,
@@ -129,6 +132,9 @@ int ief_conv_out_f32(const ief_half* x, const ief_half* w, const float* bias, fl
  * `partial` is scratch of >= B * (splits + 1) * groups * 2 floats (splits = ief_gn_splits(HW)); on completion its
  * LAST B * groups * 2 floats hold (mean, rstd) per (batch, group) — what ief_groupnorm_bwd_f16 takes as `stats`.
  * Two sources (x, x2) = channel concat [C1 | C2] normalised as one tensor, written to out [.., C1+C2].
+ * Alignment (IEF_EALIGN otherwise, nothing launched): the one-workgroup form of GroupNorm moves channel pairs, so x, x2, out,
+ * gamma, beta and partial must be 4-byte aligned; its three-launch form, ief_groupnorm_cstat_f16, LayerNorm and GEGLU move 8 halves
+ * / 4 floats at a time, so their x, x2, in, out, gamma and beta must be 16-byte aligned.
  */
 int ief_gn_splits(int HW);
 int ief_groupnorm_silu_f16(const ief_half* x, const ief_half* x2, int C1, int C2, ief_half* out,
@@ -325,7 +331,8 @@ int ief_add_f16(const ief_half* a, const ief_half* b, ief_half* out, long long n
 /* out[b][:] = in[src[b]][:] for fp16 [B][row_elems], src a DEVICE int32 [B] with values in [0, B): Plug-and-Play's
  * feature injection (/root/reference/pnp/model/register.py:161-166) as a gather in front of conv2 */
 int ief_gather_rows_f16(const ief_half* in, ief_half* out, const int* src, int B, long long row_elems, void* stream);
-/* in-place row softmax over the last dim of fp16 [rows][L] (materialised attention of the VAE mid block, d = 512) */
+/* in-place row softmax over the last dim of fp16 [rows][L] (materialised attention of the VAE mid block, d = 512); L a multiple of 8
+ * up to 16384 (IEF_ESHAPE), x 16-byte aligned (IEF_EALIGN) */
 int ief_softmax_rows_f16(ief_half* x, int rows, int L, void* stream);
 /* out[c][r] = in[r][c] for fp16 [R][C] (V^T for the P.V GEMM of the VAE attention) */
 int ief_transpose_f16(const ief_half* in, ief_half* out, int R, int C, void* stream);
