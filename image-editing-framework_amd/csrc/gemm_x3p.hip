@@ -33,7 +33,9 @@
 
 #include "x3p_common.h"
 
-template <int BM, int BN, int WAVES_M, int WAVES_N, int NS, int NL, bool CONV>
+// KCAT (linear only): the A operand is K-CONCATENATED -- K tiles below p.K1 / 32 come from A / planeA / lda, the rest from
+// A2 / planeA2 / lda2 (the weight is one [N][K1 + K2] tensor); the per-piece source pointers switch once, at that tile index.
+template <int BM, int BN, int WAVES_M, int WAVES_N, int NS, int NL, bool CONV, bool KCAT = false>
 __global__ __launch_bounds__(64 * (WAVES_M * WAVES_N + NL)) void igemm_x3p_kernel(const IefGemmX3pParams p) {
     constexpr int BK = XP_BK;
     constexpr int NWC = WAVES_M * WAVES_N;          // compute waves
@@ -109,7 +111,14 @@ __global__ __launch_bounds__(64 * (WAVES_M * WAVES_N + NL)) void igemm_x3p_kerne
                 a_y[j] = oy * p.stride - (p.pad_hi_only ? 0 : 1);
                 a_x[j] = ox * p.stride - (p.pad_hi_only ? 0 : 1);
             } else if (a_ok[j]) {
-                ptr[j] = (const char*)p.A + ((long long)plane[j] * p.planeA + (long long)m * p.lda) * 2 + kcb + (long long)kt_lo * (BK * 2);
+                if constexpr (KCAT) {
+                    const int k1t = p.K1 / BK;
+                    ptr[j] = kt_lo < k1t
+                        ? (const char*)p.A + ((long long)plane[j] * p.planeA + (long long)m * p.lda) * 2 + kcb + (long long)kt_lo * (BK * 2)
+                        : (const char*)p.A2 + ((long long)plane[j] * p.planeA2 + (long long)m * p.lda2) * 2 + kcb + (long long)(kt_lo - k1t) * (BK * 2);
+                } else {
+                    ptr[j] = (const char*)p.A + ((long long)plane[j] * p.planeA + (long long)m * p.lda) * 2 + kcb + (long long)kt_lo * (BK * 2);
+                }
                 step[j] = BK * 2;
             }
         } else {
@@ -165,6 +174,7 @@ __global__ __launch_bounds__(64 * (WAVES_M * WAVES_N + NL)) void igemm_x3p_kerne
         }
     };
 
+    int st_k = kt_lo;                 // KCAT: the K tile the next stage_tile fetches
     auto stage_tile = [&](int buf) {
         if (!stages_) return;
         half_t* base = smem + buf * SLOT + swave * (16 * BK);
@@ -174,6 +184,14 @@ __global__ __launch_bounds__(64 * (WAVES_M * WAVES_N + NL)) void igemm_x3p_kerne
             glds16(ptr[j], dst);
             if constexpr (TN > 5 && !CONV) ptr[j] += ((stepmask >> j) & 1u) ? BK * 2 : 0;      // the wide tile has no register for step[]
             else ptr[j] += step[j];
+        }
+        if constexpr (KCAT) {
+            if (++st_k == p.K1 / BK) {          // the next tile is the first of the second operand
+#pragma unroll
+                for (int j = 0; j < G; ++j)
+                    if (exists[j] && isA[j] && a_ok[j])
+                        ptr[j] = (const char*)p.A2 + ((long long)plane[j] * p.planeA2 + (long long)a_m[j] * p.lda2) * 2 + kcb;
+            }
         }
         if constexpr (CONV) {
             it_c += BK;
@@ -507,13 +525,18 @@ extern "C" int ief_gemm_x3p_tile_bn(int tile) {
     }
 }
 
-template <int BM, int BN, int WAVES_M, int WAVES_N, int NS, int NL>
+// HAS_KCAT: the tile also has the K-concatenated linear instantiation (the tiles the transformer-tail plans run)
+template <int BM, int BN, int WAVES_M, int WAVES_N, int NS, int NL, bool HAS_KCAT = false>
 static int launch_x3p(const IefGemmX3pParams& p, hipStream_t st) {
     const int tiles = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
     const int splits = p.splits > 1 ? p.splits : 1;
     constexpr int NT = 64 * (WAVES_M * WAVES_N + NL);
     if (p.conv) hipLaunchKernelGGL((igemm_x3p_kernel<BM, BN, WAVES_M, WAVES_N, NS, NL, true>), dim3(tiles, splits), dim3(NT), 0, st, p);
-    else hipLaunchKernelGGL((igemm_x3p_kernel<BM, BN, WAVES_M, WAVES_N, NS, NL, false>), dim3(tiles, splits), dim3(NT), 0, st, p);
+    else if (p.K1 > 0) {
+        if constexpr (HAS_KCAT)
+            hipLaunchKernelGGL((igemm_x3p_kernel<BM, BN, WAVES_M, WAVES_N, NS, NL, false, true>), dim3(tiles, splits), dim3(NT), 0, st, p);
+        else return IEF_EINVAL;
+    } else hipLaunchKernelGGL((igemm_x3p_kernel<BM, BN, WAVES_M, WAVES_N, NS, NL, false>), dim3(tiles, splits), dim3(NT), 0, st, p);
     IEF_LAUNCH_CHECK();
     return IEF_OK;
 }
@@ -536,6 +559,12 @@ extern "C" int ief_gemm_x3p(const IefGemmX3pParams* pp, void* stream) {
     if (p.rstat_out && (p.splits > 1 || p.geglu || p.tile == 11 || p.tile == 12 || p.tile == 13 || (p.N % ief_gemm_x3p_tile_wn(p.tile)))) return IEF_EINVAL;
     if (p.rstat_in && (!p.colsum || p.rstat_slots <= 0 || p.rstat_cnt <= 0 || p.rstat_slots * p.rstat_cnt != p.K || p.splits > 1 ||
                        p.conv || !(p.ln_eps > 0.f) || ((uintptr_t)p.colsum & 15))) return IEF_EINVAL;
+    if (p.K1 != 0) {        // K-concatenated A operand: [A | A2] . W^T, linear launches on tiles 1, 3, 4 and 6 only
+        if (p.conv || p.geglu || p.rstat_in || !p.A2) return IEF_EINVAL;
+        if (p.tile != 1 && p.tile != 3 && p.tile != 4 && p.tile != 6) return IEF_EINVAL;
+        if (p.K1 < 0 || p.K1 >= p.K || (p.K1 % XP_BK) || ((p.K - p.K1) % XP_BK)) return IEF_ESHAPE;
+        if ((p.lda2 & 7) || (p.planeA2 & 7) || ((uintptr_t)p.A2 & 15)) return IEF_EALIGN;
+    }
     if (p.conv) {
         if (p.C1 <= 0 || p.C2 < 0 || (p.C1 % XP_BK) || (p.C2 % XP_BK) || (p.CE1 % XP_BK) || (p.CE2 % XP_BK)) return IEF_ESHAPE;
         if ((p.C2 > 0 && !p.A2) || (p.CE1 > 0 && !p.E1) || (p.CE2 > 0 && !p.E2) || (p.CE2 > 0 && p.CE1 == 0)) return IEF_EINVAL;
@@ -558,14 +587,14 @@ extern "C" int ief_gemm_x3p(const IefGemmX3pParams* pp, void* stream) {
     int rc;
     switch (p.tile) {
         case 2: rc = launch_x3p<128, 160, 4, 2, 4, 4>(p, st); break;
-        case 3: rc = launch_x3p<128, 80, 4, 1, 3, 0>(p, st); break;
-        case 4: rc = launch_x3p<256, 160, 4, 2, 3, 0>(p, st); break;
+        case 3: rc = launch_x3p<128, 80, 4, 1, 3, 0, true>(p, st); break;
+        case 4: rc = launch_x3p<256, 160, 4, 2, 3, 0, true>(p, st); break;
         case 5: rc = launch_x3p<64, 160, 2, 2, 4, 0>(p, st); break;
-        case 6: rc = launch_x3p<128, 64, 4, 1, 3, 0>(p, st); break;
+        case 6: rc = launch_x3p<128, 64, 4, 1, 3, 0, true>(p, st); break;
         case 7: rc = launch_x3p<128, 160, 2, 2, 2, 0>(p, st); break;       // 4 waves (64 x 80 each), 72 KiB of LDS: two workgroups per CU
         case 8: rc = launch_x3p<256, 320, 4, 2, 2, 0>(p, st); break;       // 8 waves of 64 x 160: the fewest staged bytes per FLOP (wide N only)
         case 11: case 12: case 13: rc = ief_conv_halo_x3p_dispatch(p, st); break;
-        case 1: default: rc = launch_x3p<128, 160, 4, 2, 4, 0>(p, st); break;
+        case 1: default: rc = launch_x3p<128, 160, 4, 2, 4, 0, true>(p, st); break;
     }
     if (rc) return rc;
     if (p.splits > 1) {

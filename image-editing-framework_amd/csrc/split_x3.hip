@@ -99,6 +99,46 @@ extern "C" int ief_x3_upsample_phase_weights(const float* w, void* planes, int C
     return IEF_OK;
 }
 
+// Two linears with nothing non-linear between them as ONE (the tail of a Transformer2DModel, FeedForward.net[2] then proj_out):
+//     (g W2^T + b2 + h) Wp^T + bp = [g | h] [Wp W2 | Wp]^T + (Wp b2 + bp)
+// One thread per element of wcat [C][K + C] and of bcat [C] (column K + C of the index space): fp64 sums over j in increasing
+// order, rounded once to fp32.  Consecutive threads read consecutive columns of W2 and the same element of Wp.  Runs once per
+// weight set.
+__global__ __launch_bounds__(256) void x3_fold_linear_pair_kernel(const float* __restrict__ wp, const float* __restrict__ w2,
+                                                                  const float* __restrict__ b2, const float* __restrict__ bp,
+                                                                  float* __restrict__ wcat, float* __restrict__ bcat, int C, int K) {
+    const int cols = K + C + 1;
+    const long long total = (long long)C * cols;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        const int r = (int)(i / cols), c = (int)(i - (long long)r * cols);
+        const float* wr = wp + (long long)r * C;
+        if (c < K) {
+            double a = 0.0;
+            for (int j = 0; j < C; ++j) a += (double)wr[j] * (double)w2[(long long)j * K + c];
+            wcat[(long long)r * (K + C) + c] = (float)a;
+        } else if (c < K + C) {
+            wcat[(long long)r * (K + C) + c] = wr[c - K];
+        } else {
+            double a = 0.0;
+            if (b2)
+                for (int j = 0; j < C; ++j) a += (double)wr[j] * (double)b2[j];
+            if (bp) a += (double)bp[r];
+            bcat[r] = (float)a;
+        }
+    }
+}
+extern "C" int ief_x3_fold_linear_pair(const float* wp, const float* w2, const float* b2, const float* bp, float* wcat, float* bcat,
+                                       int C, int K, void* stream) {
+    if (!wp || !w2 || !wcat || !bcat) return IEF_EINVAL;
+    if (C <= 0 || K <= 0) return IEF_ESHAPE;
+    long long grid = ((long long)C * (K + C + 1) + 255) / 256;
+    if (grid > 16384) grid = 16384;
+    hipLaunchKernelGGL(x3_fold_linear_pair_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, wp, w2, b2, bp, wcat, bcat, C,
+                       K);
+    IEF_LAUNCH_CHECK();
+    return IEF_OK;
+}
+
 // BPRE: the B operand comes as pre-split fp16 planes (p.Wp: [2][N][K] contiguous, ief_x3_split_weights); otherwise it is
 // fp32 and split while staged, like A (the batched attention products: both operands are activations).
 template <int WM, int WN, int TM, int TN, int KIND, bool TRANSB, bool BPRE>

@@ -580,6 +580,50 @@ def x3_upsample_phase_planes(w, scale=None):
     return planes
 
 
+def fold_linear_pair_ref(wp, w2, b2=None, bp=None):
+    """host reference of `ief_x3_fold_linear_pair` (any device, fp64 throughout): ([Wp W2 | Wp] fp64 [C, K + C], Wp b2 + bp fp64 [C])
+    with (g W2^T + b2 + h) Wp^T + bp = [g | h] wcat^T + bcat"""
+    wp64, w264 = wp.double(), w2.double()
+    if wp64.dim() != 2 or wp64.shape[0] != wp64.shape[1] or w264.dim() != 2 or w264.shape[0] != wp64.shape[0]:
+        raise ValueError("fold_linear_pair: wp must be [C, C] and w2 [C, K]")
+    b = torch.zeros(wp64.shape[0], dtype=torch.float64, device=wp.device)
+    if b2 is not None:
+        b = wp64 @ b2.double()
+    if bp is not None:
+        b = b + bp.double()
+    return torch.cat([wp64 @ w264, wp64], 1), b
+
+
+def x3_fold_linear_pair(wp, w2, b2=None, bp=None):
+    """(wcat fp32 [C, K + C], bcat fp32 [C]) of two linears folded into one (`ief_x3_fold_linear_pair`: w2 [C, K] then wp [C, C]).
+    A DERIVED weight, cached per (wp, w2) pair like the phase planes: made at the first eager use (after a multi-GPU weight
+    broadcast, which runs before any forward), None while a graph is being captured and it does not exist yet, re-made when either
+    weight or bias was updated in place, freed with wp.  Its operand planes come from `x3_weight_planes(wcat)`."""
+    key = (wp.data_ptr(), tuple(wp.shape), w2.data_ptr(), tuple(w2.shape), "fold")
+    srcs = (wp, w2, b2, bp)
+    hit = _x3_planes.get(key)
+    if hit is not None and all((r is None and t is None) or (r is not None and r() is t and v == t._version)
+                               for t, (r, v) in zip(srcs, hit[0])):
+        return hit[2]
+    if _capturing():
+        return None
+    if wp.dim() != 2 or wp.shape[0] != wp.shape[1] or w2.dim() != 2 or w2.shape[0] != wp.shape[0]:
+        raise ValueError("x3_fold_linear_pair: wp must be [C, C] and w2 [C, K]")
+    C, K = w2.shape
+    for t, nm in ((wp, "wp"), (w2, "w2"), (b2, "b2"), (bp, "bp")):
+        if t is not None and (not _dev32(t, nm).is_contiguous() or (t.dim() == 1 and t.numel() != C)):
+            raise ValueError(f"x3_fold_linear_pair: {nm} must be contiguous fp32 ([C] for a bias)")
+    lib = load()
+    wcat = torch.empty(C, K + C, dtype=torch.float32, device=wp.device)
+    bcat = torch.empty(C, dtype=torch.float32, device=wp.device)
+    _check(lib.ief_x3_fold_linear_pair(wp.data_ptr(), w2.data_ptr(), _ptr(b2), _ptr(bp), wcat.data_ptr(), bcat.data_ptr(), C, K,
+                                       _stream()), "ief_x3_fold_linear_pair")
+    import weakref
+    _x3_planes[key] = (tuple((None, 0) if t is None else (weakref.ref(t), t._version) for t in srcs), 0, (wcat, bcat))
+    weakref.finalize(wp, _x3_planes.pop, key, None)
+    return wcat, bcat
+
+
 def _set_x3(p, sa, sb, w=None) -> str:
     """fill the split-operand fields of an IefGemmF32Params from the current mode; returns the kernel family's name.
     w: the launch's B operand when it is a weight ([N, K...] contiguous fp32): its cached pre-split planes ride along"""

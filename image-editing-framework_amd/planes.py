@@ -283,23 +283,44 @@ LN_FOLD = os.environ.get("IEF_X3P_FOLD_LN", "0") == "1"      # 1: fold the trans
 # stream then writes fp32 AND planes AND row statistics, its consumers lose their split-K plans: the launches saved cost less
 
 
+KCAT_TILES = (1, 3, 4, 6)      # tiles with a K-concatenated instantiation (csrc/gemm_x3p.hip)
+_KCAT_NEAREST = {2: 1, 5: 1, 7: 1, 8: 4}      # what a plan on another tile runs on
+
+
+FOLD_TAIL = os.environ.get("IEF_X3P_FOLD_TAIL", "1") == "1"      # 0: the transformer tail keeps FeedForward.net[2] and proj_out as two launches (A/B runs)
+
+
 def gemm(a, w, bias=None, residual=None, rowvec=None, rows_per_batch=0, out=None, out_planes=None, out_scale=1.0,
-         geglu=False, tile=0, splits=0, row_stats=False, ln=None):
+         geglu=False, tile=0, splits=0, row_stats=False, ln=None, a2=None):
     """(a . w^T + bias + rowvec + residual) * out_scale with a: Planes [..., K], w: fp32 weight [N, K] (its planes are cached).
     out: an fp32 tensor to write / True (allocate one) / None (allocate one unless planes are asked for) / False (none);
     out_planes: True / a Planes to receive the result's planes.  Returns the fp32 tensor, the Planes, or (fp32, Planes).
     row_stats=True: a RowStats of the output rows is appended to the result; ln=(RowStats of a's rows, colsum, eps): the launch
-    folds the LayerNorm of its input (w / bias are then the folded ones, `FoldedLN`)."""
+    folds the LayerNorm of its input (w / bias are then the folded ones, `FoldedLN`).
+    a2: Planes [..., K2] -- the A operand is [a | a2] (K-concatenated, never materialised) and w is [N, K1 + K2]; the bits of a plain
+    launch over the concatenated rows.  Not with geglu or ln."""
     lib = hip.load()
     if not isinstance(a, Planes):
         raise TypeError("planes.gemm: a must be Planes")
     M, K, lda = a.rows_ld("a")
+    K1 = 0
+    if a2 is not None:
+        if not isinstance(a2, Planes):
+            raise TypeError("planes.gemm: a2 must be Planes")
+        if geglu or ln is not None:
+            raise ValueError("planes.gemm: a K-concatenated launch takes no geglu and no folded LayerNorm")
+        M2, K2, lda2 = a2.rows_ld("a2")
+        if M2 != M:
+            raise ValueError(f"planes.gemm: a2 has {M2} rows, a has {M}")
+        K1, K = K, K + K2
     N = w.shape[0]
     if w.dim() != 2 or w.shape[1] != K:
         raise ValueError(f"planes.gemm: K mismatch {tuple(w.shape)} vs {K}")
     wp = weight_planes(w)
     p = IefGemmX3pParams()
     p.A, p.planeA, p.lda = a.t.data_ptr(), a.plane, lda
+    if a2 is not None:
+        p.A2, p.planeA2, p.lda2, p.K1 = a2.t.data_ptr(), a2.plane, lda2, K1
     p.W, p.planeW, p.ldw = wp.data_ptr(), wp.stride(0), K
     No = N // 2 if geglu else N
     o32, op = _out_args(p, M, No, out, out_planes, a.device, a.shape[:-1])
@@ -311,10 +332,13 @@ def gemm(a, w, bias=None, residual=None, rowvec=None, rows_per_batch=0, out=None
     else:
         key = f"gemm|{M}|{N}|{K}" + ("|g" if geglu else "")
         if AUTOTUNE and key not in _plan_table() and not hip._capturing() and hip._prof is None:
-            _autotune(key, candidate_plans(M, N, K, geglu=geglu),
+            cands = candidate_plans(M, N, K, geglu=geglu)
+            _autotune(key, [c for c in cands if a2 is None or c[0] in KCAT_TILES],
                       lambda t, sp, wi: gemm(a, wi, bias=bias, residual=residual, rowvec=rowvec, rows_per_batch=rows_per_batch, out=out,
-                                             out_planes=out_planes, out_scale=out_scale, geglu=geglu, tile=t, splits=sp), w)
+                                             out_planes=out_planes, out_scale=out_scale, geglu=geglu, tile=t, splits=sp, a2=a2), w)
         p.tile, p.splits = pick_plan(M, N, K, variant="|g" if geglu else "")
+        if a2 is not None:
+            p.tile = _KCAT_NEAREST.get(p.tile, p.tile)
     if geglu or row_stats or ln is not None:
         p.splits = 1
     rs = None
@@ -331,7 +355,7 @@ def gemm(a, w, bias=None, residual=None, rowvec=None, rows_per_batch=0, out=None
         p.rstat_in, p.rstat_slots, p.rstat_cnt, p.colsum, p.ln_eps = st.buf.data_ptr(), st.slots, st.cnt, colsum.data_ptr(), eps
     ws = hip._fill_epilogue(p, hip._rows_ld32, "planes.gemm", M, N, a.device, bias, rowvec, rows_per_batch, residual, p.splits)       # noqa: F841 (alive until queued)
     nbytes = 4.0 * (M * K + N * K + M * No * ((1 if o32 is not None else 0) + (1 if op is not None else 0)) + (M * N if residual is not None else 0))
-    kn = f"igemm_x3p_kernel<false> t{p.tile}" + (f" {M}x{N}x{K} s{p.splits}" if hip.PROF_SHAPES else "")
+    kn = f"igemm_x3p_kernel<false>{' kcat' if a2 is not None else ''} t{p.tile}" + (f" {M}x{N}x{K} s{p.splits}" if hip.PROF_SHAPES else "")
     bm, bn = _TILES[p.tile]
     hip.note_staged(kn, 4.0 * K * (bm + bn) * -(-M // bm) * -(-N // bn))       # every output tile stages (bm + bn) rows x K x two fp16 planes
     with _Timed(kn, 2.0 * M * N * K, nbytes):

@@ -276,11 +276,12 @@ class Attention(nn.Module):
         w = self.w_qkv if self.w_qkv is not None else self.to_q.weight
         self.ln3 = planes.FoldedLN(w, None, norm.weight, norm.bias, norm.eps)
 
-    def forward_x3p(self, xp, ctx, residual, ln_stats=None, want_stats=False, cfg_rows=None):
+    def forward_x3p(self, xp, ctx, residual, ln_stats=None, want_stats=False, cfg_rows=None, want_planes=False):
         """split-operand mode on operand planes (csrc/gemm_x3p.hip): xp = planes of the LayerNorm'ed input (written by the
         LayerNorm launch) -- or, with ln_stats (planes.RowStats of its rows), planes of the RAW residual stream: the LayerNorm is
         then folded into the input projection.  The attention kernel writes the planes to_out's GEMM stages by LDS-DMA; returns
-        fp32 (the residual stream); want_stats: (fp32, Planes, RowStats) of the output for the next folded LayerNorm.  Same
+        fp32 (the residual stream); want_stats: (fp32, Planes, RowStats) of the output for the next folded LayerNorm;
+        want_planes: (fp32, Planes) -- to_out also writes the planes of the stream (the folded transformer tail reads them).  Same
         dataflow as `forward` (`/root/reference/p2p/model/register.py:11-64`).
         cfg_rows (`hip.BatchRows`, the shared prefix of a CFG step): xp holds the Bp rows both halves of the CFG batch share.  A
         self-attention module then runs at Bp rows (its plan, asked about the FULL batch, must leave it alone); a cross-attention
@@ -358,6 +359,8 @@ class Attention(nn.Module):
         lin = self.to_out[0]
         if want_stats:
             return planes.gemm(o, lin.weight, bias=lin.bias, residual=residual, out=True, out_planes=True, row_stats=True)
+        if want_planes:
+            return planes.gemm(o, lin.weight, bias=lin.bias, residual=residual, out=True, out_planes=True)
         return planes.gemm(o, lin.weight, bias=lin.bias, residual=residual)
 
 
@@ -470,9 +473,12 @@ class BasicTransformerBlock(nn.Module):
             return planes.gemm(g, lin.weight, bias=lin.bias, residual=h, out=True, out_planes=True, row_stats=True)
         return planes.gemm(g, lin.weight, bias=lin.bias, residual=h)
 
-    def forward_x3p(self, h, ctx, last, cfg_rows=None, carry=()):
+    def forward_x3p(self, h, ctx, last, cfg_rows=None, carry=(), fold_tail=False):
         """split-operand mode on operand planes: every LayerNorm writes the planes its GEMM consumes, FeedForward.net[0]
         writes the GEGLU product as planes; last: the block's output is read by proj_out only -> planes only.
+        fold_tail (last block, attn2 native): FeedForward.net[2] is left to the caller, who runs it folded into proj_out
+        (`Transformer2DModel.tail_fold`) -- attn2's to_out also writes the planes of the stream and the block returns
+        (GEGLU product, those planes), both Planes.
         cfg_rows (`hip.BatchRows`; both attention modules native): h holds the Bp rows the halves of a CFG batch share.  The
         self half -- LayerNorm 1, attn1, LayerNorm 2, attn2's query projection -- runs on them; ONE repeat launch then makes the 2 Bp
         rows of attn1's output (the residual of attn2's to_out) and of every tensor in `carry` (what the caller's later launches
@@ -483,14 +489,23 @@ class BasicTransformerBlock(nn.Module):
             n2 = planes.layernorm(h, self.norm2.weight, self.norm2.bias, self.norm2.eps)
             rep = hip.repeat_batch(h, *carry)
             h, carry = (rep[0], tuple(rep[1:])) if carry else (rep, ())
-            h = self.attn2.forward_x3p(n2, ctx, residual=h, cfg_rows=cfg_rows)
+            h = self.attn2.forward_x3p(n2, ctx, residual=h, cfg_rows=cfg_rows, want_planes=fold_tail)
         else:
             h = self._attend_x3p(self.attn1, self.norm1, h, None)
-            h = self._attend_x3p(self.attn2, self.norm2, h, ctx)
+            if fold_tail:
+                h = self.attn2.forward_x3p(planes.layernorm(h, self.norm2.weight, self.norm2.bias, self.norm2.eps), ctx, residual=h,
+                                           want_planes=True)
+            else:
+                h = self._attend_x3p(self.attn2, self.norm2, h, ctx)
+        hp = None
+        if fold_tail:
+            h, hp = h
         n3 = planes.layernorm(h, self.norm3.weight, self.norm3.bias, self.norm3.eps)
         f0, lin = self.ff.net[0].proj, self.ff.net[2]
         g = planes.gemm(n3, f0.weight, bias=f0.bias, geglu=True, out=False, out_planes=True)
-        if last:
+        if fold_tail:
+            r = (g, hp)
+        elif last:
             r = planes.gemm(g, lin.weight, bias=lin.bias, residual=h, out=False, out_planes=True)
         else:
             r = planes.gemm(g, lin.weight, bias=lin.bias, residual=h)
@@ -528,6 +543,20 @@ class Transformer2DModel(nn.Module):
         return self.proj_out(h.reshape(B, H, W, C), residual=x, col_stats=col_stats)
 
 
+    def tail_fold(self):
+        """(wcat, bcat) of the last block's FeedForward.net[2] folded into proj_out, or None: the transformer's tail
+            r = g W2^T + b2 + h (planes only, read by proj_out alone),   out = r Wp^T + bp + x
+        is ONE launch  out = [g | h] [Wp W2 | Wp]^T + (Wp b2 + bp) + x  over K = 4 C + C (`hip.x3_fold_linear_pair`; same FLOPs, one
+        launch, the planes of r and -- where the pair ran split-K -- one reducer less).  The folded weight is derived once per weight
+        set at the first eager forward, never while capturing.  None (the two launches stay): IEF_X3P_FOLD_TAIL=0, the folded
+        LayerNorms (IEF_X3P_FOLD_LN=1: the block then has no planes of h without statistics), a hooked attn2 (the generic path
+        hands back fp32 only)."""
+        blk = self.transformer_blocks[-1]
+        if not planes.FOLD_TAIL or planes.LN_FOLD or not blk.attn2.is_native():
+            return None
+        lin = blk.ff.net[2]
+        return hip.x3_fold_linear_pair(self.proj_out.weight, lin.weight, lin.bias, self.proj_out.bias)
+
     def forward_x3p(self, x, encoder_hidden_states=None, want_planes=False, cfg_rows=None, carry=()):
         """x fp32 NHWC -> (out fp32, Planes | None): GroupNorm writes proj_in's operand planes, the last block's FeedForward
         writes proj_out's; proj_out's epilogue adds the fp32 residual and (want_planes) also emits the planes of the result for
@@ -540,15 +569,18 @@ class Transformer2DModel(nn.Module):
         n = self.norm
         hn = planes.groupnorm(x, n.weight, n.bias, n.num_groups, n.eps, silu=False)
         last = len(self.transformer_blocks) - 1
+        fold = self.tail_fold()
         if cfg_rows is not None:
             h = planes.gemm(hn.reshape(B, H * W, C), self.proj_in.weight, bias=self.proj_in.bias)
             for k, blk in enumerate(self.transformer_blocks):
+                ft = fold is not None and k == last
                 if k == 0:
-                    h, rep = blk.forward_x3p(h, encoder_hidden_states, last=(k == last), cfg_rows=cfg_rows, carry=(x,) + tuple(carry))
+                    h, rep = blk.forward_x3p(h, encoder_hidden_states, last=(k == last), cfg_rows=cfg_rows, carry=(x,) + tuple(carry),
+                                             fold_tail=ft)
                     x, carry = rep[0], rep[1:]
                     B = x.shape[0]
                 else:
-                    h = blk.forward_x3p(h, encoder_hidden_states, last=(k == last))
+                    h = blk.forward_x3p(h, encoder_hidden_states, last=(k == last), fold_tail=ft)
         elif all(blk.foldable_x3p() for blk in self.transformer_blocks):
             h, hp, st = planes.gemm(hn.reshape(B, H * W, C), self.proj_in.weight, bias=self.proj_in.bias, out=True, out_planes=True,
                                     row_stats=True)
@@ -561,9 +593,13 @@ class Transformer2DModel(nn.Module):
         else:
             h = planes.gemm(hn.reshape(B, H * W, C), self.proj_in.weight, bias=self.proj_in.bias)
             for k, blk in enumerate(self.transformer_blocks):
-                h = blk.forward_x3p(h, encoder_hidden_states, last=(k == last))
-        r = planes.gemm(h, self.proj_out.weight, bias=self.proj_out.bias, residual=x.reshape(B, H * W, C), out=True,
-                        out_planes=want_planes)
+                h = blk.forward_x3p(h, encoder_hidden_states, last=(k == last), fold_tail=(fold is not None and k == last))
+        if fold is not None:
+            g, hp = h
+            r = planes.gemm(g, fold[0], a2=hp, bias=fold[1], residual=x.reshape(B, H * W, C), out=True, out_planes=want_planes)
+        else:
+            r = planes.gemm(h, self.proj_out.weight, bias=self.proj_out.bias, residual=x.reshape(B, H * W, C), out=True,
+                            out_planes=want_planes)
         if want_planes:
             r = r[0].reshape(B, H, W, C), r[1].reshape(B, H, W, C)
         else:

@@ -646,8 +646,20 @@ typedef struct IefGemmX3pParams {
     const float* colsum;
     int rstat_slots, rstat_cnt;
     float ln_eps;
+    /* dense, K-CONCATENATED A operand (K1 > 0): out = [A | A2] . W^T -- K columns below K1 are read from A / planeA / lda, the
+     * other K - K1 from A2 / planeA2 / lda2; W stays one [N][K] tensor and the K tiles run in the order of a plain launch over the
+     * concatenated rows (same bits).  K1 and K - K1 multiples of 32 (IEF_ESHAPE), A2 16-byte aligned with lda2 and planeA2
+     * multiples of 8 (IEF_EALIGN); tiles 1, 3, 4 and 6 only, not with conv, geglu or rstat_in (IEF_EINVAL).  Split-K ranges may
+     * straddle K1. */
+    int K1, lda2;
 } IefGemmX3pParams;
 int ief_gemm_x3p(const IefGemmX3pParams* p, void* stream);
+/* Two linears with nothing non-linear between them, folded into one (the tail of a Transformer2DModel: FeedForward.net[2] followed
+ * by proj_out):  (g W2^T + b2 + h) Wp^T + bp = [g | h] [Wp W2 | Wp]^T + (Wp b2 + bp).  wp fp32 [C][C], w2 fp32 [C][K], b2 / bp fp32
+ * [C] or NULL -> wcat fp32 [C][K + C] = [Wp W2 | Wp] and bcat fp32 [C] = Wp b2 + bp; every sum is accumulated in fp64 in
+ * increasing index order and rounded once to fp32. */
+int ief_x3_fold_linear_pair(const float* wp, const float* w2, const float* b2, const float* bp, float* wcat, float* bcat, int C, int K,
+                            void* stream);
 /* Upsample2D's weight in PHASE form for tile 13: w fp32 [Cout][3][3][C] (16-byte aligned, C % 4 == 0) -> fp16 planes
  * [2][4 phases (py, px)][Cout][4 taps (sy, sx)][C] at `scale`.  Output pixel (2y + py, 2x + px) of nearest-2x + 3x3 / pad 1 is a 2x2
  * convolution of the low-resolution image over the taps ty = py + sy, tx = px + sx (3x3 indexing: tap t = low-res row y + t - 1);

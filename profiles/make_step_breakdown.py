@@ -10,7 +10,8 @@ import sys
 
 def family(n):
     if n.startswith("igemm_x3p_kernel"):
-        return "conv (implicit GEMM on planes)" if n.split("(")[0].rstrip(">").endswith("true") else "linear (igemm_x3p)"
+        args = n.split("(")[0].split("<", 1)[1].rstrip(">").split(", ")       # <BM, BN, WAVES_M, WAVES_N, NS, NL, CONV[, KCAT]>
+        return "conv (implicit GEMM on planes)" if args[6] == "true" else "linear (igemm_x3p)"
     if n.startswith("conv3x3_halo_x3p"):
         return "conv (halo on planes)"
     if n.startswith("attn_flash"):
