@@ -567,7 +567,25 @@ extern "C" int ief_softmax_rows_f32(float* x, long long rows, int L, void* strea
 // head) and all 96 output columns (three 32 x 32 accumulators); A = the source rows straight from global memory (lane: row
 // lane & 31, k = 2 step + (lane >> 5)), B = M rows from an LDS copy of the slot's table (M[v][w] = MT[w][v]; padded columns
 // are zero).  One workgroup = 4 waves = 128 rows.
-__global__ __launch_bounds__(256) void p2p_cross_edit_f32_kernel(float* __restrict__ P, const int* __restrict__ edit_src,
+// P_src is the UNEDITED map of the source row.  A source row that the same launch edits too would be overwritten by its own
+// workgroups while ANOTHER row's read it, so `p2p_cross_edit_keep_f32_kernel` copies every edited row that another row names as
+// its source to `keep` beforehand, and the other rows read it from there (keep NULL: the caller vouches that there is none).  A
+// row reading ITSELF needs no copy: a wave reads its 32 map rows whole before it stores the first of them, and no other wave
+// touches them.
+__global__ __launch_bounds__(256) void p2p_cross_edit_keep_f32_kernel(const float* __restrict__ P, float* __restrict__ keep,
+                                                                      const int* __restrict__ edit_src, int B, long long per_row) {
+    const int b = blockIdx.y;
+    const int sb = edit_src[b];
+    if (sb < 0) return;                                  // not edited: nobody overwrites it
+    bool used = false;
+    for (int j = 0; j < B; ++j) used = used || (j != b && edit_src[j] == b);
+    if (!used) return;                                   // uniform over the workgroup
+    const float* src = P + (long long)b * per_row;
+    float* dst = keep + (long long)b * per_row;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < per_row; i += (long long)gridDim.x * 256) dst[i] = src[i];
+}
+__global__ __launch_bounds__(256) void p2p_cross_edit_f32_kernel(float* __restrict__ P, const float* __restrict__ keep,
+                                                                 const int* __restrict__ edit_src,
                                                                  const int* __restrict__ edit_slot, const float* __restrict__ MT,
                                                                  const float* __restrict__ coef, int B, int heads, int N, int L) {
     __shared__ float sm[96 * 97];                        // sm[v * 97 + w] = M[v][w]
@@ -582,7 +600,8 @@ __global__ __launch_bounds__(256) void p2p_cross_edit_f32_kernel(float* __restri
     const int q0 = blockIdx.x * 128 + wv * 32;
     if (q0 >= N) return;
     const int q = min(q0 + li, N - 1);                   // rows past N: computed on a duplicate, never stored
-    const float* ps = P + (((long long)sb * heads + h) * N + q) * L;
+    const float* Ps = (keep && sb != b && edit_src[sb] >= 0) ? keep : P;       // see above
+    const float* ps = Ps + (((long long)sb * heads + h) * N + q) * L;
     f32x16 acc[3];
 #pragma unroll
     for (int t = 0; t < 3; ++t)
@@ -614,14 +633,25 @@ __global__ __launch_bounds__(256) void p2p_cross_edit_f32_kernel(float* __restri
         }
     }
 }
-extern "C" int ief_p2p_cross_edit_f32(float* P, const int* edit_src, const int* edit_slot, const float* MT, const float* coef,
-                                      int B, int heads, int N, int L, void* stream) {
+extern "C" int ief_p2p_cross_edit_keep_f32(float* P, float* keep, const int* edit_src, const int* edit_slot, const float* MT,
+                                           const float* coef, int B, int heads, int N, int L, void* stream) {
     if (!P || !edit_src || !edit_slot || !MT || !coef) return IEF_EINVAL;
     if (B <= 0 || heads <= 0 || N <= 0 || L <= 0 || L > 96) return IEF_ESHAPE;
-    hipLaunchKernelGGL(p2p_cross_edit_f32_kernel, dim3((N + 127) / 128, B * heads), dim3(256), 0, (hipStream_t)stream, P,
+    if (keep) {
+        const long long per_row = (long long)heads * N * L;
+        const int nb = (int)((per_row + 256 * 8 - 1) / (256 * 8));
+        hipLaunchKernelGGL(p2p_cross_edit_keep_f32_kernel, dim3(nb < 64 ? nb : 64, B), dim3(256), 0, (hipStream_t)stream, P, keep,
+                           edit_src, B, per_row);
+        IEF_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(p2p_cross_edit_f32_kernel, dim3((N + 127) / 128, B * heads), dim3(256), 0, (hipStream_t)stream, P, keep,
                        edit_src, edit_slot, MT, coef, B, heads, N, L);
     IEF_LAUNCH_CHECK();
     return IEF_OK;
+}
+extern "C" int ief_p2p_cross_edit_f32(float* P, const int* edit_src, const int* edit_slot, const float* MT, const float* coef,
+                                      int B, int heads, int N, int L, void* stream) {
+    return ief_p2p_cross_edit_keep_f32(P, nullptr, edit_src, edit_slot, MT, coef, B, heads, N, L, stream);
 }
 
 // --------------------------------------------------------------------------------------------- norms

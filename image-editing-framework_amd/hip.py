@@ -844,6 +844,19 @@ def _attn_layout(t, name, dev):
     return h.stride(0), h.stride(1)
 
 
+def _attn_dest(t, name, dev, g):
+    """a destination of the launches that carry its batch stride (IefAttnF32Params.sOb / sOPb, `_fill_attn`): [B, N, C] of the
+    geometry g with unit channel stride, whose rows and batch rows do not overlap -- any batch stride from N * ld up, so o[1::2] of
+    a [2 B, N, C] buffer is fine, like a column slice of a wider one.  dev: the mode's tensor check (returns what the strides are
+    read from)"""
+    h = dev(t, name)
+    if tuple(h.shape) != (g.B, g.N, g.C):
+        raise ValueError(f"{name}: the destination must be [{g.B}, {g.N}, {g.C}], got {tuple(h.shape)}")
+    if h.stride(2) != 1 or h.stride(1) < g.C or (g.B > 1 and h.stride(0) < g.N * h.stride(1)):
+        raise ValueError(f"{name}: expected unit channel stride, a row stride of at least {g.C} and batch rows that do not overlap")
+    return h
+
+
 def _attn_geometry_of(dev, who, q, k, v, heads, out=None, do=None, o=None, **kw):
     """`attn_geometry` of a launch after the mode's tensor check `dev` and the layout check of everything it is given"""
     for t, nm in ((q, "q"), (k, "k"), (v, "v"), (out, "out"), (do, "do"), (o, "o")):
@@ -897,12 +910,28 @@ def _fill_attn(p, g, heads, scale, q, k, v, q_src=None, k_src=None, v_src=None, 
 
 
 def _edit_tables(mt, coef, dtype, who="attn_cross_p2p"):
-    """the Prompt-to-Prompt edit tables of a launch: mt [slots, 96, 96] in the mode's dtype, coef [slots, 2, 96] fp32, contiguous"""
+    """the Prompt-to-Prompt edit tables of a launch: mt [slots, 96, 96] in the mode's dtype, coef [slots, 2, 96] fp32, contiguous,
+    one coefficient pair per table (the kernels index both by edit_slot[b])"""
     if not (isinstance(mt, torch.Tensor) and mt.is_cuda and mt.dtype == dtype):
         raise TypeError(f"{who}: mt must be a {dtype} device tensor")
     _dev32(coef, "coef")
-    if tuple(mt.shape[-2:]) != (96, 96) or not mt.is_contiguous() or coef.shape[-1] != 96:
-        raise ValueError(f"{who}: mt must be contiguous [slots,96,96] {dtype}, coef [slots,2,96] fp32")
+    if mt.dim() != 3 or tuple(mt.shape[1:]) != (96, 96) or not mt.is_contiguous() or tuple(coef.shape) != (mt.shape[0], 2, 96):
+        raise ValueError(f"{who}: mt must be contiguous [slots,96,96] {dtype}, coef [slots,2,96] fp32 with mt's slots, got "
+                         f"{tuple(mt.shape)} / {tuple(coef.shape)}")
+
+
+def _edit_lists(edit_src, edit_slot, B, L, who="attn_cross_p2p"):
+    """the edit pointers of a launch WITH an edit: both given, contiguous int32 device lists of exactly B entries -- the kernels
+    index them by batch row and cannot check them, a short list would be read past its end -- over at most 96 keys (what the
+    tables hold).  The three bindings of the edit (`_attn_cross_p2p_x3`, the fp16 launch of `attn_cross_p2p`, `p2p_cross_edit_`)
+    call it before anything is launched."""
+    if edit_src is None or edit_slot is None:
+        raise ValueError(f"{who}: an edit needs both edit_src and edit_slot")
+    for t, nm in ((edit_src, "edit_src"), (edit_slot, "edit_slot")):
+        if _devi32(t, nm).dim() != 1 or t.numel() != B:
+            raise ValueError(f"{who}: {nm} needs one entry per batch row ({B}), got {tuple(t.shape)}")
+    if L > 96:
+        raise ValueError(f"{who}: the edit tables hold 96 tokens, got {L} keys")
 
 
 def gemm(a, w, bias=None, residual=None, rowvec=None, rows_per_batch=0, out=None, out_scale=1.0, tile_hint=0, splits=1,
@@ -1573,14 +1602,20 @@ def _attn_apply_f32(probs, v, heads, v_src=None, out=None, map_scale=None):
 
 
 def p2p_cross_edit_(probs, B, heads, edit_src, edit_slot, mt32, coef):
-    """in place on fp32 maps [B*heads, N, L]: P'[w] = c1[w] (P_src M)[w] + c2[w] P_tgt[w] for the rows edit_src marks"""
+    """in place on fp32 maps [B*heads, N, L]: P'[w] = c1[w] (P_src M)[w] + c2[w] P_tgt[w] for the rows edit_src marks.  P_src is
+    always the UNEDITED map of the source row: a source row that this launch edits too (from another row) is set aside first, by
+    a launch that copies nothing where no such row exists (the scratch is handed over untouched then)"""
     lib = load()
     _edit_tables(mt32, coef, torch.float32, "p2p_cross_edit_")
     if not _act32(probs, "probs").is_contiguous():
         raise ValueError("p2p_cross_edit_: probs must be contiguous")
-    _check(lib.ief_p2p_cross_edit_f32(probs.data_ptr(), _devi32(edit_src, "edit_src").data_ptr(),
-                                      _devi32(edit_slot, "edit_slot").data_ptr(), mt32.data_ptr(), coef.data_ptr(), B, heads,
-                                      probs.shape[1], probs.shape[2], _stream()), "ief_p2p_cross_edit_f32")
+    if probs.dim() != 3 or probs.shape[0] != B * heads:
+        raise ValueError(f"p2p_cross_edit_: probs must be [B*heads, N, L] = [{B * heads}, N, L], got {tuple(probs.shape)}")
+    _edit_lists(edit_src, edit_slot, B, probs.shape[2], "p2p_cross_edit_")
+    keep = torch.empty_like(probs)
+    _check(lib.ief_p2p_cross_edit_keep_f32(probs.data_ptr(), keep.data_ptr(), edit_src.data_ptr(), edit_slot.data_ptr(),
+                                           mt32.data_ptr(), coef.data_ptr(), B, heads, probs.shape[1], probs.shape[2], _stream()),
+           "ief_p2p_cross_edit_keep_f32")
     return probs
 
 
@@ -1676,16 +1711,23 @@ def _attn_cross_p2p_x3(q, k, v, heads, scale, edit_src, edit_slot, mt32, coef, o
                        q_src=None):
     """`ief_attn_cross_p2p_f32`: the edited cross-attention layer of the f16x3 mode in one launch (maps stay in registers).
     coef_bound: max_w (|c1| + |c2|) over the plan's coefficient tables (sizes the split of the edited maps).
-    edit_src None: plain attention by the same kernel.  q_src (`BatchRows`): the launch's batch is k's; row b reads q[q_src[b]]."""
+    edit_src None: plain attention by the same kernel.  q_src (`BatchRows`): the launch's batch is k's; row b reads q[q_src[b]].
+    out: the caller's fp32 destination (`_attn_dest`: o[1::2] of a wider batch, a column slice); out_planes True: fresh operand
+    planes instead (out is then not used), a `planes.Planes` destination: the caller's planes, and with out= both from one launch."""
     lib = load()
     rows = None if q_src is None else _cfg_rows_of(q_src, q, k)
-    g = _attn_geometry_of(_act32, "attn_cross_p2p", q, k, v, heads, None if out_planes else out, q_src=q_src is not None,
+    g = _attn_geometry_of(_act32, "attn_cross_p2p", q, k, v, heads, q_src=q_src is not None,
                           batch=None if q_src is None else k.shape[0])
     B, N, L, d = g.B, g.N, g.L, g.d
+    if not cross_p2p_x3_ok(d, L):
+        raise ValueError(f"attn_cross_p2p: attn_cross_p2p_x3_kernel has head dims 40 / 64 / 80 / 160 and at most 96 keys, got {d} / {L}")
+    if hasattr(out_planes, "hi"):
+        _attn_dest(out_planes, "out_planes", lambda t, nm: _dev16(t.hi, nm), g)
+    if out is not None and (not out_planes or hasattr(out_planes, "hi")):
+        _attn_dest(out, "out", _act32, g)
     if edit_src is not None:
         _edit_tables(mt32, coef, torch.float32)
-        if _devi32(edit_src, "edit_src").numel() != B or _devi32(edit_slot, "edit_slot").numel() != B:
-            raise ValueError("attn_cross_p2p: edit_src / edit_slot need one entry per batch row")
+        _edit_lists(edit_src, edit_slot, B, L)
     p = IefAttnF32Params()
     res = _fill_attn(p, g, heads, scale, q, k, v, q_src=rows, out=out, out_planes=out_planes)
     p.p_scale = map_split_scale(coef_bound)
@@ -1718,7 +1760,10 @@ def attn_cross_p2p(q, k, v, heads, scale, edit_src=None, edit_slot=None, mt=None
                 return o
         elif _F32_CONTRACT == "x3" and X3_FUSE_CROSS and cross_p2p_x3_ok(q.shape[2] // heads, k.shape[1]):
             return _attn_cross_p2p_x3(q, k, v, heads, scale, edit_src, edit_slot, mt, coef, out, out_planes, coef_bound)
-        _attn_geometry_of(_act32, "attn_cross_p2p", q, k, v, heads, out)
+        g = _attn_geometry_of(_act32, "attn_cross_p2p", q, k, v, heads, out)
+        if edit_src is not None:                # refused before the scores are launched, not between two of the four launches
+            _edit_tables(mt, coef, torch.float32)
+            _edit_lists(edit_src, edit_slot, g.B, g.L)
         probs = _attn_scores_f32(q, k, heads, scale)
         if edit_src is not None:
             p2p_cross_edit_(probs, q.shape[0], heads, edit_src, edit_slot, mt, coef)
@@ -1731,12 +1776,12 @@ def attn_cross_p2p(q, k, v, heads, scale, edit_src=None, edit_slot=None, mt=None
     if out is None:
         out = torch.empty(q.shape[0], q.shape[1], q.shape[2], dtype=torch.float16, device=q.device)
     p = IefCrossParams()
-    _attn_common(p, "attn_cross_p2p", q, k, v, out, heads)
+    g = _attn_common(p, "attn_cross_p2p", q, k, v, out, heads)
     p.scale = scale
-    p.edit_src, p.edit_slot = _ptr(_devi32(edit_src, "edit_src")), _ptr(_devi32(edit_slot, "edit_slot"))
     if edit_src is not None:
         _edit_tables(mt, coef, torch.float16)
-        p.MT, p.coef = mt.data_ptr(), coef.data_ptr()
+        _edit_lists(edit_src, edit_slot, g.B, g.L)
+        p.edit_src, p.edit_slot, p.MT, p.coef = edit_src.data_ptr(), edit_slot.data_ptr(), mt.data_ptr(), coef.data_ptr()
     with _Timed(f"attn_cross_p2p_kernel<{p.d}>", 4.0 * p.B * p.heads * p.N * p.L * p.d,
                 2.0 * p.B * p.heads * p.d * (2 * p.N + 2 * p.L)):
         _check(lib.ief_attn_cross_p2p_f16(byref(p), _stream()), "ief_attn_cross_p2p_f16")

@@ -525,6 +525,12 @@ int ief_softmax_rows_f32(float* x, long long rows, int L, void* stream);
  * [slots][96][96] (M transposed, zero padded), coef fp32 [slots][2][96]; edit_src / edit_slot as IefCrossParams */
 int ief_p2p_cross_edit_f32(float* P, const int* edit_src, const int* edit_slot, const float* MT, const float* coef, int B,
                            int heads, int N, int L, void* stream);
+/* the same with P_src guaranteed to be the UNEDITED map of the source row whatever edit_src holds: an edited row that another row
+ * names as its source is copied to keep (fp32, P's size, contents undefined afterwards) by a first launch and read from there; where
+ * edit_src holds no such row nothing is copied.  keep NULL is ief_p2p_cross_edit_f32: the caller vouches that no source row other
+ * than a row's own is edited by the launch. */
+int ief_p2p_cross_edit_keep_f32(float* P, float* keep, const int* edit_src, const int* edit_slot, const float* MT, const float* coef,
+                                int B, int heads, int N, int L, void* stream);
 /* the four launches above (scores, softmax, edit, apply) as ONE: cross-attention over L <= 96 keys with the map edit applied to
  * maps that stay in registers; split-operand arithmetic (p->x3 is not consulted), d in {40, 64, 80, 160}; edit_src NULL: plain
  * attention (csrc/cross_p2p_x3.hip).  q_src (B entries, or NULL): the maps of row b read Q from batch row q_src[b], those of its
