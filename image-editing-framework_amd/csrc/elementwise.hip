@@ -3,26 +3,9 @@
 #include "ief_common.h"
 #include "ief_params.h"
 #include "ddpm_step.h"
+#include "ddim_step.h"
 
-// eps = eps_u + g (eps_c - eps_u);  x0 = (x - sqrt(1-a_f) eps) / sqrt(a_f);  x' = sqrt(a_t) x0 + sqrt(1-a_t) eps
-// Same operation order as the reference's scheduler.step / ddim_reverse so fp32 results stay
-// within an ulp or two of the eager formula (/root/reference/p2p/model/sd_utils.py:74-76,
-// /root/reference/p2p/inversion/ddim.py:14-17).
-struct DdimCoef { float sb_f, sa_f, sa_t, sb_t, g; };
-__device__ __forceinline__ DdimCoef ddim_coef(const float* __restrict__ coef) {
-    const float a_f = coef[0], a_t = coef[1];
-    return {sqrtf(1.0f - a_f), sqrtf(a_f), sqrtf(a_t), sqrtf(1.0f - a_t), coef[2]};
-}
-// one element of the step, shared by the plain and the rectifying kernel: x' (returned) and the x0 prediction
-__device__ __forceinline__ float cfg_ddim_elem(const DdimCoef& c, const float* __restrict__ eu, const float* __restrict__ ec,
-                                               const float* __restrict__ x, float* __restrict__ x0o, long long i) {
-    float e = ec[i];
-    if (eu) { const float u = eu[i]; e = u + c.g * (e - u); }
-    const float x0 = (x[i] - c.sb_f * e) / c.sa_f;
-    if (x0o) x0o[i] = x0;
-    return c.sa_t * x0 + c.sb_t * e;
-}
-
+// The element of the CFG + DDIM update (DdimCoef, ddim_coef, cfg_ddim_elem) lives in ddim_step.h, shared with prox.hip.
 __global__ __launch_bounds__(256) void cfg_ddim_kernel(const float* __restrict__ eu, const float* __restrict__ ec,
                                                        const float* __restrict__ x, float* __restrict__ xo,
                                                        float* __restrict__ x0o, const float* __restrict__ coef,

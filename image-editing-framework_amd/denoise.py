@@ -14,6 +14,8 @@ overhead would exceed the GPU time.  Here the whole step is captured once:
     [DiffEdit: the same launch puts every row back onto the stored inversion trajectory outside that row's edit mask]
     [LEDITS++: the batch is [uncond | concept_1 .. concept_E] on ONE latent; after the UNet the implicit masks (two one-workgroup
      launches) and the masked multi-concept guidance + eta = 1 update with this step's stored noise map]
+    [proximal guidance on a negative-prompt-inversion edit: the per-row quantile of |eps_c - eps_u| (one workgroup per row), then the
+     thresholded guidance, the update and the pull of x0 towards the encoded source outside the dilated edit mask in one launch]
     [P2P plan with a LocalBlend: the word-masked blend of the updated latents, in place]
     advance_step
 (on the f16x3 planes trunk the UNet takes the latents themselves and runs what both halves of the CFG batch share once: no copy;
@@ -222,6 +224,73 @@ def check_ledits_loop(plan, *, unet_plan, mode, guidance_scale, uncond_list, sou
         raise ValueError(f"ledits: the plan was lowered for latents of {plan.led['hw']}, the loop runs {tuple(row_shape[-2:])}")
 
 
+class ProxGuidance:
+    """The plan of proximal guidance on a negative-prompt-inversion edit (Han et al., "Improving Tuning-Free Real Image Editing with
+    Proximal Guidance"): what a loop's two extra launches (`hip.prox_threshold`, `hip.cfg_ddim_step(prox=)`) need.
+      mode      "l0" (hard) or "l1" (soft) thresholding of eps_c - eps_u at the row's quantile
+      quantile  q in [0, 1]: the per-row quantile of |eps_c - eps_u|
+      radius    0 .. 3: the Chebyshev dilation of the edit mask the inversion guidance spares
+      prox_on   one 0 / 1 per edit step: threshold in this step
+      eta       one number per edit step: the pull of the x0 prediction towards the encoded source outside the mask (0 = none)
+    mode and radius are launch arguments, so they are part of a pooled loop's key; quantile and the two rows are table contents."""
+
+    def __init__(self, mode, quantile, radius, prox_on, eta):
+        if mode not in hip.PROX_MODES:
+            raise ValueError(f"prox: mode is one of {sorted(hip.PROX_MODES)}, got {mode!r}")
+        quantile = float(quantile)
+        if not 0.0 <= quantile <= 1.0:
+            raise ValueError(f"prox: the quantile lies in [0, 1], got {quantile!r}")
+        if isinstance(radius, bool) or not isinstance(radius, int) or not 0 <= radius <= 3:
+            raise ValueError(f"prox: the dilation radius is an integer in [0, 3], got {radius!r}")
+        self.mode, self.quantile, self.radius = mode, quantile, radius
+        self.prox_on = [1.0 if p else 0.0 for p in prox_on]
+        self.eta = [float(e) for e in eta]
+        if len(self.prox_on) != len(self.eta) or not self.eta:
+            raise ValueError(f"prox: {len(self.prox_on)} prox_on entries and {len(self.eta)} eta entries (one each per edit step)")
+
+    @classmethod
+    def from_schedule(cls, timesteps, mode="l0", quantile=0.7, radius=1, prox_steps=None, recon_lr=1.0, recon_t=400):
+        """the plan the command lines build: prox_on in the edit steps [A, B) of `prox_steps` (None: all), eta = recon_lr at the
+        timesteps below recon_t and 0 elsewhere"""
+        ts = [int(t) for t in timesteps]
+        a, b = (0, len(ts)) if prox_steps is None else (int(prox_steps[0]), int(prox_steps[1]))
+        if not 0 <= a <= b <= len(ts):
+            raise ValueError(f"prox: prox_steps {a} {b} outside the {len(ts)} edit steps")
+        return cls(mode, quantile, radius, [a <= i < b for i in range(len(ts))], [float(recon_lr) if t < recon_t else 0.0 for t in ts])
+
+    def rank(self, row_elems):
+        """fp32 [2] = [lo, frac] of the quantile over a row of row_elems values (`control.ledits_rank`, the pinned host rule)"""
+        from .control import ledits_rank
+        return torch.tensor(list(ledits_rank(self.quantile, row_elems)), dtype=torch.float32)
+
+
+def check_prox(plan, *, mode, cfg, uncond_list, source_trajectory, noise_maps, edit_mask, ledits, added_cond_kwargs, local_blend,
+               source_latent, row_shape, num_steps):
+    """the argument checks of a loop under proximal guidance (host-side facts only; raises ValueError): `plan` is a `ProxGuidance`,
+    `source_latent` the encoded source image, fp32 [C, h, w] (or [1, C, h, w])"""
+    if not isinstance(plan, ProxGuidance):
+        raise ValueError("prox: expected a ProxGuidance plan")
+    for other, name, what in ((uncond_list, "uncond_list", "null-text embeddings"),
+                              (source_trajectory, "source_trajectory", "Direct Inversion"),
+                              (noise_maps, "noise_maps", "DDPM inversion"), (edit_mask, "edit_mask", "DiffEdit"),
+                              (ledits, "ledits", "LEDITS++"), (added_cond_kwargs, "added_cond_kwargs", "SDXL"),
+                              (local_blend, "LocalBlend", "a LocalBlend on the controller")):
+        if other is not None and other is not False:
+            raise ValueError(f"prox together with {name}: proximal guidance runs on a negative-prompt-inversion edit, not with {what}")
+    if mode != "denoise" or not cfg:
+        raise ValueError("prox together with a loop without guidance: proximal guidance thresholds eps_c - eps_u, which only a "
+                         "classifier-free-guidance denoising loop forms")
+    if not isinstance(source_latent, torch.Tensor) or source_latent.dtype != torch.float32:
+        raise ValueError("prox: needs source_latent, the encoded source image as one fp32 tensor [C, h, w]")
+    if tuple(source_latent.shape[-3:]) != tuple(row_shape) or source_latent.numel() != row_shape[0] * row_shape[1] * row_shape[2]:
+        raise ValueError(f"prox: source_latent of shape {tuple(source_latent.shape)} for latents of shape {tuple(row_shape)}")
+    if row_shape[0] * row_shape[1] * row_shape[2] > hip.PROX_MAX_ROW:
+        raise ValueError(f"prox: a latent row of {row_shape[0] * row_shape[1] * row_shape[2]} elements, the threshold serves at most "
+                         f"{hip.PROX_MAX_ROW}")
+    if len(plan.eta) != num_steps:
+        raise ValueError(f"prox: the plan's rows cover {len(plan.eta)} edit steps, the loop runs {num_steps}")
+
+
 def _mask_rows(mask, num_latents, device):
     """the device buffer of an edit mask: fp32 [Bp, h, w], one mask per batch row"""
     m = mask.to(device).float()
@@ -233,7 +302,7 @@ class FusedDenoiser:
                  mode: str = "denoise", uncond_list: Optional[List[torch.Tensor]] = None, use_graph: bool = True,
                  added_cond_kwargs=None, source_trajectory: Optional[torch.Tensor] = None,
                  noise_maps: Optional[torch.Tensor] = None, skip: int = 0, edit_mask: Optional[torch.Tensor] = None,
-                 ledits=None, solver_order: int = 1):
+                 ledits=None, solver_order: int = 1, prox=None, source_latent: Optional[torch.Tensor] = None):
         """context: [2*Bp,77,C] (uncond, cond) for mode 'denoise' with CFG, [Bp,77,C] for 'invert' / no-CFG.
         added_cond_kwargs: SDXL's {"text_embeds" [B, 1280], "time_ids" [B, 6]} (one row per UNet batch row); they are
         constant over the steps, so they fold into the per-step time-embedding rows (then one row PER BATCH ROW).
@@ -252,7 +321,11 @@ class FusedDenoiser:
         solver_order (with noise_maps): 1 = the eta = 1 update; 2 = the second-order multistep SDE-DPM-Solver++ on maps extracted
         at order 2 with the same skip (`DDPMInversion.noise_maps(solver_order=2)`): the loop owns the x0 prediction of the previous
         step and a five-column coefficient table {a, p, sigma, dir, c2} (`DDIMScheduler.dpmpp_table`), and its step ends with
-        `ief_cfg_dpmpp_step_f32` / `ief_ledits_dpmpp_step_f32` inside the captured graph."""
+        `ief_cfg_dpmpp_step_f32` / `ief_ledits_dpmpp_step_f32` inside the captured graph.
+        prox, source_latent: proximal guidance on a negative-prompt-inversion edit -- a `ProxGuidance` plan and the encoded source
+        image, fp32 [C, h, w]; the context's unconditional rows are the caller's (NPI: the source prompt's embedding).  The step
+        ends with `hip.prox_threshold` and `hip.cfg_ddim_step(prox=)` in place of the plain update, the coefficient rows are
+        {a_from, a_to, g, prox_on, eta}, and nothing syncs."""
         check_solver_order(solver_order, noise_maps)
         self.solver_order = solver_order
         self.model, self.unet, self.sched = model, model.unet, model.scheduler
@@ -260,6 +333,14 @@ class FusedDenoiser:
         self.mode = mode
         self.cfg = guidance_scale is not None
         self.ledits = ledits
+        self.prox = prox
+        if prox is not None:
+            check_prox(prox, mode=mode, cfg=self.cfg, uncond_list=uncond_list, source_trajectory=source_trajectory,
+                       noise_maps=noise_maps, edit_mask=edit_mask, ledits=ledits, added_cond_kwargs=added_cond_kwargs,
+                       local_blend=getattr(self.unet._plan, "blend_w", None), source_latent=source_latent,
+                       row_shape=(self.unet.config.in_channels, *latent_hw), num_steps=len(self.sched.timesteps))
+        elif source_latent is not None:
+            raise ValueError("source_latent: only a loop under proximal guidance (prox=) reads the encoded source image")
         if ledits is not None:
             check_ledits_loop(ledits, unet_plan=self.unet._plan, mode=mode, guidance_scale=guidance_scale, uncond_list=uncond_list,
                               source_trajectory=source_trajectory, edit_mask=edit_mask, noise_maps=noise_maps, skip=skip,
@@ -308,7 +389,7 @@ class FusedDenoiser:
         if ledits is not None:              # every row of [uncond | concepts] is the one latent
             self.lat_in = torch.zeros(self.B, C, h, w, dtype=torch.float32, device=dev)
         self.step = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.coef_cur = torch.zeros(5 if solver_order == 2 else 4, dtype=torch.float32, device=dev)
+        self.coef_cur = torch.zeros(5 if (solver_order == 2 or prox is not None) else 4, dtype=torch.float32, device=dev)
         # order 2: the x0 prediction the previous step wrote.  Never zeroed: the first step of a run is order 1 and does not read it
         self.x0_prev = None
         if solver_order == 2:
@@ -321,6 +402,12 @@ class FusedDenoiser:
         self.g_rows = None
         # and the edit masks of a DiffEdit loop, one per batch row
         self.mask = None if edit_mask is None else _mask_rows(edit_mask, num_latents, dev)
+        # and the encoded source, the quantile's rank and the per-row thresholds of a loop under proximal guidance
+        self.z0 = self.prox_rank = self.prox_thres = None
+        if prox is not None:
+            self.z0 = source_latent.to(dev).reshape(C, h, w).contiguous().clone()
+            self.prox_rank = prox.rank(C * h * w).to(dev)
+            self.prox_thres = torch.zeros(self.Bp, dtype=torch.float32, device=dev)
         self._fill(context, guidance_scale, uncond_list, added_cond_kwargs)
         self.use_graph = use_graph
         self.graph = None
@@ -359,6 +446,9 @@ class FusedDenoiser:
             put("coef_table", torch.tensor(coef, dtype=torch.float32, device=dev))
             if self.ledits is None:
                 put("g_rows", torch.tensor(guidance_rows(guidance_scale, self.Bp), dtype=torch.float32, device=dev))
+        elif getattr(self, "prox", None) is not None:   # rows {a_from, a_to, g, prox_on, eta}
+            put("coef_table", torch.tensor([[a, b, g, on, eta] for (a, b), on, eta in zip(coef, self.prox.prox_on, self.prox.eta)],
+                                           dtype=torch.float32, device=dev))
         else:
             put("coef_table", torch.tensor([[a, b, g, 0.0] for a, b in coef], dtype=torch.float32, device=dev))
         aug = self.unet.aug_embedding(added_cond_kwargs)          # None unless the UNet has SDXL's additional embedding
@@ -394,7 +484,7 @@ class FusedDenoiser:
                                         **facts(tuple(self.lat.shape[-2:]), ctx_len))
 
     def _key(self, context, uncond_list, source_trajectory=None, noise_maps=None, skip=0, edit_mask=None, ledits=None,
-             solver_order=1):
+             solver_order=1, prox=None):
         plan = self.unet._plan
         key = (id(self.unet), self.mode, self.Bp, tuple(self.lat.shape[-2:]), self.cfg, tuple(context.shape),
                None if uncond_list is None else len(uncond_list), len(self.sched.timesteps),
@@ -404,10 +494,12 @@ class FusedDenoiser:
         # a LEDITS++ loop says so itself (its plan's signature, above, carries E, the mask mode and the module indices)
         key = key if ledits is None else key + ("ledits",)
         # an order-1 loop keeps the key it always had; an order-2 loop (other launches, a wider table) names its solver
-        return key if solver_order == 1 else key + (("solver_order", solver_order),)
+        key = key if solver_order == 1 else key + (("solver_order", solver_order),)
+        # proximal guidance: other launches, and mode and radius are launch arguments (the quantile and the rows are contents)
+        return key if prox is None else key + (("prox", prox.mode, prox.radius),)
 
     def rebind(self, context, guidance_scale, uncond_list, added_cond_kwargs=None, source_trajectory=None, noise_maps=None,
-               skip=0, edit_mask=None, ledits=None, solver_order=1):
+               skip=0, edit_mask=None, ledits=None, solver_order=1, prox=None, source_latent=None):
         """point a captured loop at the next image: new tables, new cross-attention K/V, the new controller's plan, the next
         image's inversion trajectory or noise maps and guidance scales, or its edit masks; a LEDITS++ loop takes the next
         image's concepts, scales and thresholds from the freshly registered plan"""
@@ -416,6 +508,19 @@ class FusedDenoiser:
             raise ValueError(f"rebind: a loop captured at solver order {self.solver_order} serves only jobs of that order")
         if (ledits is None) != (self.ledits is None):
             raise ValueError("rebind: a LEDITS++ loop serves only LEDITS++ jobs, and the reverse")
+        if (prox is None) != (self.prox is None) or (prox is not None and (prox.mode, prox.radius) != (self.prox.mode, self.prox.radius)):
+            raise ValueError("rebind: a loop captured under proximal guidance serves only jobs of the same mode and radius, and the "
+                             "reverse")
+        if prox is not None:
+            check_prox(prox, mode=self.mode, cfg=self.cfg, uncond_list=uncond_list, source_trajectory=source_trajectory,
+                       noise_maps=noise_maps, edit_mask=edit_mask, ledits=ledits, added_cond_kwargs=added_cond_kwargs,
+                       local_blend=getattr(self.unet._plan, "blend_w", None), source_latent=source_latent,
+                       row_shape=tuple(self.lat.shape[1:]), num_steps=len(self.sched.timesteps))
+            self.prox = prox            # `_fill` writes its rows into the coefficient table
+            self.z0.copy_(source_latent.to(self.z0.device).reshape(self.z0.shape))
+            self.prox_rank.copy_(prox.rank(self.z0.numel()))
+        elif source_latent is not None:
+            raise ValueError("source_latent: only a loop under proximal guidance (prox=) reads the encoded source image")
         if ledits is not None:
             check_ledits_loop(ledits, unet_plan=self.unet._plan, mode=self.mode, guidance_scale=guidance_scale, uncond_list=uncond_list,
                               source_trajectory=source_trajectory, edit_mask=edit_mask, noise_maps=noise_maps, skip=skip,
@@ -493,6 +598,12 @@ class FusedDenoiser:
         elif self.mask is not None:
             hip.cfg_ddim_step(eps[: self.Bp], eps[self.Bp:], self.lat, self.coef_cur, out=self.lat,
                               masked=(self.traj, self.step, self.mask))
+        elif self.prox is not None:
+            # the per-row quantile of |eps_c - eps_u| (one workgroup per row), then the thresholded guidance, the update and the
+            # pull towards the encoded source in one launch; this step's prox_on and eta came with the coefficient row
+            hip.prox_threshold(eps[: self.Bp], eps[self.Bp:], self.prox_rank, out=self.prox_thres)
+            hip.cfg_ddim_step(eps[: self.Bp], eps[self.Bp:], self.lat, self.coef_cur, out=self.lat,
+                              prox=(self.prox_thres, self.z0, self.prox.mode, self.prox.radius))
         elif self.cfg:
             hip.cfg_ddim_step(eps[: self.Bp], eps[self.Bp:], self.lat, self.coef_cur, out=self.lat,
                               rect=None if self.traj is None else (self.traj, self.step))
@@ -761,7 +872,7 @@ class CfgSplitDenoiser(FusedDenoiser):
 
 def acquire(model, context, num_latents, latent_hw, guidance_scale, mode="denoise", uncond_list=None,
             use_graph=True, added_cond_kwargs=None, source_trajectory=None, noise_maps=None, skip=0,
-            edit_mask=None, ledits=None, solver_order=1) -> FusedDenoiser:
+            edit_mask=None, ledits=None, solver_order=1, prox=None, source_latent=None) -> FusedDenoiser:
     """a FusedDenoiser for this job: a pooled one with a captured graph of the same shape / plan signature, re-pointed
     at the new context, tables and controller — or a new one.  source_trajectory: Direct Inversion (`FusedDenoiser`); loops
     with and without one never share a pool entry.  noise_maps, skip: edit-friendly DDPM inversion (`FusedDenoiser`;
@@ -769,26 +880,28 @@ def acquire(model, context, num_latents, latent_hw, guidance_scale, mode="denois
     source_trajectory and skip): DiffEdit (`FusedDenoiser`); loops with and without a mask never share a pool entry.  ledits (with
     noise_maps and skip; guidance_scale None): LEDITS++ (`FusedDenoiser`), the 'ledits' plan registered on the UNet -- its signature
     (E, the mask mode, the module indices) is part of the pool key, so pooled loops of different kinds never mix.  solver_order
-    (with noise_maps): 2 = the second-order SDE-DPM-Solver++ step (`FusedDenoiser`); part of the pool key, order-1 keys unchanged"""
+    (with noise_maps): 2 = the second-order SDE-DPM-Solver++ step (`FusedDenoiser`); part of the pool key, order-1 keys unchanged.
+    prox (with source_latent): proximal guidance on a negative-prompt-inversion edit (`ProxGuidance`, `FusedDenoiser`); its mode and
+    radius are part of the pool key, its quantile and per-step rows are contents a pooled loop is re-pointed at"""
     check_solver_order(solver_order, noise_maps)
     if REUSE_GRAPHS and use_graph:
         probe = FusedDenoiser.__new__(FusedDenoiser)
         probe.unet, probe.sched, probe.mode = model.unet, model.scheduler, mode
         probe.cfg, probe.Bp, probe.ledits = guidance_scale is not None, num_latents, ledits
         probe.lat = torch.empty(0, 0, *latent_hw)
-        key = probe._key(context, uncond_list, source_trajectory, noise_maps, skip, edit_mask, ledits, solver_order)
+        key = probe._key(context, uncond_list, source_trajectory, noise_maps, skip, edit_mask, ledits, solver_order, prox)
         free = _POOL.get(key)
         if free:
             loop = free.pop()
             loop.rebind(context, guidance_scale, uncond_list, added_cond_kwargs, source_trajectory, noise_maps, skip, edit_mask, ledits,
-                        solver_order)
+                        solver_order, prox, source_latent)
             return loop
         loop = FusedDenoiser(model, context, num_latents, latent_hw, guidance_scale, mode, uncond_list, use_graph,
-                             added_cond_kwargs, source_trajectory, noise_maps, skip, edit_mask, ledits, solver_order)
+                             added_cond_kwargs, source_trajectory, noise_maps, skip, edit_mask, ledits, solver_order, prox, source_latent)
         loop._pool_key = key
         return loop
     return FusedDenoiser(model, context, num_latents, latent_hw, guidance_scale, mode, uncond_list, use_graph,
-                         added_cond_kwargs, source_trajectory, noise_maps, skip, edit_mask, ledits, solver_order)
+                         added_cond_kwargs, source_trajectory, noise_maps, skip, edit_mask, ledits, solver_order, prox, source_latent)
 
 
 def drop_pool():

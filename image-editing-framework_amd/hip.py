@@ -1830,8 +1830,40 @@ def attn_apply(probs, v, heads, out=None):
 
 
 # ------------------------------------------------------------------------------- sampler
-def cfg_ddim_step(eps_u, eps_c, x, coef, out=None, x0_out=None, rect=None, masked=None):
+PROX_MODES = {"l0": 0, "l1": 1}      # the `mode` argument of ief_cfg_ddim_step_prox_f32
+PROX_MAX_ROW = 65536                 # the longest row ief_prox_threshold_f32 selects over
+
+
+def prox_threshold(eps_u, eps_c, rank, out=None):
+    """proximal guidance's per-row threshold (`ief_prox_threshold_f32`): out[b] = the quantile of |eps_c[b] - eps_u[b]| over the
+    elements of batch row b, t = v_(lo) + frac (v_(lo + 1) - v_(lo)) with exact order statistics.  eps_u, eps_c device fp32
+    [B, ...] of one shape, 1 .. 65536 elements per row; rank device fp32 [2] = [lo, frac] (`control.ledits_rank` of the row
+    length); out device fp32 [B]."""
+    lib = load()
+    _dev32(eps_u, "eps_u")
+    _dev32(eps_c, "eps_c")
+    if eps_u.dim() < 1 or eps_u.shape != eps_c.shape or eps_u.numel() == 0:
+        raise ValueError(f"prox_threshold: eps_u and eps_c must be [B, ...] of one shape, got {tuple(eps_u.shape)} and "
+                         f"{tuple(eps_c.shape)}")
+    B, n = eps_u.shape[0], eps_u[0].numel()
+    if not 1 <= n <= PROX_MAX_ROW:
+        raise ValueError(f"prox_threshold: a row holds 1 .. {PROX_MAX_ROW} elements, got {n}")
+    if _dev32(rank, "rank").numel() != 2:
+        raise ValueError(f"prox_threshold: rank is [lo, frac], one pair for every row, got {tuple(rank.shape)}")
+    if out is None:
+        out = torch.empty(B, dtype=torch.float32, device=eps_u.device)
+    if _dev32(out, "out").numel() != B:
+        raise ValueError(f"prox_threshold: out must hold {B} elements")
+    _check(lib.ief_prox_threshold_f32(eps_u.data_ptr(), eps_c.data_ptr(), rank.data_ptr(), out.data_ptr(), B, n, _stream()),
+           "ief_prox_threshold_f32")
+    return out
+
+
+def cfg_ddim_step(eps_u, eps_c, x, coef, out=None, x0_out=None, rect=None, masked=None, prox=None):
     """x' from (eps_u, eps_c, x) with coef = device fp32 [a_from, a_to, guidance]; eps_u None => no CFG.
+    prox = (thres, z0, mode, radius): the step under proximal guidance (`ief_cfg_ddim_step_prox_f32`) -- x [Bp, C, h, w], coef
+    device fp32 [a_from, a_to, g, prox_on, eta], thres device fp32 [Bp] (`prox_threshold`), z0 device fp32 [C, h, w] the encoded
+    source, mode "l0" / "l1", radius 0 .. 3 the dilation of the edit mask.  Row 0 is the plain step's bit for bit.
     rect = (traj, step): Direct Inversion in the same launch -- batch row 0 of x [Bp, ...] becomes x'[0] + (z - x'[0]) with
     z = traj[clamp(step[0], 0, S - 1)]; traj device fp32 [S, *x.shape[1:]], step device int32 [1] (read by the kernel).
     masked = (traj, step, mask): DiffEdit in the same launch -- x [Bp, C, h, w]; row b keeps x'[b] where mask[b] != 0 and takes
@@ -1840,6 +1872,40 @@ def cfg_ddim_step(eps_u, eps_c, x, coef, out=None, x0_out=None, rect=None, maske
     _dev32(eps_c, "eps_c")
     _dev32(x, "x")
     _dev32(coef, "coef")
+    if prox is not None:
+        if rect is not None or masked is not None:
+            raise ValueError("cfg_ddim_step: prox and rect / masked are different steps; choose one")
+        thres, z0, mode, radius = prox
+        if eps_u is None:
+            raise ValueError("cfg_ddim_step: a proximal step thresholds eps_c - eps_u; it needs eps_u")
+        _dev32(eps_u, "eps_u")
+        _dev32(thres, "prox thresholds")
+        _dev32(z0, "prox source latent")
+        if x.dim() != 4 or eps_c.shape != x.shape or eps_u.shape != x.shape:
+            raise ValueError(f"cfg_ddim_step: a proximal step takes eps_u, eps_c and x as [Bp, C, h, w] of one shape, got "
+                             f"{tuple(eps_u.shape)}, {tuple(eps_c.shape)} and {tuple(x.shape)}")
+        if coef.numel() != 5:
+            raise ValueError(f"cfg_ddim_step: a proximal step's coef is [a_from, a_to, g, prox_on, eta], got {coef.numel()} elements")
+        if thres.numel() != x.shape[0]:
+            raise ValueError(f"cfg_ddim_step: {thres.numel()} thresholds for {x.shape[0]} batch rows")
+        if tuple(z0.shape[-3:]) != tuple(x.shape[1:]) or z0.numel() != x[0].numel():
+            raise ValueError(f"cfg_ddim_step: the source latent must be [{', '.join(map(str, x.shape[1:]))}], got {tuple(z0.shape)}")
+        if mode not in PROX_MODES:
+            raise ValueError(f"cfg_ddim_step: the proximal mode is one of {sorted(PROX_MODES)}, got {mode!r}")
+        if isinstance(radius, bool) or not isinstance(radius, int) or not 0 <= radius <= 3:
+            raise ValueError(f"cfg_ddim_step: the dilation radius is an integer in [0, 3], got {radius!r}")
+        if x[0].numel() > PROX_MAX_ROW:
+            raise ValueError(f"cfg_ddim_step: a proximal step serves rows of at most {PROX_MAX_ROW} elements, got {x[0].numel()}")
+        if out is None:
+            out = torch.empty_like(x)
+        for t, name in ((out, "out"), (x0_out, "x0_out")):
+            if t is not None and (_dev32(t, name).shape != x.shape):
+                raise ValueError(f"cfg_ddim_step: {name} must have the shape of x")
+        _check(lib.ief_cfg_ddim_step_prox_f32(eps_u.data_ptr(), eps_c.data_ptr(), x.data_ptr(), out.data_ptr(), _ptr(x0_out),
+                                              coef.data_ptr(), thres.data_ptr(), z0.data_ptr(), x.numel(), x[0].numel(),
+                                              x.shape[2], x.shape[3], PROX_MODES[mode], radius, _stream()),
+               "ief_cfg_ddim_step_prox_f32")
+        return out
     if masked is not None:
         if rect is not None:
             raise ValueError("cfg_ddim_step: rect and masked are two different steps; choose one")

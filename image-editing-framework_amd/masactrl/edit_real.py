@@ -1,7 +1,10 @@
 """Invert a real image, then edit it with MasaCtrl — CLI of `/root/reference/masactrl/edit_real.py` (same flags and
 defaults: `--inversion_type` "null-text" (:27), `STEP = 4`, `LAYPER = 10`; outputs `./exp/source.png`,
 `./exp/inversion.png`, `./exp/edit.png`).  `--inversion_type direct` (not a reference value): Direct Inversion, the DDIM inversion
-whose trajectory the edit's source row is moved back onto after every step (`ief_amd.p2p.inversion.direct`)."""
+whose trajectory the edit's source row is moved back onto after every step (`ief_amd.p2p.inversion.direct`).
+`--inversion_type npi` (not a reference value): negative-prompt inversion (`ief_amd.masactrl.inversion.npi`) with proximal guidance
+inside the fused step, `--prox l0` by default here (`none`: plain NPI; `l1`: soft thresholding), `--prox_quantile 0.7`,
+`--prox_steps A B` (default all), `--recon_lr 1.0` below timestep `--recon_t 400`, `--dilate_mask 1`.  Not for SDXL pipelines."""
 import argparse
 import os
 import sys
@@ -16,11 +19,13 @@ from ief_amd.masactrl.model.attention_control import (MutualSelfAttentionControl
                                                       MutualSelfAttentionControlMaskAuto, MutualSelfAttentionControlUnion,
                                                       load_mask_png)
 from ief_amd.masactrl.model.register import regiter_attention_editor_diffusers, unregister_attention_control  # noqa: E402
+from ief_amd.masactrl.inversion.npi import NPI  # noqa: E402
 from ief_amd.masactrl.model.sd_utils import MasaCtrl, MasaCtrl_NTI, MasaCtrl_XL, MasaCtrl_XL_NTI  # noqa: E402
 from ief_amd.p2p.inversion.ddim import ddim_inversion, ddim_inversion_xl  # noqa: E402
 from ief_amd.p2p.inversion.direct import DirectInversion, DirectInversion_XL  # noqa: E402
 from ief_amd.p2p.inversion.nti import NTI, NTI_XL_5e2 as NTI_XL  # noqa: E402  (this folder's copy: lr 5e-2)
 from ief_amd.p2p.utils.save_image import save_img  # noqa: E402
+from ief_amd.prox_args import add_prox_arguments, check_prox_arguments  # noqa: E402
 
 parser = argparse.ArgumentParser("General config")
 parser.add_argument("--sd_version", type=str, default="1.5")
@@ -43,17 +48,18 @@ parser.add_argument("--mask_save_dir", type=str, default=None)
 # --union: the target image attends over the source keys AND its own under one softmax (MutualSelfAttentionControlUnion); start
 # step and layer as the plain editor's; not together with --mask_s / --mask_t or --mask_auto
 parser.add_argument("--union", action="store_true")
+add_prox_arguments(parser, default="l0")
 
 STEP, LAYPER = 4, 10
 NUM_INNER_STEPS, EARLY_STOP_EPSILON = 10, 1e-5
 
 
 def edit_one(pipe, editor, invertor, image, source_prompt, target_prompt, inversion_type, device, size,
-             num_inference_steps=50, guidance_scale=7.5, masks=None, auto=None, union=False):
+             num_inference_steps=50, guidance_scale=7.5, masks=None, auto=None, union=False, prox=None):
     """invert + MasaCtrl-edit one PIL image -> uint8 images [2,H,W,3] (reconstruction, edit); :128-153 of the reference.
     masks: optional (mask_s, mask_t) fp32 [h, w] in {0, 1} -> the mask-guided editor; auto: optional dict(thres=, ref_token_idx=,
     cur_token_idx=, mask_save_dir=) -> the editor that makes its masks from cross-attention; union: the editor with united
-    source and target keys"""
+    source and target keys; prox: `check_prox_arguments`' dict for inversion_type "npi" (None: plain negative-prompt inversion)"""
     latent = invertor.image2latent(model=pipe, image=image, device=device, dtype=torch.float32)
     latents, context = invertor.ddim_inversion_loop(pipe, latent, source_prompt)
     extra = {}
@@ -63,6 +69,12 @@ def edit_one(pipe, editor, invertor, image, source_prompt, target_prompt, invers
                                                                      EARLY_STOP_EPSILON, guidance_scale)
     elif inversion_type == "direct":
         extra["source_trajectory"] = invertor.trajectory(latents)
+    elif inversion_type == "npi":
+        extra["negative_prompt_embeds"] = invertor.negative_prompt_embeds(context)
+        if prox is not None:
+            pipe.scheduler.set_timesteps(num_inference_steps)
+            extra["prox"] = invertor.prox_plan(pipe, **prox)
+            extra["source_latent"] = invertor.source_latent(latents)
     elif inversion_type != "ddim":
         raise ValueError("Please choose right inversion type")
     init_latent = torch.cat([latents[-1], latents[-1]])
@@ -94,6 +106,8 @@ def pick(pipe, inversion_type, num_inference_steps=50):
         return (NTI_XL() if xl else NTI()), (MasaCtrl_XL_NTI if xl else MasaCtrl_NTI)(pipe, num_inference_steps)
     if inversion_type == "direct":
         return (DirectInversion_XL() if xl else DirectInversion()), (MasaCtrl_XL if xl else MasaCtrl)(pipe, num_inference_steps)
+    if inversion_type == "npi" and not xl:
+        return NPI(), MasaCtrl(pipe, num_inference_steps)
     raise ValueError("Please choose right inversion type")
 
 
@@ -105,6 +119,7 @@ def main(argv=None):
         parser.error("--mask_auto makes its own masks: not together with --mask_s / --mask_t")
     if args.union and (args.mask_auto or args.mask_s is not None):
         parser.error("--union takes no masks: not together with --mask_s / --mask_t or --mask_auto")
+    prox = check_prox_arguments(parser, args)
     device = torch.device("cuda:{}".format(args.device))
     seed_everything(args.seed)
     num_inference_steps = 50
@@ -119,7 +134,7 @@ def main(argv=None):
     images = edit_one(pipe, editor, invertor, original_image, [args.source_prompt], [args.target_prompt],
                       args.inversion_type, device, size, num_inference_steps, masks=masks,
                       auto=dict(thres=args.thres, ref_token_idx=args.ref_token_idx, cur_token_idx=args.cur_token_idx,
-                                mask_save_dir=args.mask_save_dir) if args.mask_auto else None, union=args.union)
+                                mask_save_dir=args.mask_save_dir) if args.mask_auto else None, union=args.union, prox=prox)
     save_img(images[0], os.path.join(out_path, "inversion.png"))
     save_img(images[1], os.path.join(out_path, "edit.png"))
 

@@ -5,7 +5,7 @@ import torch
 
 from ... import hip
 from ...denoise import acquire
-from ...p2p.model.sd_utils import encode_prompt_xl
+from ...p2p.model.sd_utils import check_npi, encode_prompt_xl, npi_context
 
 
 class MasaCtrl:
@@ -26,10 +26,15 @@ class MasaCtrl:
     @torch.no_grad()
     def __call__(self, prompt, batch_size=1, height=512, width=512, num_inference_steps=50, guidance_scale=7.5,
                  latents=None, unconditioning=None, neg_prompt=None, ref_intermediate_latents=None,
-                 return_intermediates=False, return_latents=False, uncond_embeddings_list=None, source_trajectory=None, **kwds):
+                 return_intermediates=False, return_latents=False, uncond_embeddings_list=None, source_trajectory=None,
+                 negative_prompt_embeds=None, prox=None, source_latent=None, **kwds):
         """source_trajectory (not a reference argument): Direct Inversion -- fp32 [S, C, h, w], row i = z*_{S-1-i} of the source
         image's DDIM inversion (`p2p.inversion.direct.DirectInversion.trajectory`); after every step the source row (prompt 0) is
-        moved back onto it, in the launch of the CFG + DDIM update (`denoise.FusedDenoiser`)."""
+        moved back onto it, in the launch of the CFG + DDIM update (`denoise.FusedDenoiser`).
+        negative_prompt_embeds (not a reference argument): negative-prompt inversion -- the SOURCE prompt's embedding [1, 77, C]
+        (`masactrl.inversion.npi.NPI`), the context of every unconditional row in place of `neg_prompt`'s.
+        prox, source_latent (with negative_prompt_embeds): proximal guidance -- a `denoise.ProxGuidance` plan and the encoded source
+        image, fp32 [C, h, w]; the step loop ends its step with the quantile threshold and the proximal CFG + DDIM update."""
         model = self.model
         dev = model.unet.device
         if isinstance(prompt, list):
@@ -56,7 +61,13 @@ class MasaCtrl:
         if source_trajectory is not None and uncond_list is not None:
             raise ValueError("source_trajectory together with uncond_embeddings_list: choose Direct Inversion or null-text "
                              "embeddings, not both")
-        if guidance_scale > 1.0:
+        check_npi(negative_prompt_embeds, prox, uncond_list=uncond_list, cfg_split=False, low_resource=False)
+        if negative_prompt_embeds is not None and (self.xl or guidance_scale <= 1.0):
+            raise ValueError("negative_prompt_embeds together with " + ("added_cond_kwargs: negative-prompt inversion is built for the "
+                             "SD1.x / SD2.x pipelines" if self.xl else "a loop without guidance: there is no unconditional row"))
+        if guidance_scale > 1.0 and negative_prompt_embeds is not None:
+            context, g = torch.cat([npi_context(negative_prompt_embeds, text_embeddings), text_embeddings]), guidance_scale
+        elif guidance_scale > 1.0:
             uc = tok([neg_prompt or ""] * batch_size, padding="max_length", max_length=tok.model_max_length,
                      return_tensors="pt")
             context = torch.cat([model.text_encoder(uc.input_ids.to(dev))[0], text_embeddings])
@@ -71,7 +82,8 @@ class MasaCtrl:
         # would replay the kernels of the capture pass without calling it)
         native = all(m.is_native() for m in model.unet.attention_modules())
         loop = acquire(model, context, batch_size, (height // 8, width // 8), g, uncond_list=uncond_list,
-                       added_cond_kwargs=added_cond_kwargs, use_graph=native, source_trajectory=source_trajectory)
+                       added_cond_kwargs=added_cond_kwargs, use_graph=native, source_trajectory=source_trajectory,
+                       prox=prox, source_latent=source_latent)
         try:
             latents = loop.run(latents)
         finally:

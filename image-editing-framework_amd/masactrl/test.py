@@ -1,7 +1,8 @@
 """PIE-Bench driver for MasaCtrl — `/root/reference/masactrl/test.py` (per image: invert, then the mutual
 self-attention sampler from `cat([x_T, x_T])`), sharded over the GPUs of one node like `p2p/test.py`: rank r of W takes
 items i with i % W == r, no collective on the data path.  `--synthetic N` replaces the (unavailable) PIE download.
-`--inversion_type`: `ddim`, `null-text`, or `direct` (not a reference value; Direct Inversion, `ief_amd.p2p.inversion.direct`)."""
+`--inversion_type`: `ddim`, `null-text`, `direct` (not a reference value; Direct Inversion, `ief_amd.p2p.inversion.direct`) or `npi`
+(not a reference value; negative-prompt inversion with proximal guidance, `--prox l0` by default, flags as `edit_real.py`)."""
 import argparse
 import json
 import os
@@ -21,6 +22,7 @@ _spec = importlib.util.spec_from_file_location("masactrl_edit_real",
 _mod = importlib.util.module_from_spec(_spec)
 _spec.loader.exec_module(_mod)          # THIS folder's edit_real.py (p2p/ has one of the same name on sys.path)
 edit_one, pick = _mod.edit_one, _mod.pick
+from ief_amd.prox_args import add_prox_arguments, check_prox_arguments  # noqa: E402
 from ief_amd.p2p.dataset.pie import PIE, SyntheticPIE  # noqa: E402
 from ief_amd.p2p.utils.save_image import PngWriter  # noqa: E402
 
@@ -35,7 +37,10 @@ def parse_args(argv=None):
     ap.add_argument("--inversion_type", type=str, default="ddim")
     ap.add_argument("--synthetic", type=int, default=0, help="use N generated images instead of ./PIE")
     ap.add_argument("--no_save", action="store_true")
-    return ap.parse_args(argv)
+    add_prox_arguments(ap, default="l0")
+    args = ap.parse_args(argv)
+    args.prox_plan = check_prox_arguments(ap, args)
+    return args
 
 
 def main(argv=None):
@@ -67,7 +72,8 @@ def main(argv=None):
         for i in mine:
             image_path, source_prompt, target_prompt = items[i]
             original = Image.open(image_path).convert("RGB").resize((size, size))
-            images = edit_one(pipe, editor, invertor, original, [source_prompt], [target_prompt], args.inversion_type, device, size)
+            images = edit_one(pipe, editor, invertor, original, [source_prompt], [target_prompt], args.inversion_type, device, size,
+                              prox=args.prox_plan)
             if not args.no_save:
                 out_path = os.path.join(args.exp_path, os.path.relpath(image_path.split(".")[0], root))
                 os.makedirs(out_path, exist_ok=True)

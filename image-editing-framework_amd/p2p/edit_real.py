@@ -10,6 +10,10 @@ target row; `--seed` also seeds the maps' noise.  Not for SDXL pipelines.  `--nu
 and edit on N steps of the second-order multistep SDE-DPM-Solver++ (LEDITS++'s solver, meant for about 20 steps) instead of 50 eta = 1
 DDPM steps; `--skip` then defaults to 36 % of N.  That 20 second-order steps edit as well as 50 first-order ones is the paper's claim:
 the synthetic weights here cannot show it, so 50 / order 1 stay the defaults.
+`--inversion_type npi` (not a reference value): negative-prompt inversion (`ief_amd.p2p.inversion.npi`) -- the DDIM inversion, and the
+edit's unconditional rows read the source prompt's embedding.  `--prox l0|l1` adds proximal guidance inside the fused step (default
+none here): `--prox_quantile 0.7`, `--prox_steps A B` (default all), `--recon_lr 1.0` below timestep `--recon_t 400`, `--dilate_mask 1`.
+Not for SDXL pipelines, not with blend words.
 """
 import argparse
 import os
@@ -22,12 +26,14 @@ from _bootstrap import load_pipe, seed_everything
 from ief_amd.p2p.inversion.ddim import ddim_inversion, ddim_inversion_xl
 from ief_amd.p2p.inversion.ddpm import DDPMInversion
 from ief_amd.p2p.inversion.direct import DirectInversion, DirectInversion_XL
+from ief_amd.p2p.inversion.npi import NPI
 from ief_amd.p2p.inversion.nti import NTI, NTI_XL
 from ief_amd.p2p.model.attention_control import AttentionRefine, AttentionReplace
 from ief_amd.p2p.model.ptp_utils import local_blend_from_words
 from ief_amd.p2p.model.register import unregister_attention_control
 from ief_amd.p2p.model.sd_utils import P2P, P2P_NTI, P2P_XL, P2P_XL_NTI
 from ief_amd.p2p.utils.save_image import save_img
+from ief_amd.prox_args import add_prox_arguments, check_prox_arguments
 from ief_amd.solver_args import NUM_STEPS, StoreGiven, add_solver_arguments, check_solver_arguments, resolve_skip
 
 XL_VERSIONS = ("xl-base", "smallxl")       # the `StableDiffusionXLPipeline` branch of `_bootstrap._build_pipe`
@@ -90,6 +96,7 @@ parser.add_argument("--blend_source_words", type=str, nargs="+", default=None)
 parser.add_argument("--blend_target_words", type=str, nargs="+", default=None)
 parser.add_argument("--blend_threshold", type=float, default=0.3)
 add_ddpm_arguments(parser)
+add_prox_arguments(parser, default="none")
 parser.add_argument("--invert_batch", type=int, default=4, help="--inversion_type ddpm: rows (timesteps) per UNet launch, at CFG batch 2 K (8 measured fastest on SD1.5)")
 
 
@@ -114,6 +121,17 @@ def edit_latent(pipe, editor, x_T, source_prompt, target_prompt, edit_type, devi
     return images
 
 
+def npi_extra(pipe, invertor, latents, context, prox, num_inference_steps=50):
+    """the sampler arguments of a negative-prompt-inversion edit from the DDIM inversion's (latents, context): the source embedding
+    as negative context, and with `prox` (`check_prox_arguments`' dict) the proximal plan and the encoded source"""
+    extra = {"negative_prompt_embeds": invertor.negative_prompt_embeds(context)}
+    if prox is not None:
+        pipe.scheduler.set_timesteps(num_inference_steps)
+        extra["prox"] = invertor.prox_plan(pipe, **prox)
+        extra["source_latent"] = invertor.source_latent(latents)
+    return extra
+
+
 def ddpm_invert(pipe, invertor, latent, source_prompt, num_inference_steps, ddpm):
     """the noise maps of one encoded image -> (y_skip [1,4,h,w], maps [S - skip,4,h,w])"""
     pipe.scheduler.set_timesteps(num_inference_steps)
@@ -126,9 +144,10 @@ def ddpm_invert(pipe, invertor, latent, source_prompt, num_inference_steps, ddpm
 
 def edit_one(pipe, editor, invertor, image, source_prompt, target_prompt, inversion_type, edit_type, device,
              num_inference_steps=50, guidance_scale=7.5, cross_replace_steps=0.8, self_replace_steps=0.6,
-             num_inner_steps=10, early_stop_epsilon=1e-5, local_blend=None, ddpm=None):
+             num_inner_steps=10, early_stop_epsilon=1e-5, local_blend=None, ddpm=None, prox=None):
     """invert + edit one PIL image -> uint8 images [2,H,W,3] (inversion reconstruction, edit).  ddpm: `check_ddpm_arguments`' dict
-    for inversion_type "ddpm" (its `seed` seeds this image's noise)"""
+    for inversion_type "ddpm" (its `seed` seeds this image's noise); prox: `check_prox_arguments`' dict for inversion_type "npi"
+    (None: plain negative-prompt inversion)"""
     latent = invertor.image2latent(model=pipe, image=image, device=device, dtype=torch.float32)
     if inversion_type == "ddpm":
         num_inference_steps = ddpm.get("num_steps", num_inference_steps)
@@ -144,6 +163,8 @@ def edit_one(pipe, editor, invertor, image, source_prompt, target_prompt, invers
                                                                      early_stop_epsilon, guidance_scale)
     elif inversion_type == "direct":
         extra["source_trajectory"] = invertor.trajectory(latents)
+    elif inversion_type == "npi":
+        extra.update(npi_extra(pipe, invertor, latents, context, prox, num_inference_steps))
     elif inversion_type != "ddim":
         raise ValueError("Please choose right inversion type")
     return edit_latent(pipe, editor, latents[-1], source_prompt, target_prompt, edit_type, device, extra,
@@ -153,6 +174,7 @@ def edit_one(pipe, editor, invertor, image, source_prompt, target_prompt, invers
 def main(argv=None):
     args = parser.parse_args(argv)
     ddpm = check_ddpm_arguments(parser, args)
+    prox = check_prox_arguments(parser, args, blend=args.blend_source_words is not None or args.blend_target_words is not None)
     if (args.blend_source_words is None) != (args.blend_target_words is None):
         parser.error("--blend_source_words and --blend_target_words go together")
     device = torch.device("cuda:{}".format(args.device))
@@ -173,6 +195,9 @@ def main(argv=None):
     elif args.inversion_type == "ddpm":
         editor = P2P(model=pipe, num_inference_steps=args.num_steps)
         invertor = DDPMInversion()
+    elif args.inversion_type == "npi":
+        editor = P2P(model=pipe, num_inference_steps=50)
+        invertor = NPI()
     else:
         raise ValueError("Please choose right inversion type")
     size = pipe.unet.config.sample_size * pipe.vae_scale_factor
@@ -183,7 +208,7 @@ def main(argv=None):
                       edit_type, device,
                       local_blend=local_blend_from_words(pipe.tokenizer, [args.source_prompt, args.target_prompt],
                                                          args.blend_source_words, args.blend_target_words, args.blend_threshold,
-                                                         device), ddpm=ddpm)
+                                                         device), ddpm=ddpm, prox=prox)
     save_img(images[0], os.path.join(out_path, "inversion.png"))
     save_img(images[1], os.path.join(out_path, "edit.png"))
 

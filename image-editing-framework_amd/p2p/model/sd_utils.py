@@ -57,6 +57,32 @@ def encode_prompt_xl(model, prompt, device, do_classifier_free_guidance, height,
     return prompt_embeds.to(device), {"text_embeds": add_text_embeds.to(device), "time_ids": add_time_ids}
 
 
+def npi_context(negative_prompt_embeds, text_embeddings):
+    """negative-prompt inversion's unconditional half: the source prompt's embedding [1, 77, C] (or [77, C]) in EVERY row"""
+    neg = negative_prompt_embeds
+    if not isinstance(neg, torch.Tensor) or neg.dim() not in (2, 3) or (neg.dim() == 3 and neg.shape[0] != 1) or \
+            tuple(neg.shape[-2:]) != tuple(text_embeddings.shape[-2:]):
+        raise ValueError(f"negative_prompt_embeds: expected the source prompt's embedding [1, {text_embeddings.shape[-2]}, "
+                         f"{text_embeddings.shape[-1]}], got {tuple(getattr(neg, 'shape', ()))}")
+    neg = neg.reshape(1, *neg.shape[-2:]).to(device=text_embeddings.device, dtype=text_embeddings.dtype)
+    return neg.expand(*text_embeddings.shape).contiguous()
+
+
+def check_npi(negative_prompt_embeds, prox, *, uncond_list, cfg_split, low_resource):
+    """what a negative-prompt-inversion edit and proximal guidance exclude (host-side facts only; raises ValueError)"""
+    if negative_prompt_embeds is not None and uncond_list is not None:
+        raise ValueError("negative_prompt_embeds together with uncond_embeddings_list: choose negative-prompt inversion or null-text "
+                         "embeddings, not both")
+    if prox is None:
+        return
+    if negative_prompt_embeds is None:
+        raise ValueError("prox without negative_prompt_embeds: proximal guidance is built on negative-prompt inversion")
+    if cfg_split:
+        raise ValueError("prox together with the CFG split: proximal guidance is not built for the two-GPU split")
+    if low_resource:
+        raise ValueError("prox together with low_resource: proximal guidance runs inside the fused step loop")
+
+
 def _fusable(model, controller, low_resource) -> bool:
     if low_resource:
         return False
@@ -86,7 +112,7 @@ class P2P:
                               latent: Optional[torch.FloatTensor] = None, low_resource: bool = False,
                               uncond_embeddings_list=None, height: Optional[int] = None, width: Optional[int] = None,
                               return_latents: bool = False, cfg_split_group=None, source_trajectory=None, noise_maps=None,
-                              skip: int = 0, solver_order: int = 1):
+                              skip: int = 0, solver_order: int = 1, negative_prompt_embeds=None, prox=None, source_latent=None):
         """cfg_split_group (not a reference argument): a torch.distributed group of TWO ranks that run this ONE edit
         together — rank 0 the unconditional rows of the CFG batch, rank 1 the conditional rows, one eps exchange per
         step (`denoise.CfgSplitDenoiser`); both ranks return the same latents / images.
@@ -98,8 +124,14 @@ class P2P:
         them from 0), every step is the eta = 1 update with that step's map on every row, and `guidance_scale` may be a sequence
         of one scale per prompt (the source prompt takes the scale the maps were extracted with).
         solver_order (with noise_maps): 2 = the second-order multistep SDE-DPM-Solver++ step on maps extracted at order 2 with the
-        same skip (`DDPMInversion.noise_maps(solver_order=2)`); 1 (default) = the eta = 1 update."""
+        same skip (`DDPMInversion.noise_maps(solver_order=2)`); 1 (default) = the eta = 1 update.
+        negative_prompt_embeds (not a reference argument): negative-prompt inversion -- [1, 77, C] (or [77, C]), the SOURCE prompt's
+        embedding (`inversion.npi.NPI`), the context of EVERY unconditional row in place of the empty prompt's.
+        prox, source_latent (with negative_prompt_embeds): proximal guidance -- a `denoise.ProxGuidance` plan and the encoded source
+        image, fp32 [C, h, w]; the fused loop ends its step with the quantile threshold and the proximal CFG + DDIM update."""
         check_solver_order(solver_order, noise_maps)
+        check_npi(negative_prompt_embeds, prox, uncond_list=uncond_embeddings_list, cfg_split=cfg_split_group is not None,
+                  low_resource=low_resource)
         if source_trajectory is not None and uncond_embeddings_list is not None:
             raise ValueError("source_trajectory together with uncond_embeddings_list: choose Direct Inversion or null-text "
                              "embeddings, not both")
@@ -128,15 +160,23 @@ class P2P:
         uncond_embeddings, text_embeddings, added_cond_kwargs = self._encode(model, prompt, height, width)
         latent, latents = self.init_latent(latent, model, height, width, generator, batch_size)
         model.scheduler.set_timesteps(num_inference_steps)
+        if negative_prompt_embeds is not None:
+            if added_cond_kwargs is not None:
+                raise ValueError("negative_prompt_embeds together with added_cond_kwargs: negative-prompt inversion is built for the "
+                                 "SD1.x / SD2.x pipelines")
+            uncond_embeddings = npi_context(negative_prompt_embeds, text_embeddings)
         context = torch.cat([uncond_embeddings, text_embeddings])
         if _fusable(model, controller, low_resource):
             loop = acquire(model, context, batch_size, (height // 8, width // 8), guidance_scale,
                                  uncond_list=uncond_embeddings_list, added_cond_kwargs=added_cond_kwargs,
-                                 source_trajectory=source_trajectory, noise_maps=noise_maps, skip=skip, solver_order=solver_order)
+                                 source_trajectory=source_trajectory, noise_maps=noise_maps, skip=skip, solver_order=solver_order,
+                                 prox=prox, source_latent=source_latent)
             try:
                 latents = loop.run(latents)
             finally:
                 loop.release()
+        elif prox is not None:
+            raise ValueError("prox: proximal guidance runs inside the fused step loop; this controller / low_resource run steps eagerly")
         elif noise_maps is not None:
             if added_cond_kwargs is not None:
                 raise ValueError("noise_maps: DDPM inversion is built for the SD1.x / SD2.x pipelines")
@@ -220,7 +260,9 @@ class P2P:
         [(prompts, controller, x_T, None, source_trajectory)] (Direct Inversion, as `text2image_ldm_stable`) or
         [(prompts, controller, y_skip, None, None, (noise_maps, skip, guidance scales))] (edit-friendly DDPM inversion: the sixth
         element; its scales, one per prompt or one number, replace `guidance_scale` for that job; a fourth entry is the job's
-        solver order, 1 where it is left out);
+        solver order, 1 where it is left out) or
+        [(prompts, controller, x_T, None, None, None, negative_prompt_embeds)] (negative-prompt inversion: the seventh element,
+        the source embedding every unconditional row reads);
         every controller must be one of the lowered classes.  Each job's loop is captured while its controller is
         registered, then all loops are stepped in turn on their own streams (`denoise.run_interleaved`).  Returns
         [(images uint8 [len(prompts),H,W,3], x_T)] — the same values as one `text2image_ldm_stable` call per job."""
@@ -239,12 +281,19 @@ class P2P:
                 solver_order = job[5][3] if len(job) > 5 and job[5] is not None and len(job[5]) > 3 else 1
                 if noise_maps is not None and (uncond_list is not None or source_trajectory is not None):
                     raise ValueError("edit_many: a job brings ONE of noise maps, a source trajectory and null-text embeddings")
+                negative = job[6] if len(job) > 6 else None
+                check_npi(negative, None, uncond_list=uncond_list, cfg_split=False, low_resource=False)
                 register_attention_control(model, controller)
                 if not _fusable(model, controller, False):
                     raise RuntimeError("edit_many: only controllers lowered to a device plan can run concurrently")
                 # `_encode`: the SD1.x / 2.x text encoder, or (P2P_XL) both SDXL encoders + pooled embedding / time ids
                 uncond_embeddings, text_embeddings, added_cond_kwargs = self._encode(model, prompt, height, width)
                 latent, latents = self.init_latent(latent, model, height, width, None, len(prompt))
+                if negative is not None:
+                    if added_cond_kwargs is not None:
+                        raise ValueError("negative_prompt_embeds together with added_cond_kwargs: negative-prompt inversion is built "
+                                         "for the SD1.x / SD2.x pipelines")
+                    uncond_embeddings = npi_context(negative, text_embeddings)
                 loop = acquire(model, torch.cat([uncond_embeddings, text_embeddings]), len(prompt),
                                      (height // 8, width // 8), g_job, uncond_list=uncond_list,
                                      added_cond_kwargs=added_cond_kwargs, source_trajectory=source_trajectory,

@@ -29,6 +29,10 @@ settings; image i of a shard draws its noise from a CPU generator seeded `--seed
 change the pixels; K is part of the numerics in the fp32-storage modes (a batched forward equals batch-1 forwards to 1e-6 of eps, as
 for the batched DDIM inversion).  Not for SDXL pipelines.  `--num_steps N --solver_order 2` (ddpm only): N steps of the second-order
 multistep SDE-DPM-Solver++ for inversion and edit (`edit_real.py`); `--skip` then defaults to int(0.36 N).
+`--inversion_type npi` (not a reference value): negative-prompt inversion (`ief_amd.p2p.inversion.npi`) -- only another context for
+the unconditional rows, so `--invert_batch` / `--in_flight` work as for `ddim`.  `--prox l0|l1` (with its `--prox_quantile`,
+`--prox_steps`, `--recon_lr`, `--recon_t`, `--dilate_mask`; `edit_real.py`) adds proximal guidance inside the fused step: one edit at a
+time (`--in_flight 1`).  Not for SDXL pipelines.
 """
 import argparse
 import json
@@ -40,13 +44,15 @@ from PIL import Image
 
 from _bootstrap import load_pipe, seed_everything
 
-from edit_real import XL_VERSIONS, add_ddpm_arguments, check_ddpm_arguments, ddpm_invert, edit_latent, edit_one
+from edit_real import XL_VERSIONS, add_ddpm_arguments, check_ddpm_arguments, ddpm_invert, edit_latent, edit_one, npi_extra
 from ief_amd.p2p.model.attention_control import AttentionRefine, AttentionReplace
 from ief_amd.p2p.dataset.pie import PIE, SyntheticPIE
 from ief_amd.p2p.inversion.ddim import ddim_inversion, ddim_inversion_xl
 from ief_amd.p2p.inversion.ddpm import DDPMInversion
 from ief_amd.p2p.inversion.direct import DirectInversion, DirectInversion_XL
+from ief_amd.p2p.inversion.npi import NPI
 from ief_amd.p2p.inversion.nti import NTI, NTI_XL
+from ief_amd.prox_args import add_prox_arguments, check_prox_arguments
 from ief_amd.p2p.model.sd_utils import P2P, P2P_NTI, P2P_XL, P2P_XL_NTI
 from ief_amd.p2p.utils.save_image import PngWriter
 
@@ -63,16 +69,20 @@ def edit_type_of(source_prompt: str, target_prompt: str) -> str:
 
 
 def run_items(pipe, editor, invertor, items, size, device, inversion_type="ddim", invert_batch=1, in_flight=1, save=None,
-              nti_batch=1, ddpm=None):
+              nti_batch=1, ddpm=None, prox=None):
     """the per-image loop of `/root/reference/p2p/test.py:116-181` over `items` = [(image path, source prompt, target
     prompt)]; `save(image_path, original PIL image, uint8 images [2,H,W,3])` is called per image.  invert_batch /
     in_flight = 1 is the reference's order (invert one image, edit it, next); see the module docstring for the others.
     nti_batch > 1: the null-text optimisations run in groups of nti_batch through one batched optimiser.
     ddpm: `edit_real.check_ddpm_arguments`' dict for inversion_type "ddpm" (`_run_ddpm_chunk`; invert_batch is then its rows per launch).
+    prox: `check_prox_arguments`' dict for inversion_type "npi" (None: plain negative-prompt inversion); in_flight stays 1 with it.
     Also what `bench.py` times for its images/sec figures."""
     save = save or (lambda *a: None)
     nti = inversion_type == "null-text"
     direct = inversion_type == "direct"
+    npi = inversion_type == "npi"
+    if prox is not None and max(1, in_flight) > 1:
+        raise ValueError("prox together with in_flight > 1: proximal guidance runs one edit at a time")
     bs = max(1, invert_batch)
     E = max(1, in_flight)
     nb = max(1, nti_batch) if nti else 1
@@ -85,7 +95,7 @@ def run_items(pipe, editor, invertor, items, size, device, inversion_type="ddim"
                 image_path, source_prompt, target_prompt = chunk[0]
                 images = edit_one(pipe, editor, invertor, originals[0], [source_prompt], [target_prompt], inversion_type,
                                   edit_type_of(source_prompt, target_prompt), device,
-                                  ddpm=None if ddpm is None else dict(ddpm, seed=ddpm["seed"] + c0))
+                                  ddpm=None if ddpm is None else dict(ddpm, seed=ddpm["seed"] + c0), prox=prox)
                 save(image_path, originals[0], images)
                 continue
             if ddpm is not None:
@@ -109,6 +119,8 @@ def run_items(pipe, editor, invertor, items, size, device, inversion_type="ddim"
             x_T = [t[-1] for t in traj]
             # Direct Inversion: per image, the rows its edit's source branch is moved back onto
             rows = [invertor.trajectory(t) if direct else None for t in traj]
+            # negative-prompt inversion: per image, the source embedding (and the proximal plan with the encoded source)
+            npis = [npi_extra(pipe, invertor, t, c, prox) if npi else None for t, c in zip(traj, ctxs)]
             # null-text optimisation: E images in flight
             uncond = [None] * len(chunk)
             if nti and nb > 1:
@@ -125,7 +137,7 @@ def run_items(pipe, editor, invertor, items, size, device, inversion_type="ddim"
                 if len(part) == 1:
                     j = part[0]
                     _, src, tgt = chunk[j]
-                    extra = {"uncond_embeddings_list": uncond[j]} if nti else ({"source_trajectory": rows[j]} if direct else None)
+                    extra = {"uncond_embeddings_list": uncond[j]} if nti else ({"source_trajectory": rows[j]} if direct else npis[j])
                     results = [edit_latent(pipe, editor, x_T[j], [src], [tgt], edit_type_of(src, tgt), device, extra)]
                 else:
                     jobs, ctrls = [], []
@@ -135,7 +147,8 @@ def run_items(pipe, editor, invertor, items, size, device, inversion_type="ddim"
                         ctrl = cls(prompts=[src, tgt], tokenizer=pipe.tokenizer, num_steps=50, cross_replace_steps=0.8,
                                    self_replace_steps=0.6, device=device)
                         ctrls.append(ctrl)
-                        jobs.append(([src, tgt], ctrl, x_T[j]) + ((uncond[j],) if nti else ((None, rows[j]) if direct else ())))
+                        jobs.append(([src, tgt], ctrl, x_T[j]) + ((uncond[j],) if nti else ((None, rows[j]) if direct else (
+                            (None, None, None, npis[j]["negative_prompt_embeds"]) if npi else ()))))
                     results = [im for im, _ in editor.edit_many(pipe, jobs, num_inference_steps=50, guidance_scale=7.5)]
                     for ctrl in ctrls:
                         ctrl.reset()
@@ -188,8 +201,10 @@ def parse_args(argv=None):
                     help="null-text optimisations per UNet batch (1: per image, --in_flight of them at a time); not for SDXL")
     ap.add_argument("--seed", type=int, default=42, help="global seed; with --inversion_type ddpm also the seed of the maps' noise")
     add_ddpm_arguments(ap)
+    add_prox_arguments(ap, default="none")
     args = ap.parse_args(argv)
     args.ddpm = check_ddpm_arguments(ap, args, args.nti_batch)
+    args.prox_plan = check_prox_arguments(ap, args, in_flight=args.in_flight, nti_batch=args.nti_batch)
     if args.nti_batch < 1:
         ap.error("--nti_batch must be >= 1")
     if args.nti_batch > 1 and args.inversion_type == "direct":
@@ -225,6 +240,9 @@ def main(argv=None):
     elif args.inversion_type == "ddpm":
         editor = P2P(model=pipe, num_inference_steps=args.num_steps)
         invertor = DDPMInversion()
+    elif args.inversion_type == "npi":
+        editor = P2P(model=pipe, num_inference_steps=50)
+        invertor = NPI()
     else:
         raise ValueError("Please choose right inversion type")
     size = pipe.unet.config.sample_size * pipe.vae_scale_factor
@@ -254,7 +272,7 @@ def main(argv=None):
             writer.save_img(images[1], os.path.join(out_path, "edit.png"))
 
         run_items(pipe, editor, invertor, [items[i] for i in mine], size, device, args.inversion_type, args.invert_batch,
-                  args.in_flight, save, nti_batch=args.nti_batch, ddpm=args.ddpm)
+                  args.in_flight, save, nti_batch=args.nti_batch, ddpm=args.ddpm, prox=args.prox_plan)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     n = torch.tensor([float(len(mine)), dt], device=device)

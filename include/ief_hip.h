@@ -324,6 +324,37 @@ int ief_ledits_ddpm_step_f32(const float* eps, const float* mask, const float* s
 int ief_ledits_dpmpp_step_f32(const float* eps, const float* mask, const float* scale, const float* x, float* x_out, float* x0_out,
                               float* x0_prev, const float* coef, long long row_elems, long long hw, const float* noise,
                               int noise_rows, const int* step, int E, void* stream);
+/* Proximal guidance on a negative-prompt-inversion edit (Miyake et al., "Negative-prompt Inversion"; Han et al., "Improving
+ * Tuning-Free Real Image Editing with Proximal Guidance"), two launches (csrc/prox.hip).  All arithmetic fp32, every operation
+ * rounded on its own; one writer per element, no atomics on global memory, no buffer the caller must zero, the same bits from run
+ * to run.  The UNet batch is [u_0 .. u_(B-1) | c_0 .. c_(B-1)]; row 0 is the source, rows >= 1 are targets.
+ * ief_prox_threshold_f32: thres_out[b] = the quantile of |eps_c - eps_u| over the row_elems elements of batch row b, by THE QUANTILE
+ * RULE of the LEDITS++ launches above:  t = v_(lo) + frac (v_(hi) - v_(lo)),  hi = min(lo + 1, row_elems - 1), both order statistics
+ * exact.  rank: DEVICE fp32 [2] = {lo, frac}, one pair for every row (the rows have one length), formed on the host as there.
+ * eps_u, eps_c fp32 [B][row_elems]; thres_out fp32 [B].  One workgroup per row, the row's values in registers.
+ * IEF_EINVAL: a null pointer; IEF_ESHAPE: B < 1, row_elems outside [1, 65536]; IEF_EALIGN: a pointer off the 4-byte grid.  Nothing
+ * is launched by a refused call (this holds for both). */
+int ief_prox_threshold_f32(const float* eps_u, const float* eps_c, const float* rank, float* thres_out, int B, long long row_elems,
+                           void* stream);
+/* The CFG + DDIM step under proximal guidance.  For element i = b row_elems + c h w + p, with d = eps_c - eps_u and
+ * lambda = thres[b]:
+ *   rows b >= 1 with prox_on != 0:   mode 0 (l0)  d' = |d| > lambda ? d : 0
+ *                                    mode 1 (l1)  d' = d > lambda ? d - lambda : (d < -lambda ? d + lambda : 0);    otherwise d' = d
+ *   eps = eps_u + g d';   x0 = (x - sqrt(1 - a_from) eps) / sqrt(a_from)      (the device function of ief_cfg_ddim_step_f32)
+ *   rows b >= 1 with eta != 0:       m = 1 if any element of the same row and channel within Chebyshev distance radius of pixel p
+ *                                    has |d| > lambda (pixels outside the image count as 0); with prox_on == 0, m = 1 everywhere;
+ *                                    x0 = m ? x0 : x0 - eta (x0 - z0[c h w + p])
+ *   x_out = sqrt(a_to) x0 + sqrt(1 - a_to) eps;   x0_out (optional) = the x0 above
+ * Row 0 is never thresholded and never pulled: it equals ief_cfg_ddim_step_f32's x_out and x0_out bit for bit, and so does every
+ * row when prox_on == 0 and eta == 0.  coef: DEVICE fp32 [5] = {a_from, a_to, g, prox_on, eta}; thres: DEVICE fp32 [n / row_elems]
+ * (ief_prox_threshold_f32's output); z0: DEVICE fp32 [row_elems], the encoded source latent; eps_u, eps_c, x, x_out fp32 [n].
+ * x_out == x allowed (the stencil reads eps_u and eps_c only); x0_out must not overlap the inputs.
+ * IEF_EINVAL: a null eps_u / eps_c / x / x_out / coef / thres / z0; IEF_ESHAPE: n <= 0, row_elems outside [1, 65536],
+ * n % row_elems != 0, h < 1, w < 1, row_elems no multiple of h w, mode not 0 or 1, radius outside [0, 3]; IEF_EALIGN: a pointer off
+ * the 4-byte grid. */
+int ief_cfg_ddim_step_prox_f32(const float* eps_u, const float* eps_c, const float* x, float* x_out, float* x0_out, const float* coef,
+                               const float* thres, const float* z0, long long n, long long row_elems, int h, int w, int mode,
+                               int radius, void* stream);
 /* sinusoidal timestep embedding, flip_sin_to_cos, shift 0: out fp16 [B][dim] = [cos | sin] */
 int ief_timestep_embedding_f16(const float* t, ief_half* out, int B, int dim, void* stream);
 /* out = a + b elementwise on fp16 (residual add when a hook owns Attention.forward) */
