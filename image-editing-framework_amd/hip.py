@@ -935,7 +935,7 @@ def _edit_lists(edit_src, edit_slot, B, L, who="attn_cross_p2p"):
 
 
 def gemm(a, w, bias=None, residual=None, rowvec=None, rows_per_batch=0, out=None, out_scale=1.0, tile_hint=0, splits=1,
-         stages=2, geglu=False, ln=None, row_stats=False, col_stats=False):
+         stages=2, geglu=False, ln=None, row_stats=False, col_stats=False, w_act=False):
     """out[..., n] = (a[..., :] . w[n, :] + bias[n] + rowvec[row // rows_per_batch, n] + residual[..., n]) * out_scale
 
     a: fp16 [..., K] (last dim contiguous, uniform row stride); w: fp16 [N, K]; bias/rowvec fp32.
@@ -944,6 +944,8 @@ def gemm(a, w, bias=None, residual=None, rowvec=None, rows_per_batch=0, out=None
     rstd * (a . w - mean * colsum) + bias, i.e. LayerNorm(a) . W^T when w = W * gamma and bias carries beta . W^T.
     `col_stats=True` (a 1x1 projection over an NHWC activation): returns (out, ColStats | None) for the consuming GroupNorm.
     fp32 `a` / `w` (reference-precision mode) run on the fp32-input MFMA; LayerNorm folding does not exist there.
+    `w_act=True`: w is an ACTIVATION (the keys of an attention done by GEMM), not a weight: no planes are kept of it, and in the
+    split-operand mode the product runs on the fp32-input MFMA (`_gemm_f32`): no static split scale fits both operands.
     """
     if _is32(a):
         if ln is not None or row_stats:
@@ -952,7 +954,7 @@ def gemm(a, w, bias=None, residual=None, rowvec=None, rows_per_batch=0, out=None
             o = _gemm_f32(a, w, bias=bias, out=out, out_scale=out_scale, geglu=True)       # GEGLU in the GEMM's epilogue
             return (o, None) if col_stats else o
         o = _gemm_f32(a, w, bias=bias, residual=residual, rowvec=rowvec, rows_per_batch=rows_per_batch,
-                      out=None if geglu else out, out_scale=out_scale)
+                      out=None if geglu else out, out_scale=out_scale, w_act=w_act)
         if geglu:
             o = geglu_il(o, out=out)
         return (o, None) if col_stats else o
@@ -1078,10 +1080,10 @@ def conv3x3(x, w, bias=None, x2=None, stride=1, upsample=False, rowvec=None, res
     return (out, cst) if col_stats else out
 
 
-def _splits_f32(lib, conv, M, N, K):
+def _splits_f32(lib, conv, M, N, K, exact=False):
     """split-K count (1: none) for the fp32 GEMM when M x N alone gives too few 128-row tiles for the 256 CUs (the 16x16 / 8x8 levels):
-    aim at ~512 workgroups, every slice keeping >= 4 K tiles of 32"""
-    x3 = _F32_CONTRACT == "x3"
+    aim at ~512 workgroups, every slice keeping >= 4 K tiles of 32.  exact: the launch takes the fp32-input MFMA in either mode"""
+    x3 = _F32_CONTRACT == "x3" and not exact
     nk = -(-K // 32)
     if x3:      # 128 x 80 tiles, two workgroups per CU: split below 1.5 per CU, towards 2 per CU (measured: without the split the
         # 32x32 / 16x16 levels run 1.5-2x slower than the reducer launches cost); 128 x 160 tiles, one 8-wave workgroup per CU:
@@ -1100,9 +1102,14 @@ def _splits_f32(lib, conv, M, N, K):
     return splits
 
 
-def _gemm_f32(a, w, bias=None, residual=None, rowvec=None, rows_per_batch=0, out=None, out_scale=1.0, transb=False, geglu=False):
+def _gemm_f32(a, w, bias=None, residual=None, rowvec=None, rows_per_batch=0, out=None, out_scale=1.0, transb=False, geglu=False,
+              w_act=False, a_map=False):
     """fp32 out[..., n] = (a . w[n] + bias[n] + rowvec[row // rows_per_batch, n] + residual[..., n]) * out_scale;
-    transb: w is [K, N] (rows along K) instead of [N, K]"""
+    transb: w is [K, N] (rows along K) instead of [N, K], an activation; a_map: a is a softmax map (entries <= 1), split at
+    the maps' scale; w_act: w [N, K] is an activation too (scores q k^T by GEMM).  Neither operand of that product has a
+    static range: at the weights' scale a key of 256 overflowed the hi half (NaN), at the activations' scale queries of ~2^-8
+    against keys of ~10^3 kept 2^-25 absolute resolution and the block missed its bound.  It runs on the fp32-input MFMA in
+    both fp32-storage modes"""
     lib = load()
     M, K, lda = _rows_ld32(a, "a")
     _act32(w, "w")
@@ -1122,20 +1129,24 @@ def _gemm_f32(a, w, bias=None, residual=None, rowvec=None, rows_per_batch=0, out
     p.A, p.W, p.Out = a.data_ptr(), w.data_ptr(), out.data_ptr()
     p.M, p.N, p.K, p.lda, p.ldw, p.ldo = M, N, K, lda, w.stride(0), ldo
     p.out_scale, p.transb = out_scale, 1 if transb else 0
-    splits = 1 if geglu else _splits_f32(lib, False, M, N, K)
+    exact = w_act and not transb and not geglu
+    splits = 1 if geglu else _splits_f32(lib, False, M, N, K, exact=exact)
     ws = _fill_epilogue(p, _rows_ld32, "gemm", M, N, a.device, bias, rowvec, rows_per_batch, residual, splits)     # noqa: F841  (keeps the slabs alive until the launch is queued)
-    kn = _set_x3(p, X3_SCALE_ACT, X3_SCALE_ACT if transb else X3_SCALE_W,        # transb: activation x activation
-                 w if (not transb and w.is_contiguous()) else None)
+    kn = "igemm_f32_kernel" if exact else _set_x3(p, X3_SCALE_PROB if a_map else X3_SCALE_ACT,
+                                                  X3_SCALE_ACT if transb else X3_SCALE_W,        # transb: activation x activation
+                                                  w if (not transb and w.is_contiguous()) else None)
     nbytes = 4.0 * (M * K + N * K + M * N * (2 if residual is not None else 1))
     with _Timed(f"{kn}<false, {'true' if transb else 'false'}>" + (f" {M}x{N}x{K} s{p.splits}" if PROF_SHAPES else ""), 2.0 * M * N * K, nbytes):
         _check(lib.ief_gemm_f32(byref(p), _stream()), "ief_gemm_f32")
     return out
 
 
-def gemm_nt(a, b, out=None):
-    """out = a @ b for a [M, K], b [K, N] (no transposed copy of b on the fp32 path)"""
+def gemm_nt(a, b, out=None, a_map=False):
+    """out = a @ b for a [M, K], b [K, N] (no transposed copy of b on the fp32 path).  `a_map=True`: a is a softmax map
+    (entries <= 1); the split-operand mode then splits it at X3_SCALE_PROB as the fused attention kernels do (at scale 1
+    the lo half of a probability below 2^-3 is an fp16 subnormal: at 4096 flat keys P.V was 1e-4 off, 25 x the mode's bound)"""
     if _is32(a):
-        return _gemm_f32(a, b, out=out, transb=True)
+        return _gemm_f32(a, b, out=out, transb=True, a_map=a_map)
     return gemm(a, transpose(b.contiguous()), out=out)
 
 

@@ -165,9 +165,9 @@ class _MidAttention:
         out = torch.empty(B, N, C, dtype=x.dtype, device=x.device)
         for b in range(B):
             q, k, v = qkv[b, :, :C], qkv[b, :, C:2 * C], qkv[b, :, 2 * C:]
-            probs = hip.gemm(q, k, out_scale=C ** -0.5)                 # [N, N] scores
+            probs = hip.gemm(q, k, out_scale=C ** -0.5, w_act=True)     # [N, N] scores; k is an activation, not a weight
             hip.softmax_rows_(probs)
-            hip.gemm_nt(probs, v, out=out[b])                            # P @ V
+            hip.gemm_nt(probs, v, out=out[b], a_map=True)                # P @ V, probabilities at the maps' split scale
         y = hip.gemm(out, self.wo, bias=self.bo, residual=x.reshape(B, N, C))
         return y.reshape(B, H, W, C), None
 
