@@ -107,9 +107,15 @@ __global__ __launch_bounds__(768) void conv3x3_halo_x3p_kernel(const IefGemmX3pP
             const char* g = ok ? an_src + ((long long)pl * an_pl + (long long)((unsigned)ms * an_cs + an_c0) * 2 + st_chunk) : zp;
             glds16(g, (half_t*)(smem + (exists ? pl * AD + buf_off + q * 1024 : DUMP)));
         };
-        const long long w_lane = (long long)(n0 + (lane >> 2)) * p.K * 2 + st_chunk;
+        // weight piece q of a plane: rows n0 + 16 q .. + 15, K tile kt = tap (Ctot / 32) + cb.  Row-major: byte (n K + 32 kt) 2; tiled
+        // (p.w_tiled, ief_x3_tile_weights): (((n >> 2) (K / 32) + kt) 4 + (n & 3)) 64 -- 16 rows further is 32 K bytes in both
+        // orders (n0 and 16 q are multiples of 4), a K tile further 64 or 256 bytes
+        const int kt_shift = p.w_tiled ? 8 : 6;
+        const long long w_lane = p.w_tiled
+            ? (long long)((n0 >> 2) + (lane >> 4)) * (p.K / BK) * 256 + ((lane >> 2) & 3) * 64 + st_chunk
+            : (long long)(n0 + (lane >> 2)) * p.K * 2 + st_chunk;
         auto issue_b = [&](int cb, int tap, bool on, int slot_off) {
-            const long long k0 = (long long)(tap * Ctot + cb * BK) * 2;
+            const long long k0 = (long long)(tap * ncb + cb) << kt_shift;
 #pragma unroll
             for (int j = 0; j < 3; ++j) {
                 const int v = l + NL * j;                     // weight piece: plane v / NPB, rows 16 (v % NPB) ..
@@ -355,9 +361,13 @@ __global__ __launch_bounds__(768) void conv3x3_halo_x3p_kernel_phase(const IefGe
             glds16(g, (half_t*)(smem + (exists ? pl * AD + buf_off + q * 1024 : DUMP)));
         };
         // this phase's slice of the weight planes: [phase][N][K], K = 4 Ctot
-        const long long w_lane = ((long long)blockIdx.z * p.N + n0 + (lane >> 2)) * p.K * 2 + st_chunk;
+        // (row-major or tiled, as the plain kernel; every phase matrix is tiled on its own)
+        const int kt_shift = p.w_tiled ? 8 : 6;
+        const long long w_lane = (long long)blockIdx.z * p.N * p.K * 2 + (p.w_tiled
+            ? (long long)((n0 >> 2) + (lane >> 4)) * (p.K / BK) * 256 + ((lane >> 2) & 3) * 64 + st_chunk
+            : (long long)(n0 + (lane >> 2)) * p.K * 2 + st_chunk);
         auto issue_b = [&](int cb, int tap, bool on, int slot_off) {
-            const long long k0 = (long long)(tap * Ctot + cb * BK) * 2;
+            const long long k0 = (long long)(tap * ncb + cb) << kt_shift;
 #pragma unroll
             for (int j = 0; j < 3; ++j) {
                 const int v = l + NL * j;                     // weight piece: plane v / NPB, rows 16 (v % NPB) ..

@@ -76,8 +76,11 @@ __global__ __launch_bounds__(64 * (WAVES_M * WAVES_N + NL)) void igemm_x3p_kerne
         nk = min(nk_all, kt_lo + per);
     }
 
-    // ---- staging state: one 64-bit source pointer per piece (plane offset included), advanced by one K tile (64 B) per stage.
-    // Out-of-range rows (M / N tails, padded taps) and filler pieces point at the zero page and do not advance.
+    // ---- staging state: one 64-bit source pointer per piece (plane offset included), advanced by one K tile per stage: 64 B, or
+    // 256 B for a weight piece in the tiled order (p.w_tiled, ief_x3_tile_weights: the K tiles of FOUR rows are interleaved, so the
+    // 16 lanes that fetch rows 4a .. 4a + 3 of a piece read two whole 128-byte lines instead of four half lines; the LDS image is
+    // the same).  Out-of-range rows (M / N tails, padded taps) and filler pieces point at the zero page and do not advance.
+    const unsigned wstep = p.w_tiled ? 8 * BK : 2 * BK;                              // wave-uniform
     const int prow = lane >> 2;                                                     // row of this lane inside a piece
     const unsigned kcb = (unsigned)(XP_LANE_CHUNK(lane) * 16);                         // chunk FETCHED for LDS slot lane & 3
     const char* ptr[G];
@@ -124,8 +127,9 @@ __global__ __launch_bounds__(64 * (WAVES_M * WAVES_N + NL)) void igemm_x3p_kerne
         } else {
             const int n = n0 + xp_perm_col<WN>(16 * blk + prow, p.geglu != 0);     // column order: x3p_common.h
             if (n < p.N) {
-                ptr[j] = (const char*)p.W + ((long long)plane[j] * p.planeW + (long long)n * p.ldw) * 2 + kcb + (long long)kt_lo * (BK * 2);
-                step[j] = BK * 2;
+                const long long wrow = p.w_tiled ? (long long)(n >> 2) * (nk_all * (8 * BK)) + (n & 3) * (2 * BK) : (long long)n * p.ldw * 2;
+                ptr[j] = (const char*)p.W + (long long)plane[j] * p.planeW * 2 + wrow + kcb + (long long)kt_lo * wstep;
+                step[j] = wstep;
             }
         }
     }
@@ -182,7 +186,7 @@ __global__ __launch_bounds__(64 * (WAVES_M * WAVES_N + NL)) void igemm_x3p_kerne
         for (int j = 0; j < G; ++j) {
             half_t* dst = (swave + NSW * j < P) ? base + NSW * j * (16 * BK) : smem + DUMP;        // wave-uniform
             glds16(ptr[j], dst);
-            if constexpr (TN > 5 && !CONV) ptr[j] += ((stepmask >> j) & 1u) ? BK * 2 : 0;      // the wide tile has no register for step[]
+            if constexpr (TN > 5 && !CONV) ptr[j] += ((stepmask >> j) & 1u) ? (isA[j] ? 2 * BK : wstep) : 0;      // the wide tile has no register for step[]
             else ptr[j] += step[j];
         }
         if constexpr (KCAT) {
@@ -505,6 +509,32 @@ extern "C" int ief_x3_split_act(const float* x, ief_half* planes, long long plan
     return IEF_OK;
 }
 
+// weight planes [2][N][K] -> the tiled order of the header (ief_x3_tile_weights): one 16-byte chunk per thread, indexed by its
+// DESTINATION (coalesced stores; the loads of 16 consecutive threads are four 64-byte runs)
+__global__ __launch_bounds__(256) void x3_tile_weights_kernel(const half_t* __restrict__ src, half_t* __restrict__ dst, int N, int K) {
+    const int nk = K / XP_BK;
+    const long long per_plane = (long long)N * K / 8, total = 2 * per_plane;
+    for (long long o = (long long)blockIdx.x * 256 + threadIdx.x; o < total; o += (long long)gridDim.x * 256) {
+        const long long pl = o / per_plane, r = o - pl * per_plane;
+        const int c = (int)(r & 3), rr = (int)((r >> 2) & 3);
+        const long long blk = r >> 4, n4 = blk / nk;
+        const int kt = (int)(blk - n4 * nk);
+        const long long n = n4 * 4 + rr;
+        *(half8*)(dst + o * 8) = *(const half8*)(src + pl * N * K + n * K + kt * XP_BK + c * 8);
+    }
+}
+extern "C" int ief_x3_tile_weights(const ief_half* planes_rowmajor, ief_half* tiled, int N, int K, void* stream) {
+    if (!planes_rowmajor || !tiled) return IEF_EINVAL;
+    if (N <= 0 || K <= 0 || (N & 3) || (K % XP_BK)) return IEF_ESHAPE;
+    if (((uintptr_t)planes_rowmajor & 15) || ((uintptr_t)tiled & 255)) return IEF_EALIGN;
+    long long grid = ((long long)N * K / 4 + 255) / 256;
+    if (grid > 16384) grid = 16384;
+    hipLaunchKernelGGL(x3_tile_weights_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, (const half_t*)planes_rowmajor,
+                       (half_t*)tiled, N, K);
+    IEF_LAUNCH_CHECK();
+    return IEF_OK;
+}
+
 extern "C" int ief_gemm_x3p_tile_bm(int tile) {
     switch (tile) {
         case 1: case 2: case 3: case 7: return 128;
@@ -551,6 +581,10 @@ extern "C" int ief_gemm_x3p(const IefGemmX3pParams* pp, void* stream) {
     if (p.splits > 1 && (!p.ws || p.splits > 64 || p.geglu || p.rstat_out || p.cstat_out)) return IEF_EINVAL;
     if (!(p.inv_scale > 0.f)) return IEF_EINVAL;
     if ((p.ldw & 7) || (p.planeW & 7) || ((uintptr_t)p.W & 15)) return IEF_EALIGN;
+    if (p.w_tiled) {        // planes in the order of ief_x3_tile_weights (tile 13: the four phase matrices, each tiled on its own)
+        if (p.planeW != (long long)(p.tile == 13 ? 4 : 1) * p.N * p.K) return IEF_ESHAPE;
+        if ((uintptr_t)p.W & 255) return IEF_EALIGN;
+    }
     if (p.Out && ((p.ldo & 3) || ((uintptr_t)p.Out & 15))) return IEF_EALIGN;
     if (p.OutP && ((p.ldp & 3) || (p.planeO & 3) || ((uintptr_t)p.OutP & 7))) return IEF_EALIGN;
     if ((p.bias && ((uintptr_t)p.bias & 15)) || (p.rowvec && ((uintptr_t)p.rowvec & 15)) ||

@@ -527,7 +527,8 @@ class f32_contraction:
 
 
 # (data_ptr, shape, scale[, "phase"]) -> (weakref to the weight tensor, its _version, planes fp16 [2, N, K]; "phase": the phase form
-# [2, 4, N, 4 C] of an Upsample2D weight, x3_upsample_phase_planes).  The entry dies WITH the weight
+# [2, 4, N, 4 C] of an Upsample2D weight, x3_upsample_phase_planes; a further tag "tiles": the same planes in the tiled order of
+# ief_x3_tile_weights, x3_weight_tiles / x3_upsample_phase_tiles, kept BESIDE the row-major ones).  The entry dies WITH the weight
 # (weakref.finalize): a model that is dropped frees its planes (they are as large as the weights).  A captured graph bakes the
 # planes' address in: an in-place update of a weight after capture would replace the entry and free planes the graph still
 # reads, so weights are immutable once a graph over them exists (the weight broadcast runs before any forward).
@@ -578,6 +579,44 @@ def x3_upsample_phase_planes(w, scale=None):
     _x3_planes[key] = (weakref.ref(w), w._version, planes)
     weakref.finalize(w, _x3_planes.pop, key, None)
     return planes
+
+
+def _x3_tiles(w, key, planes):
+    """make and cache the tiled copy (`ief_x3_tile_weights`) of row-major weight planes [2, ..., K] (rows = everything between)"""
+    if planes is None or _capturing():
+        return None
+    lib = load()
+    k = planes.shape[-1]
+    tiled = torch.empty_like(planes)
+    _check(lib.ief_x3_tile_weights(planes.data_ptr(), tiled.data_ptr(), planes.numel() // (2 * k), k, _stream()), "ief_x3_tile_weights")
+    import weakref
+    _x3_planes[key] = (weakref.ref(w), w._version, tiled)
+    weakref.finalize(w, _x3_planes.pop, key, None)
+    return tiled
+
+
+def x3_weight_tiles(w, scale=None):
+    """the planes of `x3_weight_planes(w, scale)` in the TILED order the planes kernels fetch whole 128-byte lines from
+    (`ief_x3_tile_weights`, IefGemmX3pParams.w_tiled): fp16 [2, N, K] holding the same halves at other addresses, a bit-copy made
+    from the row-major planes at first use and cached beside them (same key plus a tag, dies with the weight).  N % 4 == 0 and
+    K % 32 == 0.  None while a graph is being captured and the copy does not exist yet."""
+    scale = X3_SCALE_W if scale is None else scale
+    key = (w.data_ptr(), tuple(w.shape), float(scale), "tiles")
+    hit = _x3_planes.get(key)
+    if hit is not None and hit[0]() is w and hit[1] == w._version:
+        return hit[2]
+    return _x3_tiles(w, key, x3_weight_planes(w, scale))
+
+
+def x3_upsample_phase_tiles(w, scale=None):
+    """`x3_upsample_phase_planes(w, scale)` [2, 4, Cout, 4 C] with each of the four phase matrices in the tiled order of
+    `x3_weight_tiles` (Cout % 4 == 0: the four matrices of a plane tile as ONE matrix of 4 Cout rows)"""
+    scale = X3_SCALE_W if scale is None else scale
+    key = (w.data_ptr(), tuple(w.shape), float(scale), "phase", "tiles")
+    hit = _x3_planes.get(key)
+    if hit is not None and hit[0]() is w and hit[1] == w._version:
+        return hit[2]
+    return _x3_tiles(w, key, x3_upsample_phase_planes(w, scale))
 
 
 def fold_linear_pair_ref(wp, w2, b2=None, bp=None):

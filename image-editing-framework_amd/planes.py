@@ -104,6 +104,31 @@ def weight_planes(w):
     return t
 
 
+W_TILES = os.environ.get("IEF_X3P_WTILES", "1") == "1"      # 0: the launches read the row-major weight planes (A/B runs; the same bits)
+
+
+def weight_tiles(w):
+    """an fp32 weight's cached planes [2, N, K] in the tiled order (`hip.x3_weight_tiles`: what `gemm` / `conv3x3` launch on)"""
+    t = hip.x3_weight_tiles(w, W_SCALE)
+    if t is None:
+        raise RuntimeError("tiled weight planes missing while capturing: run one eager forward first")
+    return t
+
+
+def _weight_arg(p, w, N, K, phase=False):
+    """fill W / planeW / ldw / w_tiled of a launch from the weight's cached planes: the tiled order when W_TILES is on and the
+    shape has one (the library refuses the other shapes anyway), the row-major planes otherwise; returns the tensor"""
+    tiled = W_TILES and N % 4 == 0 and K % 32 == 0
+    if phase:
+        wp = hip.x3_upsample_phase_tiles(w, W_SCALE) if tiled else hip.x3_upsample_phase_planes(w, W_SCALE)
+        if wp is None:
+            raise RuntimeError("phase weight planes missing while capturing: run one eager forward first")
+    else:
+        wp = weight_tiles(w) if tiled else weight_planes(w)
+    p.W, p.planeW, p.ldw, p.w_tiled = wp.data_ptr(), wp.stride(0), K, 1 if tiled else 0
+    return wp
+
+
 # ---- plan: tile id and split-K per (M, N, K); tuned table first (tuned_plans_x3.json), heuristic otherwise
 _PLAN_FILE = os.environ.get("IEF_PLAN_FILE_X3") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "tuned_plans_x3.json")
 _plans = None
@@ -206,8 +231,12 @@ def _autotune(key, cands, run, w):
     wc = hip._cold_copies(w)
     for x in wc:
         weight_planes(x)
+        if W_TILES:
+            hip.x3_weight_tiles(x, W_SCALE)
         if any(t == 13 for t, _ in cands):
             hip.x3_upsample_phase_planes(x, W_SCALE)
+            if W_TILES:
+                hip.x3_upsample_phase_tiles(x, W_SCALE)
     best = None
     for t, sp in cands:
         try:
@@ -219,6 +248,8 @@ def _autotune(key, cands, run, w):
     for x in wc[1:]:
         hip._x3_planes.pop((x.data_ptr(), tuple(x.shape), float(W_SCALE)), None)
         hip._x3_planes.pop((x.data_ptr(), tuple(x.shape), float(W_SCALE), "phase"), None)
+        hip._x3_planes.pop((x.data_ptr(), tuple(x.shape), float(W_SCALE), "tiles"), None)
+        hip._x3_planes.pop((x.data_ptr(), tuple(x.shape), float(W_SCALE), "phase", "tiles"), None)
     if best is not None:
         _plan_table()[key] = (best[1], best[2])
     return best
@@ -316,12 +347,11 @@ def gemm(a, w, bias=None, residual=None, rowvec=None, rows_per_batch=0, out=None
     N = w.shape[0]
     if w.dim() != 2 or w.shape[1] != K:
         raise ValueError(f"planes.gemm: K mismatch {tuple(w.shape)} vs {K}")
-    wp = weight_planes(w)
     p = IefGemmX3pParams()
     p.A, p.planeA, p.lda = a.t.data_ptr(), a.plane, lda
     if a2 is not None:
         p.A2, p.planeA2, p.lda2, p.K1 = a2.t.data_ptr(), a2.plane, lda2, K1
-    p.W, p.planeW, p.ldw = wp.data_ptr(), wp.stride(0), K
+    wp = _weight_arg(p, w, N, K)        # noqa: F841 (alive until queued)
     No = N // 2 if geglu else N
     o32, op = _out_args(p, M, No, out, out_planes, a.device, a.shape[:-1])
     p.M, p.N, p.K = M, N, K
@@ -425,19 +455,16 @@ def conv3x3(x, w, bias=None, x2=None, stride=1, upsample=False, rowvec=None, res
         if not phase_ok:
             raise ValueError("planes.conv3x3: this geometry has no phase form (tile 13)")
         p.splits = min(p.splits, (C1 + C2) // 32)
-        wp = hip.x3_upsample_phase_planes(w, W_SCALE)       # [2, 4, Cout, 4 C]: the 9-tap planes of this weight are never made
-        if wp is None:
-            raise RuntimeError("phase weight planes missing while capturing: run one eager forward first")
         K = 4 * (C1 + C2)
         p.K = K
+        wp = _weight_arg(p, w, Cout, K, phase=True)       # noqa: F841  [2, 4, Cout, 4 C]: the 9-tap planes of this weight are never made
     else:
         if p.tile in (11, 12):
             if not halo_ok:
                 raise ValueError("planes.conv3x3: this geometry has no halo form (tile 11 / 12)")
             p.tile = 12 if upsample else 11
             p.splits = min(p.splits, (C1 + C2) // 32)
-        wp = weight_planes(w)
-    p.W, p.planeW, p.ldw = wp.data_ptr(), wp.stride(0), K
+        wp = _weight_arg(p, w, Cout, K)       # noqa: F841
     ws = hip._fill_epilogue(p, hip._rows_ld32, "planes.conv3x3", M, Cout, x.device, bias, rowvec, g.rows_per_batch, residual, p.splits)     # noqa: F841
     nbytes = 4.0 * (B * Hp * Wp * (C1 + C2) + M * (CE1 + CE2) + Cout * K + M * Cout * ((1 if o32 is not None else 0) + (1 if op is not None else 0) + (1 if residual is not None else 0)))
     # (tile 13: K is 4 (C1 + C2) here, so the FLOPs, weight bytes and staged bytes below are the four taps the launch executes)

@@ -689,8 +689,20 @@ typedef struct IefGemmX3pParams {
      * multiples of 8 (IEF_EALIGN); tiles 1, 3, 4 and 6 only, not with conv, geglu or rstat_in (IEF_EINVAL).  Split-K ranges may
      * straddle K1. */
     int K1, lda2;
+    /* w_tiled != 0: W points at the planes in the TILED order of ief_x3_tile_weights (the same halves, other addresses: every
+     * result keeps its bits).  planeW must be N K (tile 13: 4 N K, each phase matrix tiled on its own; IEF_ESHAPE) and W 256-byte
+     * aligned (IEF_EALIGN); ldw is not used beyond its checks. */
+    int w_tiled;
 } IefGemmX3pParams;
 int ief_gemm_x3p(const IefGemmX3pParams* p, void* stream);
+/* Weight planes [2][N][K] (row-major, from any producer: ief_x3_split_weights, one phase matrix of ief_x3_upsample_phase_weights,
+ * the planes of a folded pair) -> the same halves in the order the LDS-DMA pieces of the planes kernels fetch whole 128-byte lines
+ * from: with nk = K / 32, the half at plane pl, row n, column 32 kt + kk goes to half index
+ *     pl N K + ((((n >> 2) nk + kt) 4 + (n & 3)) 32 + kk)
+ * -- four consecutive rows x one 32-deep K tile are 256 contiguous, 256-byte aligned bytes, the next K tile of the same four rows
+ * follows.  A piece's 16 lanes that fetch rows 4a .. 4a + 3 then read two whole lines instead of four half lines.  A plain copy
+ * in 16-byte vectors.  N % 4 or K % 32: IEF_ESHAPE; planes_rowmajor not 16-byte or tiled not 256-byte aligned: IEF_EALIGN. */
+int ief_x3_tile_weights(const ief_half* planes_rowmajor, ief_half* tiled, int N, int K, void* stream);
 /* Two linears with nothing non-linear between them, folded into one (the tail of a Transformer2DModel: FeedForward.net[2] followed
  * by proj_out):  (g W2^T + b2 + h) Wp^T + bp = [g | h] [Wp W2 | Wp]^T + (Wp b2 + bp).  wp fp32 [C][C], w2 fp32 [C][K], b2 / bp fp32
  * [C] or NULL -> wcat fp32 [C][K + C] = [Wp W2 | Wp] and bcat fp32 [C] = Wp b2 + bp; every sum is accumulated in fp64 in
